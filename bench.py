@@ -11,7 +11,12 @@ by torch.distributed.run) every rank owns its own contiguous block of frames (we
 step ends with the single exchange of the path: the gather of the packed track records on rank 0
 (RCCL over xGMI).  value = markers produced by all ranks / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can
+carry: the parity gates (the whole timed batch against the exhaustive walk, a prefix against the C oracle), the CPU
+baselines, latencies, the blob stage, the 4 x 4 and 64 x 256 sub-records and bundle adjustment.  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -651,6 +656,35 @@ def full_batch_parity(local_rank, dev, stream, rig, M, gate, g_cap, d_blobs, d_c
         walk.close()
 
 
+DUMP_SAMPLE_FRAMES = 4096          # frames whose points --dump-outputs writes (a fixed, seeded sample)
+DUMP_SAMPLE_BYTES = 32 << 20       # ... and at most this many bytes of points (64 x 256: a few hundred frames)
+DUMP_ALL_FRAMES = 1 << 20          # per-frame counts are written for every frame up to this many, else at the same sample
+
+
+def dump_outputs(out_dir, F, K, C, d_xyz, d_err, d_corr, d_nout, d_status, d_ncand):
+    """--dump-outputs: what the timed path left in its output buffers after its last step, one DIR/<name>.npy per array.
+    The points (xyz, err, corr) are written for a sample of frames drawn with a fixed seed (frames.npy: their indices),
+    packed in frame order -- the first n_out[f] slots of each sampled frame f whose status is 0, nothing of the padding
+    past n_out nor of a frame the path flags (its status is written).  Counts as float64 (exact), corr as float32 (exact),
+    xyz / err as computed.  At most 64 MB in all (32 MiB of points + 24 MiB of per-frame counts)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    S = int(min(F, DUMP_SAMPLE_FRAMES, max(1, DUMP_SAMPLE_BYTES // (K * (3 * 8 + 8 + 4 * C)))))
+    frames = np.sort(np.random.default_rng(20240607).choice(F, size=S, replace=False)) if S < F else np.arange(F)
+    idx = torch.from_numpy(frames).to(d_nout.device)
+    n_out, status = d_nout.cpu().numpy(), d_status.cpu().numpy()
+    valid = (np.arange(K)[None, :] < n_out[frames][:, None]) & (status[frames] == 0)[:, None]
+    xyz = d_xyz.index_select(0, idx).cpu().numpy()[valid]
+    err = d_err.index_select(0, idx).cpu().numpy()[valid]
+    corr = d_corr.index_select(0, idx).cpu().numpy()[valid].astype(np.float32)
+    per_frame = slice(None) if F <= DUMP_ALL_FRAMES else frames
+    arrays = {"frames": frames.astype(np.float64), "xyz": xyz.astype(np.float64), "err": err.astype(np.float64), "corr": corr,
+              "n_out": n_out[per_frame].astype(np.float64), "status": status[per_frame].astype(np.float64),
+              "n_cand": d_ncand.cpu().numpy()[per_frame].astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def config_record(name, local_rank, dev, stream, steps, warmup, frames=0):
     """A sub-record of the default line for one of BASELINE.json's other frame configs (configs[1] = "4x4", configs[4] =
     "64x256"): the same hot-path call as the headline (mocap_match_triangulate_dev_auto, inputs resident in HBM, HIP events on
@@ -843,6 +877,11 @@ def main():
                     help="N > 1: sub-batches a rank's shard is cut into per step, so that the gather of chunk k travels while chunk "
                          "k + 1 is computed inside ONE step (0 = automatic: 1 = the whole shard at once when the run has >= 4 steps, whose "
                          "exchanges travel under the NEXT step's kernels; a shorter run: 4, or 2 at 64 x 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity gates, CPU baselines, latencies, blob stage, the 4x4 / 64x256 "
+                         "sub-records and bundle adjustment (the --no-* options below leave parts of that out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's shard) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ba", action="store_true")
     ap.add_argument("--no-blobs", action="store_true")
@@ -999,11 +1038,13 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, F, K_MAX, C, d_xyz, d_err, d_corr, d_nout, d_status, d_ncand)
 
     # parity at the scale of the metric (round-5 verdict, item 1b): the batch the timed run just produced against the exhaustive
-    # walk of the same batch, every bit of every frame, on the device.  Outside the timed region; on every rank.
+    # walk of the same batch, every bit of every frame, on the device.  Outside the timed region; on every rank; --full only.
     full_par = None
-    if not wl["stress"] and not args.no_full_parity:
+    if args.full and not wl["stress"] and not args.no_full_parity:
         from mocap_core import devcheck
         shipped = devcheck.FrameOutputs.__new__(devcheck.FrameOutputs)
         shipped.F, shipped.K, shipped.C = F, K_MAX, C
@@ -1104,7 +1145,8 @@ def main():
                                                        "not work executed", v_mean=v_mean,
                                   candidates_per_launch=float(n_cand.sum())),
         }
-        if world == 1:
+        line["full"] = bool(args.full)
+        if world == 1 and args.full:
             # parity gate next to the number: a prefix of the very batch that was timed, vs the oracle
             from oracle import c_oracle
             nchk = 300

@@ -22,11 +22,11 @@ for m in skip fold; do
   tail -1 $O/blob_$m.log | cut -c1-200
 done
 cd $R
-timeout 900 python bench.py > $O/bench_final.log 2>&1; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_final.log 2>&1; echo "bench rc=$?"
 grep '^{"metric"' $O/bench_final.log > $O/bench_line_final.json
-timeout 400 python bench.py --workload 64x256 --frames 12500 --steps 3 --warmup 1 > $O/bench_64x256.log 2>&1; grep '^{"metric"' $O/bench_64x256.log > $O/bench_line_64x256.json
-MOCAP_BENCH_EXCHANGE=1 timeout 400 python bench.py --workload 64x256 --frames 12500 --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_64x256_exchange.log 2>&1; grep '^{"metric"' $O/bench_64x256_exchange.log > $O/bench_line_64x256_exchange.json
-MOCAP_BENCH_EXCHANGE=1 timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-ba --no-blobs --no-latency --no-configs > $O/bench_8x16_exchange.log 2>&1; grep '^{"metric"' $O/bench_8x16_exchange.log > $O/bench_line_8x16_exchange.json
+timeout 400 python bench.py --full --workload 64x256 --frames 12500 --steps 3 --warmup 1 > $O/bench_64x256.log 2>&1; grep '^{"metric"' $O/bench_64x256.log > $O/bench_line_64x256.json
+MOCAP_BENCH_EXCHANGE=1 timeout 400 python bench.py --full --workload 64x256 --frames 12500 --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_64x256_exchange.log 2>&1; grep '^{"metric"' $O/bench_64x256_exchange.log > $O/bench_line_64x256_exchange.json
+MOCAP_BENCH_EXCHANGE=1 timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-ba --no-blobs --no-latency --no-configs > $O/bench_8x16_exchange.log 2>&1; grep '^{"metric"' $O/bench_8x16_exchange.log > $O/bench_line_8x16_exchange.json
 python - <<'PY'
 import json
 O="gpurun_out/r06/final/"

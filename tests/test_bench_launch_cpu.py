@@ -38,6 +38,14 @@ def test_bench_gpus2_dry_run_at_the_stress_shape():
     assert line["config"]["exchange"]["payload_checksums_match"] is True
 
 
+def test_bench_full_and_dump_outputs_options():
+    """--full (everything beyond the headline figure) and --dump-outputs DIR are options of the command line."""
+    p = _run({}, "--help")
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = _run({"MOCAP_BENCH_DRY": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "8", "--full")
+    assert p.returncode == 0, p.stderr[-2000:]
+
+
 def test_bench_world_size_mismatch_is_an_error_not_a_silent_single_rank_run():
     p = _run({"MOCAP_BENCH_DRY": "1", "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"}, "--gpus", "2")
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)

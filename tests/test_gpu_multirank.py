@@ -40,7 +40,8 @@ def test_bench_gpus2_starts_its_own_ranks_on_the_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["MOCAP_DIST_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "2000", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-ba", "--no-blobs", "--no-latency"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-ba", "--no-blobs", "--no-latency"], env=env, capture_output=True, text=True,
+                       timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1
