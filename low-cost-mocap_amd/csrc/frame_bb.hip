@@ -56,16 +56,8 @@ constexpr int kBBRecs = kBBThreads + 64;  // surviving blocks queued between two
 // step its LDS layout sizes the block cache for.  Four everywhere (128 VGPRs; 33-40 KB of LDS) except the 8-camera, 16-blob,
 // 48-slot layout -- the bench's -- whose 29.2 KB leave room for FIVE frames per CU: 96 VGPRs (52 spilled instead of 22, +6 % per
 // frame) and a block cache of 161 entries instead of 385, and still 4.50 -> 4.31 ms per 100 k frames (profiles/r06_wide_experiments.txt, (15)).
-#ifndef MOCAP_BB_WAVES_PER_EU
-#define MOCAP_BB_WAVES_PER_EU 4
-#endif
-#ifndef MOCAP_BB_WAVES_PER_EU_48
-#define MOCAP_BB_WAVES_PER_EU_48 5
-#endif
-constexpr int bb_wg_per_cu(int RL) { return RL == 48 ? MOCAP_BB_WAVES_PER_EU_48 : MOCAP_BB_WAVES_PER_EU; }
-#ifndef MOCAP_BB_LDS_SLACK
-#define MOCAP_BB_LDS_SLACK 1024  // (measured: 512 keeps the occupancy step as well, 0 does not)
-#endif
+constexpr int bb_wg_per_cu(int RL) { return RL == 48 ? 5 : 4; }
+constexpr int kBBLdsSlack = 1024;  // (measured: 512 keeps the occupancy step as well, 0 does not)
 struct BBLayout {
   size_t bxy, bxy_nx, cnt_nx, bt, rbound, seedkey, slot_key, claimw, recs, rpk, scr, scr_bytes, goff, gcnt, outslot, boff, bnb, seedgh, slot_g, cnt,
       misc, bpl, nh, hits, act, root_blob, root_cam, nact, bnl, bv, bcache, bpk, total;
@@ -118,7 +110,7 @@ struct BBLayout {
     ncache = 0;
     const size_t per_entry = 8 + 8 * (size_t)CW;
     for (int per_cu = wg_per_cu; per_cu >= 1; per_cu--) {
-      const size_t lim = ((size_t)160 * 1024 / per_cu - MOCAP_BB_LDS_SLACK) / 256 * 256;  // (slack: allocation granule, other LDS users)
+      const size_t lim = ((size_t)160 * 1024 / per_cu - kBBLdsSlack) / 256 * 256;  // (slack: allocation granule, other LDS users)
       if (lim >= o + per_entry * 64) {
         const size_t n = (lim - o) / per_entry;
         ncache = (int)(n > 1024 ? 1024 : n);
@@ -207,19 +199,11 @@ struct BBCamTables<0> {
 // runs at 0; everything that holds the other waves of its workgroup at a barrier runs above it: the single-wave stretches
 // (chain bookkeeping, scans) at 3, the rest of the matching and the output at 2, the seed pass at 1.  A frame's serial
 // depth then costs what it costs alone, not what it costs sharing its SIMD's issue slots with three evaluations:
-// 4.70 -> 4.50 ms per 100 k frames of 8 x 16 (profiles/r06_wide_experiments.txt, (14); MOCAP_BB_PRIO=0: without).
-#ifndef MOCAP_BB_FRESH_TID
-#define MOCAP_BB_FRESH_TID 1
-#endif
-#ifndef MOCAP_BB_PRIO
-#define MOCAP_BB_PRIO 1
-#endif
+// 4.70 -> 4.50 ms per 100 k frames of 8 x 16 (profiles/r06_wide_experiments.txt, (14)).
 enum { kPrioEval = 0, kPrioSeed = 1, kPrioPhase = 2, kPrioSerial = 3 };
 template <int P>
 __device__ __forceinline__ void bb_prio() {
-#if MOCAP_BB_PRIO
   __builtin_amdgcn_s_setprio(P);
-#endif
 }
 
 // ML, RL: the layout's blobs per camera and root slots when they are known at compile time (with CT: every LDS array
@@ -236,15 +220,13 @@ struct BBState {
   int tid, lane, wave;
   // The lane's number taken afresh (an empty asm the optimiser cannot see through): what a phase derives from it -- LDS addresses,
   // (root, camera) pair indices, masks -- is computed in that phase instead of once before the frame loop, where it would sit in a
-  // register for the whole frame, i.e. in scratch (MOCAP_BB_FRESH_TID=0: without)
+  // register for the whole frame, i.e. in scratch (Makefile: FRAME_BB_FLAGS has the measurements)
   __device__ __forceinline__ void fresh_tid() {
-#if MOCAP_BB_FRESH_TID
     int t = tid;
     asm volatile("" : "+v"(t));
     tid = t;
     lane = t & 63;
     wave = t >> 6;
-#endif
   }
   __device__ __forceinline__ int cn() const { return CT > 0 ? CT : C_; }
   double* bt;

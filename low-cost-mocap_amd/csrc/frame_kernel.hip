@@ -43,43 +43,40 @@
 #include "mocap_device.hpp"
 #include "kernels.hpp"
 #include "frame_common.hpp"
-
-#ifndef MOCAP_WIDE_BATCH
-#define MOCAP_WIDE_BATCH 8  // wide frames: observations fetched ahead per pass of the candidate evaluation (4: 214.6 k, 8: 216.7 k frames/s)
-#endif
+#include <type_traits>
 
 namespace mocap {
 
 // register budget: 4 waves per SIMD (<= 128 VGPRs); the LDS footprint at 8 x 16 allows 4 workgroups
 // of 256 lanes per CU, so both limits meet at 16 waves per CU
-// timing experiments only (results invalid): wide frames without the camera-0 pairs (1) / the chain's pairs (2) / the geometry of the candidate evaluation (4: groups are still loaded, walked and merged)
-#ifndef MOCAP_WIDE_DEBUG_SKIP
-#define MOCAP_WIDE_DEBUG_SKIP 0
+constexpr int kFrameWavesPerEU = 4;
+// wide frames: observations fetched ahead per pass of the candidate evaluation (4: 214.6 k, 8: 216.7 k frames/s)
+constexpr int kWideBatch = 8;
+// wide frames: a chain step with fewer new roots than this keeps the blobs in registers and broadcasts the roots (swept: 8 +2 %,
+// 0 +34 %, never = 24)
+constexpr int kWideChainT = 24;
+// wide frames: the rest of the chain over the cameras is matched speculatively in one pass (spec_begin) when at most this many
+// blobs are left unclaimed (every provisional root costs one broadcast round per camera: a marker no earlier camera saw -- some
+// 60 unclaimed blobs -- is cheaper as one sequential step)
+constexpr int kWideSpecT = 32;
+
+// The two translation units of this file differ in MOCAP_FRAME_TU_WIDE alone (csrc/frame_kernel_wide.hip defines it and emits the
+// wide variant's instantiations; this file emits the others).  What it changes besides which half is emitted:
+#ifdef MOCAP_FRAME_TU_WIDE
+constexpr bool kTuWide = true;
+#else
+constexpr bool kTuWide = false;
 #endif
-#ifndef MOCAP_WIDE_ACC
-#define MOCAP_WIDE_ACC 1  // (1: 32.4 -> 30.5 ms per 12 500 stress frames)
-#endif
-#ifndef MOCAP_WIDE_DEPTH_CUT
-#define MOCAP_WIDE_DEPTH_CUT 0
-#endif
-#ifndef MOCAP_WIDE_CHAIN_T
-#define MOCAP_WIDE_CHAIN_T 24  // wide frames: a chain step with fewer new roots than this keeps the blobs in registers and broadcasts the roots (swept: 8 +2 %, 0 +34 %, never = 24)
-#endif
-#ifndef MOCAP_WIDE_SPEC
-#define MOCAP_WIDE_SPEC 1  // wide frames: the rest of the chain over the cameras matched speculatively in one pass once few blobs are left unclaimed (0: camera by camera)
-#endif
-#ifndef MOCAP_WIDE_PAIR2
-#define MOCAP_WIDE_PAIR2 1  // wide frames: a (root, camera) pair with two candidates at different positions of a step is decided by its own lane
-#endif
-#ifndef MOCAP_WIDE_CAM1
-#define MOCAP_WIDE_CAM1 1  // wide frames: camera 1 first, its roots then ride with the camera-0 roots through cameras 2 .. C-1 (0: a chain step for them)
-#endif
-#ifndef MOCAP_WIDE_SPEC_T
-#define MOCAP_WIDE_SPEC_T 32  // ... at most this many (every provisional root costs one broadcast round per camera: a marker no earlier camera saw -- some 60 unclaimed blobs -- is cheaper as one sequential step)
-#endif
-#ifndef MOCAP_FRAME_WAVES_PER_EU
-#define MOCAP_FRAME_WAVES_PER_EU 4
-#endif
+// - the camera tables' pointers as scalar values of their own (FrameState::cv, split_cam_view below): wide only;
+constexpr bool kSplitCv = kTuWide;
+// - the lane's number taken afresh per phase (FrameState::fresh_tid): not wide -- the wide variant is compiled without machine
+//   LICM instead (Makefile: FRAME_WIDE_FLAGS);
+constexpr bool kFreshTid = !kTuWide;
+// - the issue priority of the phases (s_setprio at every frame_prio site, see csrc/frame_bb.hip): wide only -- the chain over the
+//   cameras with its single-wave stretches and the output above the camera-0 pass and the candidate evaluation of the CU's
+//   other frame: 24.1 -> 23.8 ms per 12 500 stress frames.
+constexpr bool kPhasePrio = kTuWide;
+constexpr int kPrioMatch = 0, kPrioChain = 1, kPrioSerial = 1, kPrioEval = 0, kPrioOut = 1;
 
 // Where the per-frame state lives.  Narrow frames (the realistic rigs: 8 cameras x 16 markers needs
 // 39 KB) keep everything in LDS.  Wide frames (up to 64 cameras x 256 blobs: the blobs alone are
@@ -163,13 +160,6 @@ size_t frame_ws_bytes(int C, int M, int R, int T, int H, bool wide, bool table) 
 // reloaded as the whole block (16 v_readlane per reload: the camera tables' pointers were reloaded that way inside the candidate
 // evaluation of the wide variant, at 17 places of its loops).  own_sgprs makes each pointer a 64-bit scalar value of its own.
 // (wide variant only: 25.4 -> 24.1 ms per 12 500 stress frames; the one-wave kernels of small frames measure the same either way)
-#ifndef MOCAP_SPLIT_CV
-#ifdef MOCAP_FRAME_TU_WIDE
-#define MOCAP_SPLIT_CV 1
-#else
-#define MOCAP_SPLIT_CV 0
-#endif
-#endif
 __device__ __forceinline__ uint32_t opaque_v(uint32_t x) {
   uint32_t r;
   asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "s"(x));
@@ -184,62 +174,44 @@ __device__ __forceinline__ Tp* own_sgprs(Tp* ptr) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)opaque_v((uint32_t)(u >> 32)));
   return (Tp*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
 }
-__device__ __forceinline__ CamView split_cam_view(const CamView& v) {
-  CamView c = v;
-  c.Pq = own_sgprs(v.Pq);
-  c.RT = own_sgprs(v.RT);
-  c.K4 = own_sgprs(v.K4);
-  c.F = own_sgprs(v.F);
-  return c;
+// FrameState::cv: a copy of the camera tables with pointers of their own (kSplitCv), else the kernel argument itself
+template <bool SPLIT = kSplitCv>
+__device__ __forceinline__ std::conditional_t<SPLIT, CamView, const CamView&> split_cam_view(const CamView& v) {
+  if constexpr (SPLIT) {
+    CamView c = v;
+    c.Pq = own_sgprs(v.Pq);
+    c.RT = own_sgprs(v.RT);
+    c.K4 = own_sgprs(v.K4);
+    c.F = own_sgprs(v.F);
+    return c;
+  } else {
+    return v;
+  }
 }
 
 // HEAVY (wide variant, re-submit pass only): roots over the candidate cap are exported to the heavy-root search instead of
 // flagging their frames -- a separate instantiation, so that the code does not weigh on the registers of the first pass
 // Every phase below is __forceinline__: the frame kernels are ONE body per instantiation.  (Round 6: a self-check build had
 // write_point outlined as a real function -- calls, a stack in scratch, and a barrier the ISA test could no longer prove safe.)
-#ifndef MOCAP_FRAME_FRESH_TID
-#define MOCAP_FRAME_FRESH_TID 1
-#endif
-#ifndef MOCAP_FRAME_PRIO_MATCH
-#define MOCAP_FRAME_PRIO_MATCH 0
-#endif
-#ifndef MOCAP_FRAME_PRIO_CHAIN
-#define MOCAP_FRAME_PRIO_CHAIN 0
-#endif
-#ifndef MOCAP_FRAME_PRIO_SERIAL
-#define MOCAP_FRAME_PRIO_SERIAL MOCAP_FRAME_PRIO_CHAIN
-#endif
-#ifndef MOCAP_FRAME_PRIO_EVAL
-#define MOCAP_FRAME_PRIO_EVAL 0
-#endif
-#ifndef MOCAP_FRAME_PRIO_OUT
-#define MOCAP_FRAME_PRIO_OUT 0
-#endif
-#define MOCAP_FRAME_PRIO_ANY (MOCAP_FRAME_PRIO_MATCH | MOCAP_FRAME_PRIO_CHAIN | MOCAP_FRAME_PRIO_EVAL | MOCAP_FRAME_PRIO_OUT)
 template <int P>
 __device__ __forceinline__ void frame_prio() {
-#if MOCAP_FRAME_PRIO_ANY
-  __builtin_amdgcn_s_setprio(P);
-#endif
+  if constexpr (kPhasePrio) __builtin_amdgcn_s_setprio(P);
 }
 template <int T, bool UNIFORM_K, bool F32R, bool WIDE, bool HEAVY = false>
 struct FrameState {
   const FrameArgs& p;
-#if MOCAP_SPLIT_CV
-  const CamView cv;  // a copy whose table pointers are scalar values of their own (split_cam_view), not slices of the 16-dword kernel-argument load
-#else
-  const CamView& cv;
-#endif
+  // wide: a copy whose table pointers are scalar values of their own (split_cam_view), not slices of the 16-dword kernel-argument load
+  std::conditional_t<kSplitCv, const CamView, const CamView&> cv;
   const int C, M, R;
   int tid;
   // The lane's number taken afresh (an empty asm the optimiser cannot see through; csrc/frame_bb.hip has the measurements): what a
   // phase derives from it is computed in that phase instead of once before the frame loop -- where it would sit in scratch
   __device__ __forceinline__ void fresh_tid() {
-#if MOCAP_FRAME_FRESH_TID
-    int t = tid;
-    asm volatile("" : "+v"(t));
-    tid = t;
-#endif
+    if constexpr (kFreshTid) {
+      int t = tid;
+      asm volatile("" : "+v"(t));
+      tid = t;
+    }
   }
   int Hs;  // hit-list stride per (root, camera)
   double *line, *dist, *seg_e, *seg_x;
@@ -263,11 +235,7 @@ struct FrameState {
   int spec_base = -1;          // wide: first row of the provisional roots while they are matched speculatively (spec_begin / spec_finish), else -1
 
   __device__ FrameState(const FrameArgs& p_, unsigned char* smem)
-#if MOCAP_SPLIT_CV
       : p(p_), cv(split_cam_view(p_.cv)), C(p_.cv.C), M(p_.M), R(p_.K_max), tid(threadIdx.x) {
-#else
-      : p(p_), cv(p_.cv), C(p_.cv.C), M(p_.M), R(p_.K_max), tid(threadIdx.x) {
-#endif
     const FrameLayout L(C, M, R, T, p_.H, WIDE, TABLE);
     Hs = L.Hs;
     line = (double*)(smem + L.line);
@@ -750,12 +718,10 @@ struct FrameState {
           float thr = finf;
           if (F32R) thr = __double2float_ru(p.gate_px * lden * (1.0 + 1e-12) + (2.5 * 0x1p-24) * (2.0 * om + fabs(lc)) * (1.0 + 1e-6));
           if (!have) thr = -1.0f;
-          int np = 0, kk = 0;
-#if MOCAP_WIDE_ACC
           // bookkeeping as four accumulators, one per position of a step: += 0x10000 + k0 when the blob passes, i.e. the
-          // count in the high half and the index (sum) in the low half -- a select and an add per blob
+          // count in the high half and the index (sum) in the low half -- a select and an add per blob (against a count and
+          // an index updated per blob: 32.4 -> 30.5 ms per 12 500 stress frames)
           uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-#endif
           for (int k0 = 0; k0 < M4; k0 += 4) {  // scalar loop; four blobs per step, two broadcast reads
             const float4 X = *reinterpret_cast<const float4*>(wx + k0);
             const float4 Y = *reinterpret_cast<const float4*>(wy + k0);
@@ -763,7 +729,6 @@ struct FrameState {
             const float t2 = fmaf(a32, X.z, fmaf(b32, Y.z, c32)), t3 = fmaf(a32, X.w, fmaf(b32, Y.w, c32));
             const unsigned long long m0 = __ballot(fabsf(t0) <= thr), m1 = __ballot(fabsf(t1) <= thr);
             const unsigned long long m2 = __ballot(fabsf(t2) <= thr), m3 = __ballot(fabsf(t3) <= thr);
-#if MOCAP_WIDE_ACC
             if ((m0 | m1) | (m2 | m3)) {
               const uint32_t kb = 0x10000u + (uint32_t)k0;
               acc0 += fabsf(t0) <= thr ? kb : 0u;
@@ -771,35 +736,9 @@ struct FrameState {
               acc2 += fabsf(t2) <= thr ? kb : 0u;
               acc3 += fabsf(t3) <= thr ? kb : 0u;
             }
-#else
-            if ((m0 | m1) | (m2 | m3)) {  // some root of the batch has a candidate among these four (scalar branch)
-              if (m0) {
-                const bool ps = fabsf(t0) <= thr;
-                np += ps ? 1 : 0;
-                kk = ps ? k0 : kk;
-              }
-              if (m1) {
-                const bool ps = fabsf(t1) <= thr;
-                np += ps ? 1 : 0;
-                kk = ps ? k0 + 1 : kk;
-              }
-              if (m2) {
-                const bool ps = fabsf(t2) <= thr;
-                np += ps ? 1 : 0;
-                kk = ps ? k0 + 2 : kk;
-              }
-              if (m3) {
-                const bool ps = fabsf(t3) <= thr;
-                np += ps ? 1 : 0;
-                kk = ps ? k0 + 3 : kk;
-              }
-            }
-#endif
           }
-#if MOCAP_WIDE_ACC
-          np = (int)((acc0 >> 16) + (acc1 >> 16) + (acc2 >> 16) + (acc3 >> 16));
-          kk = acc0 ? (int)(acc0 & 0xffffu) : (acc1 ? (int)(acc1 & 0xffffu) + 1 : (acc2 ? (int)(acc2 & 0xffffu) + 2 : (int)(acc3 & 0xffffu) + 3));  // (meaningful when np == 1)
-#endif
+          const int np = (int)((acc0 >> 16) + (acc1 >> 16) + (acc2 >> 16) + (acc3 >> 16));
+          const int kk = acc0 ? (int)(acc0 & 0xffffu) : (acc1 ? (int)(acc1 & 0xffffu) + 1 : (acc2 ? (int)(acc2 & 0xffffu) + 2 : (int)(acc3 & 0xffffu) + 3));  // (meaningful when np == 1)
 #ifdef MOCAP_DEBUG_PRETEST  // self-check build: the exact decision (helpers.py:373,375) for EVERY blob the float32 pre-test
           if (have) {          // rejected; a blob inside the gate among them is a false negative (must never happen)
             int fneg = 0;
@@ -826,9 +765,7 @@ struct FrameState {
           // here, for all such lanes at once -- both distances in double (helpers.py:373), strict gate (helpers.py:375,383), the hits
           // in (distance, index) order, the closest claims by value (helpers.py:391) -- exactly resolve_pair's outcome without its
           // wave-serial round (broadcast of the line, distances of all 256 blobs, ranking by broadcast: ~250 instructions per pair).
-          bool two = false;
-#if MOCAP_WIDE_ACC && MOCAP_WIDE_PAIR2
-          two = have && np == 2 && p.H >= 2 && ((acc0 | acc1 | acc2 | acc3) >> 17) == 0u;  // (no accumulator counts two)
+          const bool two = have && np == 2 && p.H >= 2 && ((acc0 | acc1 | acc2 | acc3) >> 17) == 0u;  // (no accumulator counts two)
           if (__ballot(two)) {  // wave-uniform
             if (two) {
               const int c0 = (int)(acc0 >> 16), c1 = (int)(acc1 >> 16), c2 = (int)(acc2 >> 16), c3 = (int)(acc3 >> 16);
@@ -858,7 +795,6 @@ struct FrameState {
               }
             }
           }
-#endif
           unsigned long long multi = __ballot(have && np >= 2 && !two);
           if (multi) {  // rare: roots with several candidates, one at a time, the camera's blobs four per lane
             float2 bl[4];
@@ -1060,13 +996,13 @@ struct FrameState {
   // (helpers.py:402-406): camera by camera, a provisional root whose blob is still unclaimed is real and its closest hits
   // claim their blobs in the later cameras (helpers.py:391); the real ones move down to consecutive rows in (camera, blob)
   // order -- the numbering of the sequential chain.  Falls back to that chain (returns false, nothing changed) when there
-  // are more than MOCAP_WIDE_SPEC_T provisional roots or no rows for them, or when a hit list holds a second blob with the closest hit's coordinates
+  // are more than kWideSpecT provisional roots or no rows for them, or when a hit list holds a second blob with the closest hit's coordinates
   // (claimed with it by value: not replayable from the closest hit alone).  All lanes; synchronised on entry and exit.
   // spec_begin: the provisional roots and their rows; returns their number, 0 (no blob left unclaimed: the chain is complete) or -1.
   __device__ __forceinline__ int spec_begin(int jlo, int n_roots) {
     fresh_tid();
     const int MW = (M + 63) / 64, lane = tid & 63;
-    if (tid < 64) frame_prio<MOCAP_FRAME_PRIO_SERIAL>();
+    if (tid < 64) frame_prio<kPrioSerial>();
     if (tid < 64) {
       int u = 0;
       if (lane >= jlo && lane < C) {
@@ -1078,7 +1014,7 @@ struct FrameState {
       }
       const uint32_t incl = wave_inclusive_scan((uint32_t)u, lane);
       const int total = __builtin_amdgcn_readlane((int)incl, 63);
-      const bool fits = total <= MOCAP_WIDE_SPEC_T && n_roots + total <= R;
+      const bool fits = total <= kWideSpecT && n_roots + total <= R;
       if (fits && u) {  // lane = camera: its unclaimed blobs in blob order, behind those of the cameras before it
         int idx = n_roots + (int)incl - u;
         const int Mj = cnt[lane];
@@ -1101,7 +1037,7 @@ struct FrameState {
         misc[MI_SPEC_OVER + 1] = 0;
       }
     }
-    frame_prio<MOCAP_FRAME_PRIO_CHAIN>();
+    frame_prio<kPrioChain>();
     __syncthreads();
     const int nP = misc[MI_SPEC_N];
     __syncthreads();  // (the slot is reused as the fall-back flag below)
@@ -1125,7 +1061,7 @@ struct FrameState {
       __syncthreads();
       return false;
     }
-    if (tid < 64) frame_prio<MOCAP_FRAME_PRIO_SERIAL>();
+    if (tid < 64) frame_prio<kPrioSerial>();
     if (tid < 64) {
       const int row = n_roots + lane;
       const bool mine = lane < nP;
@@ -1189,7 +1125,7 @@ struct FrameState {
         misc[MI_NROOTS] = n_roots + nreal;
       }
     }
-    frame_prio<MOCAP_FRAME_PRIO_CHAIN>();
+    frame_prio<kPrioChain>();
     __syncthreads();
     n_roots = misc[MI_NROOTS];
     return true;
@@ -1201,7 +1137,7 @@ struct FrameState {
   __device__ __forceinline__ int create_roots(int j, int n_roots) {
     fresh_tid();
     const int MW = (M + 63) / 64;
-    if (tid < 64) frame_prio<MOCAP_FRAME_PRIO_SERIAL>();
+    if (tid < 64) frame_prio<kPrioSerial>();
     if (tid < 64) {
       const int Mj = cnt[j];
       int base_root = n_roots;
@@ -1229,13 +1165,13 @@ struct FrameState {
         misc[MI_NROOTS] = base_root;
       }
     }
-    frame_prio<MOCAP_FRAME_PRIO_CHAIN>();
+    frame_prio<kPrioChain>();
     __syncthreads();
     const int now = misc[MI_NROOTS];
     if (now > n_roots) {  // workgroup-uniform
       // cameras up to the root's own (the pairs with the cameras after it are written by the matching pass, by other waves at
       // the same time: the two must not touch the same bytes)
-      const int ncam = (MOCAP_WIDE_DEBUG_SKIP & 2) ? C : j + 1;
+      const int ncam = j + 1;
       for (int idx = tid; idx < (now - n_roots) * ncam; idx += T) {
         const int r = n_roots + idx / ncam, c = idx % ncam;
         if (c == j) set_hit_code(r, j, 1);
@@ -1283,11 +1219,9 @@ struct FrameState {
       }
       // a root's own camera counts as one "hit" (its blob), the cameras before it as none: a candidate group is decoded
       // from these two bytes per camera alone
-      const int ncam0 = (MOCAP_WIDE_DEBUG_SKIP & 1) ? C : 1;
-      for (int idx = tid; idx < n0 * ncam0; idx += T) {
-        const int r = idx / ncam0, c = idx - r * ncam0;
-        if (c == 0) set_hit_code(r, 0, 1);
-        h0[(size_t)r * C + c] = (uint8_t)r;
+      for (int r = tid; r < n0; r += T) {
+        set_hit_code(r, 0, 1);
+        h0[(size_t)r * C] = (uint8_t)r;
       }
       if (tid == 0) {
         misc[MI_NROOTS] = n0;
@@ -1300,29 +1234,24 @@ struct FrameState {
     // free lanes of the last batch instead of paying a chain step of their own (2.6 of 29 ms per 12 500 stress frames).
     int n_roots = n0, n_tot = n0, n_main = n0;
     bool pre1 = false;
-#if !(MOCAP_WIDE_DEBUG_SKIP & 1)
 #pragma nounroll
     for (int ph = 0; ph < 2; ph++) {
       const int clo = 1 + ph, chi = ph ? C : (C < 2 ? C : 2), hi = ph ? n_main : n0;
       if (clo < chi && hi > 0) match_roots_wide<true>(0, hi, clo, chi, ph == 0);
       __syncthreads();
-      if (ph == 0 && C > 2 && MOCAP_WIDE_CAM1 && !(MOCAP_WIDE_DEBUG_SKIP & 2)) {
+      if (ph == 0 && C > 2) {
         n_tot = create_roots(1, n0);
         pre1 = true;
         // ... unless they would open a new group of 256 lanes for a handful of roots: those meet their cameras as a chain step
         n_main = n_tot;
-        if (n_tot > 256 && (n_tot & 255) < MOCAP_WIDE_CHAIN_T) n_main = n_tot - (n_tot & 255);
+        if (n_tot > 256 && (n_tot & 255) < kWideChainT) n_main = n_tot - (n_tot & 255);
       }
     }
-#else
-    __syncthreads();
-#endif
-    frame_prio<MOCAP_FRAME_PRIO_CHAIN>();
-    bool spec_ok = MOCAP_WIDE_SPEC && !(MOCAP_WIDE_DEBUG_SKIP & 2) && p.wide != 2;
+    frame_prio<kPrioChain>();
+    bool spec_ok = p.wide != 2;  // (FrameArgs::wide == 2: the chain strictly camera by camera)
     for (int j = 1; j < C; j++) {
       // cameras j .. C-1 in one speculative pass as soon as few blobs are left unclaimed (spec_begin), else camera j alone
       int nP = -1;
-      if ((MOCAP_WIDE_DEBUG_SKIP & 32) && j == 2) break;
       int now = n_roots;
       if (j == 1 && pre1) {
         n_roots = n_main;  // camera 1's roots exist; those from n_main on have not met the cameras after it yet
@@ -1335,16 +1264,15 @@ struct FrameState {
         now = nP < 0 ? create_roots(j, n_roots) : n_roots + nP;
       }
       if (now > n_roots) {  // workgroup-uniform
-        if (j + 1 < C && !(MOCAP_WIDE_DEBUG_SKIP & 2)) {
+        if (j + 1 < C) {
           // few new roots (the usual chain step), or provisional ones: the blobs stay in registers and the roots are broadcast; many: one lane per root
           spec_base = nP > 0 ? n_roots : -1;
-          if (nP > 0 || now - n_roots < MOCAP_WIDE_CHAIN_T) match_pairs_wide(n_roots, now, j + 1); else match_roots_wide<false>(n_roots, now, j + 1, C, false);
+          if (nP > 0 || now - n_roots < kWideChainT) match_pairs_wide(n_roots, now, j + 1); else match_roots_wide<false>(n_roots, now, j + 1, C, false);
           spec_base = -1;
         }
         __syncthreads();
       }
       if (nP > 0) {
-        if (MOCAP_WIDE_DEBUG_SKIP & 64) break;
         if (spec_finish(nP, n_roots)) break;
         spec_ok = false;  // (rare: see spec_finish) camera j again, and the rest of the frame, sequentially
         j--;
@@ -1438,7 +1366,7 @@ struct FrameState {
       gcnt[r] = views > 1 ? (heavy ? 1u : (over ? 0u : (uint32_t)total)) : 0u;  // helpers.py:413-414 drops 1-view roots
     }
     __syncthreads();
-    if (tid < 64) frame_prio<MOCAP_FRAME_PRIO_SERIAL>();
+    if (tid < 64) frame_prio<kPrioSerial>();
     if (tid < 64) {  // candidate offsets and output slots: wave scans over the roots, 64 at a time
       const int lane = tid;
       unsigned long long carry = 0;
@@ -1462,7 +1390,7 @@ struct FrameState {
         misc[MI_G] = misc[MI_STATUS] ? 0 : (int32_t)(uint32_t)carry;
       }
     }
-    frame_prio<MOCAP_FRAME_PRIO_CHAIN>();
+    frame_prio<kPrioChain>();
     __syncthreads();
   }
 
@@ -1642,32 +1570,15 @@ struct FrameState {
       while (true) {
         double X[3], e;
         const double bound = prune ? __longlong_as_double((long long)rbound[r]) : inf;
-        if constexpr (WIDE && (MOCAP_WIDE_DEBUG_SKIP & 4)) {
-          e = 1.0 + (double)(g & 7u);
-          X[0] = X[1] = X[2] = 0.0;
-        } else if constexpr (TABLE)
+        if constexpr (TABLE)
           triangulate_and_score_tab<true, F32R>(cv, contrib, obs_ix, X, e, bound, ec);
         else if constexpr (WIDE)
           // (no depth form of the eigenvalue bound here: a wide frame's rival groups differ from the right one in one or two
           // of ~60 views by a blob within the gate of the line -- near-winners no bound separates -- so that pass over the
           // cameras, a sixth of a group's instructions, cut nothing; exactness is unaffected: a cut-off only ever skips work)
-          triangulate_and_score<UNIFORM_K, true, F32R, MOCAP_WIDE_BATCH, (MOCAP_WIDE_DEPTH_CUT != 0)>(cv, wobs, wobs, X, e, bound, ec);
+          triangulate_and_score<UNIFORM_K, true, F32R, kWideBatch, false>(cv, wobs, wobs, X, e, bound, ec);
         else
           triangulate_and_score<UNIFORM_K, true, F32R, 1>(cv, obs, obs, X, e, bound, ec);
-#ifdef MOCAP_DEBUG_EIGCHECK  // self-check of the cut-offs: a group that was cut must not beat the bound it was cut against
-        if (!(e < inf)) {
-          double X2[3], e2;
-          if constexpr (TABLE)
-            triangulate_and_score_tab<true, F32R>(cv, contrib, obs_ix, X2, e2);
-          else if constexpr (WIDE)
-            triangulate_and_score<UNIFORM_K, true, F32R>(cv, wobs, wobs, X2, e2);
-          else
-            triangulate_and_score<UNIFORM_K, true, F32R>(cv, obs, obs, X2, e2);
-          if (e2 <= bound)
-            printf("EIGCHECK frame-item tid %d root %d g %u bound %.17g true %.17g omax %g\n", tid, r, g - r_beg, bound, e2,
-                   (double)__int_as_float(misc[MI_OMAX]));
-        }
-#endif
         if (e < best_e) {  // strict <: first minimum within the lane's ascending run (best_e starts at +inf; a
           best_e = e;      // group that was cut short or whose error is not finite never enters)
           best_g = g - r_beg;
@@ -1782,7 +1693,7 @@ struct FrameState {
 };
 
 template <int T, bool UNIFORM_K, bool F32R, bool WIDE, int MODE, bool HEAVY = false>
-__global__ __launch_bounds__(T, MOCAP_FRAME_WAVES_PER_EU) void frame_kernel(FrameArgs p) {
+__global__ __launch_bounds__(T, kFrameWavesPerEU) void frame_kernel(FrameArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   FrameState<T, UNIFORM_K, F32R, WIDE, HEAVY> st(p, smem);
   const int tid = threadIdx.x;
@@ -1858,7 +1769,7 @@ __global__ __launch_bounds__(T, MOCAP_FRAME_WAVES_PER_EU) void frame_kernel(Fram
         S = q_load(&q.heavy[4 * h + 2]);
         sl = item - base;
       }
-      frame_prio<MOCAP_FRAME_PRIO_MATCH>();
+      frame_prio<kPrioMatch>();
       if constexpr (WIDE) st.match_wide(frame); else st.match(frame);
       const uint32_t G = (uint32_t)st.misc[MI_G];
       if (kind == 1) {
@@ -1895,9 +1806,9 @@ __global__ __launch_bounds__(T, MOCAP_FRAME_WAVES_PER_EU) void frame_kernel(Fram
         g_lo = (uint32_t)((uint64_t)G * (uint64_t)sl / S);
         g_hi = (uint32_t)((uint64_t)G * (uint64_t)(sl + 1) / S);
       }
-      frame_prio<MOCAP_FRAME_PRIO_EVAL>();
+      frame_prio<kPrioEval>();
       if (g_hi > g_lo) st.evaluate(g_lo, g_hi);
-      frame_prio<MOCAP_FRAME_PRIO_OUT>();
+      frame_prio<kPrioOut>();
       const int nroots = st.misc[MI_NROOTS];
       bool merge = false;
       for (int r = tid; r < nroots; r += T) {

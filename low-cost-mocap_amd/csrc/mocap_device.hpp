@@ -5,11 +5,10 @@
 //   * calculate_reprojection_error       (helpers.py:214-241, incl. cv.projectPoints)
 //
 // Design (gfx950): everything for one candidate lives in VGPRs (10-entry packed symmetric
-// B = A^T A, 16-entry eigenvector accumulator); camera tables are read with wave-uniform
-// addresses so they come in over the scalar cache (s_load) when all intrinsics are equal.
-// The 4x4 null vector comes from a shifted-Cholesky / Laguerre / inverse-iteration solve (a cyclic
-// Jacobi eigen-solve with compile-time rotation indices is kept behind -DMOCAP_EIG_JACOBI); both
-// run in registers only (no dynamic register indexing, no scratch).  FP64 throughout: B squares the condition
+// B = A^T A); camera tables are read with wave-uniform addresses so they come in over the
+// scalar cache (s_load) when all intrinsics are equal.
+// The 4x4 null vector comes from a shifted-Cholesky / Laguerre / inverse-iteration solve that runs
+// in registers only (no dynamic register indexing, no scratch).  FP64 throughout: B squares the condition
 // number of A (helpers.py:319-321) and the contract is 1e-5 relative on the 3-D point.
 //
 // The file is compiled with -ffp-contract=off: expressions whose rounding the reference
@@ -129,73 +128,9 @@ __device__ __forceinline__ double div_by(double a, double b, double r) {
   return fma(fma(-b, q, a), r, q);
 }
 
-// One Jacobi rotation in the (P,Q) plane; indices are compile-time so a[] / v[] stay in VGPRs.
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rot(double (&a)[10], double (&v)[16]) {
-  const double apq = a[sidx(P, Q)];
-  if (apq != 0.0) {
-    const double app = a[sidx(P, P)], aqq = a[sidx(Q, Q)];
-    // Rotation angle from the double-angle identities, division- and sqrt-free (two v_rsq_f64):
-    //   h = aqq - app, w = 2 apq, r = hypot(h, w):  cos 2θ = |h| / r,  sin 2θ = sgn(h) w / r
-    //   cos²θ = (1 + cos 2θ) / 2 = u,  c = sqrt(u) = u * rsqrt(u),  s = sin 2θ / (2c),  t = s / c
-    const double h = aqq - app, w = apq + apq;
-    const double ir = rsqrt(fma(h, h, w * w));
-    const double c2 = fabs(h) * ir;
-    const double s2 = (h < 0.0 ? -w : w) * ir;
-    const double u = fma(0.5, c2, 0.5);
-    const double ic = rsqrt(u);
-    const double c = u * ic;
-    const double s = 0.5 * s2 * ic;
-    const double t = s * ic;
-    a[sidx(P, P)] = fma(-t, apq, app);
-    a[sidx(Q, Q)] = fma(t, apq, aqq);
-    a[sidx(P, Q)] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (k != P && k != Q) {
-        const double akp = a[sidx(k, P)], akq = a[sidx(k, Q)];
-        a[sidx(k, P)] = fma(c, akp, -s * akq);
-        a[sidx(k, Q)] = fma(s, akp, c * akq);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const double vkp = v[k * 4 + P], vkq = v[k * 4 + Q];
-      v[k * 4 + P] = fma(c, vkp, -s * vkq);
-      v[k * 4 + Q] = fma(s, vkp, c * vkq);
-    }
-  }
-}
-
-// Eigenvector of the smallest-magnitude eigenvalue of the symmetric 4x4 B (== the last
-// right-singular vector scipy.linalg.svd(B) yields at helpers.py:320-321, up to sign).
-__device__ __forceinline__ void smallest_eigvec4_jacobi(double (&a)[10], double (&out)[4]) {
-  double v[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  for (int sweep = 0; sweep < 12; sweep++) {
-    const double off2 = fma(a[1], a[1], fma(a[2], a[2], fma(a[3], a[3],
-                        fma(a[5], a[5], fma(a[6], a[6], a[8] * a[8])))));
-    const double dg2 = fma(a[0], a[0], fma(a[4], a[4], fma(a[7], a[7], a[9] * a[9])));
-    // converged when the off-diagonal mass is ~1e-17 of the diagonal (below FP64 rounding)
-    if (!(off2 > 1e-34 * dg2)) break;
-    jacobi_rot<0, 1>(a, v);
-    jacobi_rot<0, 2>(a, v);
-    jacobi_rot<0, 3>(a, v);
-    jacobi_rot<1, 2>(a, v);
-    jacobi_rot<1, 3>(a, v);
-    jacobi_rot<2, 3>(a, v);
-  }
-  const double d0 = fabs(a[0]), d1 = fabs(a[4]), d2 = fabs(a[7]), d3 = fabs(a[9]);
-  int m = 0;
-  double dm = d0;
-  if (d1 < dm) { dm = d1; m = 1; }
-  if (d2 < dm) { dm = d2; m = 2; }
-  if (d3 < dm) { dm = d3; m = 3; }
-#pragma unroll
-  for (int k = 0; k < 4; k++)
-    out[k] = m == 0 ? v[k * 4 + 0] : m == 1 ? v[k * 4 + 1] : m == 2 ? v[k * 4 + 2] : v[k * 4 + 3];
-}
-
-// Same vector, ~6x fewer instructions: shifted Cholesky + Laguerre + inverse iteration.
+// Eigenvector of the smallest-magnitude eigenvalue of the symmetric 4x4 B (== the last right-singular vector
+// scipy.linalg.svd(B) yields at helpers.py:320-321, up to sign), with ~6x fewer instructions than a cyclic Jacobi
+// eigen-solve: shifted Cholesky + Laguerre + inverse iteration.
 //   B is symmetric positive semi-definite, so p(x) = det(B - x I) has four real roots >= 0 and
 //   Laguerre's iteration started at x = 0 climbs monotonically to the smallest one without ever
 //   overshooting it (B - x I stays positive definite -> plain Cholesky is backward stable):
@@ -216,8 +151,7 @@ constexpr int kInvIters = 5;
 // the candidate is dropped when s1 * lamcut < 1 (returns false, `out` untouched); otherwise lam_lb receives the bound
 // of the last factorisation, shrunk by the rounding allowance (Cholesky backward error and the rounding of B itself
 // are O(1e-15 tr); 2e-12 tr is charged).  lamcut = +inf switches the cut off.
-__device__ __forceinline__ bool smallest_eigvec4_cholesky(const double (&a)[10], double (&out)[4], double lamcut,
-                                                          double& lam_lb) {
+__device__ __forceinline__ bool smallest_eigvec4(const double (&a)[10], double (&out)[4], double lamcut, double& lam_lb) {
   const double tr = (a[0] + a[4]) + (a[7] + a[9]);
   // pivots are clamped from below (fmax also swallows NaN): a shift that rounding pushed past lam1
   // yields one tiny pivot, i.e. a huge last row of M -- still the wanted vector -- and s2/s1^2 -> 1,
@@ -336,18 +270,6 @@ __device__ __forceinline__ double eigcut_s1_shifted(const double (&a)[10], const
   tr = tr1 + 2.0 * c2 * ((a[0] + a[4]) + (a[7] + a[9]));
   return s1;
 }
-
-#ifdef MOCAP_EIG_JACOBI
-__device__ __forceinline__ bool smallest_eigvec4(double (&a)[10], double (&out)[4], double, double& lam_lb) {
-  smallest_eigvec4_jacobi(a, out);
-  lam_lb = 0.0;  // no bound: nothing is ever cut
-  return true;
-}
-#else
-__device__ __forceinline__ bool smallest_eigvec4(double (&a)[10], double (&out)[4], double lamcut, double& lam_lb) {
-  return smallest_eigvec4_cholesky(a, out, lamcut, lam_lb);
-}
-#endif
 
 // Exact cut-off of candidate selection from the DLT matrix alone (frame path; everything else passes EigCut{}).
 // For ANY homogeneous point x = (X, 1):  x^T B x = sum over the views of z_c^2 (du_c^2 + dv_c^2)  (z_c = P_c[2].x, the
