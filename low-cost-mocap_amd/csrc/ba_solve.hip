@@ -30,12 +30,6 @@
 
 using namespace mocap;
 
-#define HIP_TRY(ctx, expr)                                  \
-  do {                                                      \
-    hipError_t e__ = (expr);                                \
-    if (e__ != hipSuccess) return (ctx)->hip_fail(e__, #expr); \
-  } while (0)
-
 namespace {
 
 constexpr double kEps = 2.220446049250313e-16;
@@ -370,16 +364,9 @@ int ba_setup(mocap_ctx* ctx, BaWork& w, int64_t N, const double* obs, int Pmax, 
   }
   lap("fused workspace (hipMalloc)");
   const size_t pin_bytes = sizeof(double) * (nd_x + nd_G + nd_cost + nd_fout);
-  if (pin_bytes > ctx->ba_pin_cap) {
-    if (ctx->ba_pin) (void)hipHostFree(ctx->ba_pin);
-    ctx->ba_pin = nullptr;
-    ctx->ba_pin_cap = 0;
-    // coherent (fine-grained): the fused kernel's completion stamp is polled by the host while the kernel runs
-    HIP_TRY(ctx, hipHostMalloc(&ctx->ba_pin, pin_bytes, hipHostMallocCoherent));
-    ctx->ba_pin_cap = pin_bytes;
-  }
-  if (!ctx->ba_event) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ba_event, hipEventDisableTiming));
-  w.h_x = (double*)ctx->ba_pin;
+  // coherent (fine-grained): the fused kernel's completion stamp is polled by the host while the kernel runs
+  HIP_TRY(ctx, ctx->ba_pin.reserve(pin_bytes, pin_bytes, hipHostMallocCoherent));
+  w.h_x = (double*)ctx->ba_pin.ptr;
   w.h_G = w.h_x + nd_x;
   w.h_fout = w.fused ? w.h_G + nd_G + nd_cost : nullptr;
   if (w.h_fout) {
@@ -401,16 +388,11 @@ int ba_setup(mocap_ctx* ctx, BaWork& w, int64_t N, const double* obs, int Pmax, 
     lap("pageable copies + memset queued");
     return MOCAP_OK;
   }
-  if (b_obs + b_valid > ctx->ba_stage_cap) {
-    if (ctx->ba_stage) (void)hipHostFree(ctx->ba_stage);
-    ctx->ba_stage = nullptr;
-    ctx->ba_stage_cap = 0;
-    const size_t want = std::max<size_t>((b_obs + b_valid) * 5 / 4, (size_t)1 << 20);
-    HIP_TRY(ctx, hipHostMalloc(&ctx->ba_stage, want, hipHostMallocDefault));
-    ctx->ba_stage_cap = want;
+  if (b_obs + b_valid > ctx->ba_stage.cap) {
+    HIP_TRY(ctx, ctx->ba_stage.reserve(b_obs + b_valid, std::max<size_t>((b_obs + b_valid) * 5 / 4, (size_t)1 << 20), hipHostMallocDefault));
     lap("pinned staging buffer (hipHostMalloc)");
   }
-  char* st = (char*)ctx->ba_stage;
+  char* st = (char*)ctx->ba_stage.ptr;
   memcpy(st, obs, b_obs);
   if (w.m) memcpy(st + b_obs, w.valid.data(), b_valid);
   lap("host copy into the staging buffer");
@@ -424,21 +406,6 @@ int ba_setup(mocap_ctx* ctx, BaWork& w, int64_t N, const double* obs, int Pmax, 
   }
   lap("stage-in queued");
   return MOCAP_OK;
-}
-
-// Wait for everything queued on the context's stream by polling an event: the LM loop waits twice per
-// iteration on ~0.1 ms of GPU work, and a sleeping wait costs more than the work itself.
-int ba_wait(mocap_ctx* ctx) {
-  HIP_TRY(ctx, hipEventRecord(ctx->ba_event, ctx->stream));
-  for (long spins = 0;; spins++) {
-    const hipError_t e = hipEventQuery(ctx->ba_event);
-    if (e == hipSuccess) return MOCAP_OK;
-    if (e != hipErrorNotReady) return ctx->hip_fail(e, "hipEventQuery");
-    if (spins > 2000000) {  // seconds of polling: something is badly stuck, fall back to a blocking wait
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      return MOCAP_OK;
-    }
-  }
 }
 
 // residuals for P parameter vectors already in w.d_params -> w.d_r [P][N]
@@ -488,7 +455,7 @@ int ba_cost_at(mocap_ctx* ctx, BaWork& w, const double* x, int f32, int cauchy, 
   if (rc) return rc;
   double* out = w.h_G + (w.d_cost - w.d_G);
   HIP_TRY(ctx, launch_ba_cost(w.d_r, w.d_valid, w.m, f32, cauchy, out, ctx->stream));
-  rc = ba_wait(ctx);
+  rc = spin_wait(ctx, ctx->ba_event);
   if (rc) return rc;
   cost = out[0];
   finite = out[1] != 0.0;
@@ -666,7 +633,7 @@ int ba_linearize(mocap_ctx* ctx, BaWork& w, const double* x, int f32, int cauchy
   const size_t nG = (size_t)w.NP * w.NP, span = (size_t)(w.d_cost - w.d_G) + 2;
   HIP_TRY(ctx, launch_ba_gram_cost(w.d_Jaug, w.m_pad, w.NP, w.d_partial, w.ksplit, w.h_G, w.d_rho, nullptr, w.m, f32,
                                    -1 /* rho precomputed */, w.h_G + span - 2, ctx->stream));
-  rc = ba_wait(ctx);
+  rc = spin_wait(ctx, ctx->ba_event);
   if (rc) return rc;
   G.assign(w.h_G, w.h_G + nG);
   cost = w.h_G[span - 2];

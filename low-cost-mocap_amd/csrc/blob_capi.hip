@@ -14,12 +14,6 @@
 
 using namespace mocap;
 
-#define HIP_TRY(ctx, expr)                                     \
-  do {                                                         \
-    hipError_t e__ = (expr);                                   \
-    if (e__ != hipSuccess) return (ctx)->hip_fail(e__, #expr); \
-  } while (0)
-
 namespace {
 
 // cv::invert of a 3x3 CV_64F matrix (closed form, core/src/lapack.cpp), row-major
@@ -405,17 +399,24 @@ extern "C" int mocap_find_blobs(mocap_ctx* ctx, int64_t n_frames, const uint8_t*
   const size_t n_img = (size_t)n_frames * ctx->img_C;
   const size_t b_raw = n_img * ctx->img_rows * ctx->img_cols * 3, b_blobs = n_img * M_max * 2 * sizeof(float),
                b_i32 = n_img * sizeof(int32_t), b_proc = processed ? n_img * ctx->img_S * ctx->img_S * 3 : 0;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  uint8_t *d_raw, *d_proc;
+  float* d_blobs;
+  int32_t *d_counts, *d_status, *d_ncont;
+  auto lay = [&](void* base) {
+    Carver c(base);
+    d_raw = c.take<uint8_t>(b_raw);
+    d_blobs = c.take<float>(n_img * M_max * 2);
+    d_counts = c.take<int32_t>(n_img);
+    d_status = c.take<int32_t>(n_img);
+    d_ncont = c.take<int32_t>(n_img);
+    d_proc = c.take<uint8_t>(b_proc);
+    return c.off;
+  };
   DevBuf& s = ctx->img_stage;
-  const size_t total = al(b_raw) + al(b_blobs) + 3 * al(b_i32) + al(b_proc);
+  const size_t total = lay(nullptr);
   if (s.reserve(total)) return ctx->fail(MOCAP_E_HIP, "hipMalloc(%zu) failed", total);
-  unsigned char* p = (unsigned char*)s.ptr;
-  uint8_t* d_raw = p;                     p += al(b_raw);
-  float* d_blobs = (float*)p;             p += al(b_blobs);
-  int32_t* d_counts = (int32_t*)p;        p += al(b_i32);
-  int32_t* d_status = (int32_t*)p;        p += al(b_i32);
-  int32_t* d_ncont = (int32_t*)p;         p += al(b_i32);
-  uint8_t* d_proc = processed ? p : nullptr;
+  lay(s.ptr);
+  if (!processed) d_proc = nullptr;
   HIP_TRY(ctx, hipMemcpyAsync(d_raw, images, b_raw, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_blobs, 0, b_blobs, ctx->stream));
   int rc = find_blobs_dev_locked(ctx, n_frames, d_raw, M_max, d_blobs, d_counts, d_status, d_proc, d_ncont);

@@ -8,11 +8,54 @@
 
 #include "kernels.hpp"
 
-struct DevBuf {
+#define HIP_TRY(ctx, expr)                                     \
+  do {                                                         \
+    hipError_t e__ = (expr);                                   \
+    if (e__ != hipSuccess) return (ctx)->hip_fail(e__, #expr); \
+  } while (0)
+
+// device memory, pinned host memory and events belong to the context member that holds them (freed with it, never copied)
+struct Owned {
+  Owned() = default;
+  Owned(const Owned&) = delete;
+};
+
+struct DevBuf : Owned {
   void* ptr = nullptr;
   size_t cap = 0;
   int reserve(size_t bytes);  // grow-only; 0 on success
-  void release();
+  ~DevBuf() { if (ptr) (void)hipFree(ptr); }
+};
+
+struct PinBuf : Owned {  // hipHostMalloc
+  void* ptr = nullptr;
+  size_t cap = 0;
+  // grow-only: more than `cap` bytes needed = the buffer is replaced by one of `want` bytes (the growth rule is the caller's)
+  hipError_t reserve(size_t need, size_t want, unsigned flags);
+  ~PinBuf() { if (ptr) (void)hipHostFree(ptr); }
+};
+
+struct Event : Owned {
+  hipEvent_t ev = nullptr;
+  hipError_t ready() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }  // created by its first user
+  ~Event() { if (ev) (void)hipEventDestroy(ev); }
+};
+
+// Sub-buffers of one allocation, each padded to `align` bytes.  A layout is ONE function that takes its fields from a
+// Carver and returns `off`: run on a null base it gives the size to reserve, run on the buffer it gives the pointers.
+struct Carver {
+  uintptr_t base;
+  size_t align, off = 0;
+  explicit Carver(void* b, size_t align_ = 256) : base((uintptr_t)b), align(align_) {}
+  template <class T>
+  static size_t padded(size_t count, size_t align = 256) { return (sizeof(T) * count + align - 1) / align * align; }
+  template <class T>
+  T* take(size_t count) {
+    T* p = (T*)(base + off);
+    off += padded<T>(count, align);
+    return p;
+  }
+  void align_to(size_t a) { off = (off + a - 1) / a * a; }
 };
 
 struct mocap_ctx {
@@ -44,7 +87,7 @@ struct mocap_ctx {
   // stream hand-over (mocap_set_stream): every "_dev" entry point records this event behind what it enqueued; a new
   // stream is ordered behind it with hipStreamWaitEvent -- the previous stream's handle (the caller's: it may be gone)
   // is never touched again and the host never blocks
-  hipEvent_t handover_event = nullptr;
+  Event handover_event;
   bool dev_outstanding = false;
   int mark_enqueued();
   std::mutex mu;            // one context = one serialised caller (include/mocap_core.h)
@@ -58,18 +101,15 @@ struct mocap_ctx {
   mocap::CamView cv{};
   // bundle adjustment: pinned host staging (async copies that really are async) and the event the
   // LM loop spin-waits on (hipStreamSynchronize may sleep on an interrupt: +50..400 us per wait)
-  void* ba_pin = nullptr;
-  size_t ba_pin_cap = 0;
-  hipEvent_t ba_event = nullptr;
-  void* ba_stage = nullptr;  // pinned staging of a solve's inputs (observations | valid list): no pageable copies
-  size_t ba_stage_cap = 0;
+  PinBuf ba_pin;
+  Event ba_event;
+  PinBuf ba_stage;          // pinned staging of a solve's inputs (observations | valid list): no pageable copies
   void (*ba_progress)(const double* x, int n, void* user) = nullptr;  // mocap_set_ba_progress
   void* ba_progress_user = nullptr;
   DevBuf ba_fused;          // one-launch linearisation: chunk partial tiles | chunk costs | counters | (Jaug dump)
   double ba_stamp = 0.0;    // completion stamp of the last fused launch (monotonic per context)
-  void* live_pin = nullptr;  // zero-copy staging of the live (few frames per call) host entry point
-  size_t live_pin_cap = 0;
-  hipEvent_t live_event = nullptr;
+  PinBuf live_pin;          // zero-copy staging of the live (few frames per call) host entry point
+  Event live_event;
   DevBuf world;             // 16 doubles: the to-world matrix of the fused epilogue
   bool world_on = false;
   // blob extraction (mocap_set_image_params): frame geometry, undistortion maps, mask workspace
@@ -93,6 +133,14 @@ struct mocap_ctx {
   int hip_fail(hipError_t e, const char* what);
 };
 
+// Wait for everything queued on the context's stream by polling an event: a live call and the LM loop (twice per
+// iteration) wait on ~0.1 ms of GPU work, and a sleeping wait (hipStreamSynchronize may sleep on an interrupt:
+// +50..400 us) costs more than the work itself.
+int spin_wait(mocap_ctx* ctx, Event& event);
+
 // internal entry points shared between the translation units of the C ABI (context lock held by the caller)
 int mocap_blob_stage_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_images, int M_max, float* d_blobs,
                             int32_t* d_counts, int32_t* d_status);
+int locate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const double* d_err,
+                      const int32_t* d_n_pts, int O_max, double* d_pos, double* d_heading, double* d_oerr,
+                      int32_t* d_drone, int32_t* d_lead, int32_t* d_n_obj);

@@ -685,10 +685,6 @@ __global__ __launch_bounds__(kHvEnumThreads) void heavy_enum_kernel(HeavyArgs a)
   }
 }
 
-size_t heavy_enum_ws_bytes(int enum_max, int grid) {
-  return (size_t)enum_max * (4 + 4 + 4 + 8) + 64 + (size_t)enum_max * grid * kHeavyEnumPartBytes;
-}
-
 hipError_t launch_heavy_enum(const HeavyArgs& a, hipStream_t stream) {
   if (a.cv.f32_rounding)
     hipLaunchKernelGGL(heavy_enum_kernel<true>, dim3(a.enum_grid), dim3(kHvEnumThreads), 0, stream, a);

@@ -119,7 +119,6 @@ struct HeavyArgs {
 };
 constexpr int kHeavyEnumPartBytes = 40;  // {error bits u64, group u32, pad u32, X[3]}
 constexpr int kHeavyEnumMax = 256;  // roots per re-submit call (beyond: the frame keeps its candidate-overflow flag)
-size_t heavy_enum_ws_bytes(int enum_max, int grid);
 hipError_t launch_heavy_enum(const HeavyArgs& a, hipStream_t stream);
 size_t heavy_bb_ws_bytes(int ncap);
 hipError_t launch_heavy_bb(const HeavyArgs& a, int grid, hipStream_t stream);

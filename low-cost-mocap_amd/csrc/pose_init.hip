@@ -30,12 +30,6 @@
 
 using namespace mocap;
 
-#define HIP_TRY(ctx, expr)                                     \
-  do {                                                         \
-    hipError_t e__ = (expr);                                   \
-    if (e__ != hipSuccess) return (ctx)->hip_fail(e__, #expr); \
-  } while (0)
-
 namespace {
 
 constexpr int kSampleBatch = 128;  // RANSAC iterations evaluated per round trip
@@ -376,19 +370,25 @@ int find_fundamental_locked(mocap_ctx* ctx, int64_t n, const float* p1, const fl
   if (conf < 2.220446049250313e-16 || conf > 1 - 2.220446049250313e-16) conf = 0.99;
   if (max_iters < 1) max_iters = 1;
   const size_t b_pts = sizeof(float) * 2 * (size_t)n;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  float *d_p1, *d_p2;
+  int32_t *d_idx, *d_nF, *d_cnt;
+  double* d_F;
+  uint8_t* d_mask;
+  auto lay = [&](void* base) {
+    Carver c(base);
+    d_p1 = c.take<float>(2 * (size_t)n);
+    d_p2 = c.take<float>(2 * (size_t)n);
+    d_idx = c.take<int32_t>(7 * kSampleBatch);
+    d_F = c.take<double>(27 * kSampleBatch);
+    d_nF = c.take<int32_t>(3 * kSampleBatch);
+    d_cnt = c.take<int32_t>(3 * kSampleBatch);
+    d_mask = c.take<uint8_t>((size_t)n);
+    return c.off;
+  };
   DevBuf& s = ctx->scratch[0];
-  const size_t total = 2 * al(b_pts) + al(sizeof(int32_t) * 7 * kSampleBatch) + al(sizeof(double) * 27 * kSampleBatch) +
-                       2 * al(sizeof(int32_t) * 3 * kSampleBatch) + al((size_t)n);
+  const size_t total = lay(nullptr);
   if (s.reserve(total)) return ctx->fail(MOCAP_E_HIP, "hipMalloc(%zu) failed", total);
-  unsigned char* p = (unsigned char*)s.ptr;
-  float* d_p1 = (float*)p;        p += al(b_pts);
-  float* d_p2 = (float*)p;        p += al(b_pts);
-  int32_t* d_idx = (int32_t*)p;   p += al(sizeof(int32_t) * 7 * kSampleBatch);
-  double* d_F = (double*)p;       p += al(sizeof(double) * 27 * kSampleBatch);
-  int32_t* d_nF = (int32_t*)p;    p += al(sizeof(int32_t) * 3 * kSampleBatch);
-  int32_t* d_cnt = (int32_t*)p;   p += al(sizeof(int32_t) * 3 * kSampleBatch);
-  uint8_t* d_mask = (uint8_t*)p;
+  lay(s.ptr);
   HIP_TRY(ctx, hipMemcpyAsync(d_p1, p1, b_pts, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_p2, p2, b_pts, hipMemcpyHostToDevice, ctx->stream));
   CvRng rng;

@@ -286,9 +286,9 @@ def test_divmod_tiny_is_exact_for_every_operand_the_block_decode_can_see():
     for inv in (inv0, np.nextafter(inv0, np.float32(0)), np.nextafter(inv0, np.float32(2))):
         q = (rem.astype(np.float64) * inv.astype(np.float64) + 2.0 ** -8).astype(np.float32).astype(np.int64)
         assert np.array_equal(q, rem // n)
-    # the launch keeps the operands inside that range: block sizes are lowered until bb_pl * M_max < 2^13 (capi.hip), and
+    # the launch keeps the operands inside that range: block sizes are lowered until bb_pl * M_max < 2^13 (frame_capi.hip), and
     # the search kernel takes M_max <= 64 only (frame_bb_fits)
-    src = open(os.path.join(ROOT, "low-cost-mocap_amd", "csrc", "capi.hip")).read()
+    src = open(os.path.join(ROOT, "low-cost-mocap_amd", "csrc", "frame_capi.hip")).read()
     assert "(size_t)a.bb_pl * M_max * 2 * 256 >= ((size_t)1 << 22)" in src
     assert "M <= 64" in open(os.path.join(ROOT, "low-cost-mocap_amd", "csrc", "frame_bb.hip")).read()
 
