@@ -86,7 +86,12 @@ const char* mocap_last_error(const mocap_ctx* ctx);
 const char* mocap_version(void);
 /* mocap_last_frame_kernel: which kernel the last frame batch of this context went to ("frame_bb_kernel<CW=1>" = the
  * exact branch-and-bound kernel of csrc/frame_bb.hip, "frame_kernel<256>" = the exhaustive walk, ...).  Diagnostic:
- * results never depend on it.  The string is a literal owned by the library. */
+ * results never depend on it.  The string is a literal owned by the library.
+ * Which rigs take the search: every intrinsic matrix plain ([[fx,0,cx],[0,fy,cy],[0,0,1]]), <= 16 cameras, <= 64 blobs
+ * per camera, <= 255 roots, frames big enough for a 256-lane workgroup.  All cameras sharing ONE matrix report
+ * "frame_bb_kernel<CW=1>" / "<CW=2>" (<= 8 / 9-16 cameras); one matrix PER CAMERA, as a calibration gives them, reports
+ * "frame_bb_kernel<CW=1, per-camera K>" / "<CW=2, per-camera K>".  A matrix with skew (or any other entry outside that
+ * form) sends the rig to the general kernel ("frame_kernel<...>"), as do MOCAP_EVAL_BB=0 and MOCAP_OPT_EXHAUSTIVE_WALK. */
 const char* mocap_last_frame_kernel(mocap_ctx* ctx);
 
 /* enqueue on an existing hipStream_t (e.g. the host framework's current stream);

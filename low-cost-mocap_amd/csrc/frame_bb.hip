@@ -1,8 +1,9 @@
-// frame_bb.hip -- the frame path for the realistic rigs (identical plain intrinsics, <= 16 cameras, <= 64 blobs per
+// frame_bb.hip -- the frame path for the realistic rigs (plain intrinsics -- one matrix for all cameras, or one per camera
+// as a calibration gives them: frame_bb_calib_kernel, BBState's PERK --, <= 16 cameras, <= 64 blobs per
 // camera, <= 255 roots): epipolar correspondence search + EXACT branch-and-bound selection, one 256-lane workgroup per
 // frame, persistent, everything between the blob arrays in and the kept points out in LDS.  Replaces
 //   find_point_correspondance_and_object_points   (reference computer_code/api/helpers.py:339-421)
-// like frame_kernel.hip does (which keeps the general case: per-camera intrinsics, wide frames, tiny frames, and
+// like frame_kernel.hip does (which keeps the general case: intrinsics that are not plain, wide frames, tiny frames, and
 // the exhaustive walk every result of this file is tested against, MOCAP_EVAL_BB=0).
 //
 // What is different from frame_kernel.hip (measurements: DESIGN.md 3.1, docs/HISTORY.md):
@@ -175,23 +176,26 @@ struct Packed {
 // per reprojected view: arguments -> RT -> arguments -> K4, four dependent scalar-cache round trips around 42 vector
 // instructions.  The base is kept in registers (its value is hidden from the optimiser once, at the start of the
 // kernel), so a view costs one round trip, and K4 (one entry: identical intrinsics) is read once per candidate.
-template <int CT>
+// PERK (per-camera intrinsics, the calibrated rigs): Pq is [j][C][12] = K[j] [R|t][c] for j <= c (12 C C doubles), K4 has one
+// entry per intrinsics index; the other tables follow at the offsets that gives.
+template <int CT, bool PERK = false>
 struct BBCamTables {
   const double* base;
   static constexpr int C = CT;
+  static constexpr int kPq = PERK ? 12 * CT * CT : 12 * CT;
   __device__ __forceinline__ ctab_t pq(size_t off) const { return as_ctab(base + off); }
-  __device__ __forceinline__ ctab_t rt(size_t off) const { return as_ctab(base + 12 * CT + off); }
-  __device__ __forceinline__ ctab_t k4(size_t off) const { return as_ctab(base + 24 * CT + off); }
-  __device__ __forceinline__ const double* f() const { return base + 28 * CT; }
+  __device__ __forceinline__ ctab_t rt(size_t off) const { return as_ctab(base + kPq + off); }
+  __device__ __forceinline__ ctab_t k4(size_t off) const { return as_ctab(base + kPq + 12 * CT + off); }
+  __device__ __forceinline__ const double* f() const { return base + kPq + 16 * CT; }
 };
-template <>
-struct BBCamTables<0> {
+template <bool PERK>
+struct BBCamTables<0, PERK> {
   const double* base;
   int C;
   __device__ __forceinline__ ctab_t pq(size_t off) const { return as_ctab(base + off); }
-  __device__ __forceinline__ ctab_t rt(size_t off) const { return as_ctab(base + 12 * C + off); }
-  __device__ __forceinline__ ctab_t k4(size_t off) const { return as_ctab(base + 24 * C + off); }
-  __device__ __forceinline__ const double* f() const { return base + 28 * C; }
+  __device__ __forceinline__ ctab_t rt(size_t off) const { return as_ctab(base + (PERK ? 12 * C * C : 12 * C) + off); }
+  __device__ __forceinline__ ctab_t k4(size_t off) const { return as_ctab(base + (PERK ? 12 * C * C + 12 * C : 24 * C) + off); }
+  __device__ __forceinline__ const double* f() const { return base + (PERK ? 12 * C * C + 16 * C : 28 * C); }
 };
 
 // Issue priority of the frame's phases (s_setprio: arbitration between the waves of one SIMD -- here the four frames
@@ -211,11 +215,18 @@ __device__ __forceinline__ void bb_prio() {
 // out of every phase -- 5.72 -> 5.39 ms per 100 k frames of 8 x 16), 0 = runtime.  ML is the frame's M_max itself (the
 // blob buffers are copied flat); RL only has to hold K_max roots: the slot arrays are laid out for RL, the root limit
 // and the output stride stay K_max.
-template <bool F32R, int CW, int CT, int ML, int RL>
+// PERK: per-camera intrinsics (frame_bb_calib_kernel below).  The reference takes the intrinsics of a view by the POSITION of
+// its camera among the cameras the group sees (helpers.py:305-307, :231-237); every candidate of a root sees the same cameras,
+// so the position is a property of (root, camera): the running count of seen cameras in every ascending camera loop below.
+// The per-blob DLT table holds the contribution at position = camera (K[c] with pose c: a camera-0 root seen by every camera
+// before c, the common case); a view at a lower position (a camera before it saw nothing of the root, or the root was created
+// at a later camera) takes dlt_contribution on Pq[position][camera] on the spot -- the same function on the same operands
+// as the exhaustive walk's, hence the same bits, summed in the same ascending camera order.
+template <bool F32R, int CW, int CT, int ML, int RL, bool PERK = false>
 struct BBState {
   static constexpr int T = kBBThreads, W = kBBWaves;
   const FrameArgs& p;
-  BBCamTables<CT> cv;
+  BBCamTables<CT, PERK> cv;
   const int C_, M, R, RS;  // R = K_max (root limit, output stride), RS = root slots of the layout
   int tid, lane, wave;
   // The lane's number taken afresh (an empty asm the optimiser cannot see through): what a phase derives from it -- LDS addresses,
@@ -737,7 +748,7 @@ struct BBState {
           const float2 v = bxy[i];
           om = fmaxf(om, fmaxf(fabsf(v.x), fabsf(v.y)));
           double Bc[10];
-          dlt_contribution(Bc, cv.pq(12 * c), (double)v.x, (double)v.y);
+          dlt_contribution(Bc, cv.pq(PERK ? 12 * (c * C + c) : 12 * c), (double)v.x, (double)v.y);
 #pragma unroll
           for (int e = 0; e < 10; e++) bt[(size_t)i * 10 + e] = Bc[e];
         }
@@ -848,6 +859,21 @@ struct BBState {
   // ---------------------------------------------------------------- phase D
   // DLT matrix of candidate `rem` of root r with the first `skip` multi-hit cameras left open (skip = 0: the whole
   // group, rem = candidate index; skip = bnl[r]: the block's partial group, rem = block index).  Returns the views.
+  // B += the DLT contribution of blob k of camera c, the camera at position j among the group's seen cameras
+  __device__ __forceinline__ void add_view(double (&B)[10], int c, uint32_t k, int j) const {
+    if (PERK && j != c) {
+      const float2 w = bxy[(size_t)c * M + k];
+      double Bc[10];
+      dlt_contribution(Bc, cv.base + 12 * ((size_t)j * cn() + c), (double)w.x, (double)w.y);  // (per-lane position: vector loads, L1/L2-resident table)
+#pragma unroll
+      for (int e = 0; e < 10; e++) B[e] = B[e] + Bc[e];
+    } else {
+      const double* t = bt + ((size_t)c * M + k) * 10;
+#pragma unroll
+      for (int e = 0; e < 10; e++) B[e] = B[e] + t[e];
+    }
+  }
+
   template <bool WITH_B>
   __device__ __forceinline__ int group_matrix(int r, uint32_t rem, int skip, double (&B)[10], Packed<CW>& pk) const {
     const int C = cn();
@@ -856,16 +882,20 @@ struct BBState {
     const uint8_t* hr = hits + (size_t)r * C * M;
     pk.clear();
     int v = 0, ka = 0;
+    int j = 0;  // PERK: position of camera c among the root's seen cameras -- the open ones of a partial group count
     if (WITH_B) {
 #pragma unroll
       for (int e = 0; e < 10; e++) B[e] = 0.0;
     }
     for (int c = 0; c < C; c++) {
       uint32_t k = 0xFFu;
+      bool seen = false;
       if (c == rc) {
         k = root_blob[r];
+        seen = true;
       } else if (c > rc) {
         const uint32_t n = nhr[c];
+        seen = n != 0;
         if (n == 1) {
           k = hr[(size_t)c * M];
         } else if (n > 1) {
@@ -880,14 +910,11 @@ struct BBState {
         }
       }
       if (k != 0xFFu) {
-        if (WITH_B) {
-          const double* t = bt + ((size_t)c * M + k) * 10;
-#pragma unroll
-          for (int e = 0; e < 10; e++) B[e] = B[e] + t[e];
-        }
+        if (WITH_B) add_view(B, c, k, j);
         v++;
         pk.set(c, k);
       }
+      if (PERK) j += seen ? 1 : 0;
     }
     return v;
   }
@@ -920,12 +947,21 @@ struct BBState {
     }
 #pragma unroll
     for (int ee = 0; ee < 10; ee++) B[ee] = 0.0;
+    if constexpr (PERK) {
+      int j = 0;  // (the group is complete: its cameras are the root's seen cameras)
 #pragma unroll CT > 0 ? CT : 1
-    for (int c = 0; c < C; c++) {
-      const uint32_t k = pk.get(c);
-      const double* t = bt + (size_t)(k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
+      for (int c = 0; c < C; c++) {
+        const uint32_t k = pk.get(c);
+        if (k != 0xFFu) add_view(B, c, k, j++);
+      }
+    } else {
+#pragma unroll CT > 0 ? CT : 1
+      for (int c = 0; c < C; c++) {
+        const uint32_t k = pk.get(c);
+        const double* t = bt + (size_t)(k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
 #pragma unroll
-      for (int ee = 0; ee < 10; ee++) B[ee] = B[ee] + t[ee];
+        for (int ee = 0; ee < 10; ee++) B[ee] = B[ee] + t[ee];
+      }
     }
     return bv[r];
   }
@@ -1065,21 +1101,18 @@ struct BBState {
               return true;
             };
             const double bound = __longlong_as_double((long long)rbound[r]);
-            solve_and_score<true, true, F32R, false>(cv, B, v, obs_p, X, e, bound * (double)(2 * v) * (1.0 + 0x1p-40), ec);
+            solve_and_score<!PERK, true, F32R, false>(cv, B, v, obs_p, X, e, bound * (double)(2 * v) * (1.0 + 0x1p-40), ec);
 #ifdef MOCAP_DEBUG_EIGCHECK  // self-check build: a candidate whose evaluation was cut short must not beat the bound it was cut against
             if (!(e < inf)) {
               double B2[10], X2[3], e2;
 #pragma unroll
               for (int ee = 0; ee < 10; ee++) B2[ee] = 0.0;
+              int j2 = 0;
               for (int c = 0; c < C; c++) {
                 const uint32_t k = pk.get(c);
-                if (k != 0xFFu) {
-                  const double* t = bt + ((size_t)c * M + k) * 10;
-#pragma unroll
-                  for (int ee = 0; ee < 10; ee++) B2[ee] = B2[ee] + t[ee];
-                }
+                if (k != 0xFFu) add_view(B2, c, k, j2++);
               }
-              solve_and_score<true, true, F32R>(cv, B2, v, obs_p, X2, e2);
+              solve_and_score<!PERK, true, F32R>(cv, B2, v, obs_p, X2, e2);
               atomicAdd(&p.status[p.n_frames], 1);
               if (e2 <= bound) printf("EIGCHECK candidate: root %d g %u bound %.17g true %.17g\n", r, gl, bound, e2);
             }
@@ -1165,7 +1198,7 @@ struct BBState {
                 y = (double)w.y;
                 return true;
               };
-              solve_and_score<true, true, F32R>(cv, B2, v2, obs2, X2, e2);
+              solve_and_score<!PERK, true, F32R>(cv, B2, v2, obs2, X2, e2);
               atomicAdd(&p.status[p.n_frames + 1], 1);
               if (e2 <= bound) printf("EIGCHECK block: root %d block %u candidate %u bound %.17g true %.17g\n", r, gh, l, bound, e2);
             }
@@ -1216,6 +1249,7 @@ struct BBState {
     uint32_t rem = gl;  // decode the winning group
     const int rc = root_cam[r];
     int16_t* co = p.corr + o * C;
+    int j = 0;
     for (int c = 0; c < C; c++) {
       int16_t s = -1;
       if (c == rc) {
@@ -1233,11 +1267,7 @@ struct BBState {
         }
       }
       co[c] = s;
-      if (s >= 0) {
-        const double* t = bt + ((size_t)c * M + (uint32_t)s) * 10;
-#pragma unroll
-        for (int ee = 0; ee < 10; ee++) B[ee] = B[ee] + t[ee];
-      }
+      if (s >= 0) add_view(B, c, (uint32_t)s, j++);
     }
     double X[3];
     solve_point(B, X);
@@ -1248,59 +1278,19 @@ struct BBState {
 template <bool F32R, int CW, int CT, int ML, int RL>
 __global__ __launch_bounds__(kBBThreads, bb_wg_per_cu(RL)) void frame_bb_kernel(FrameArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  BBState<F32R, CW, CT, ML, RL> st(p, smem);
-  const int tid = threadIdx.x;
-  const FrameQueues& q = p.q;
-  // software pipeline over the frames: while frame k is searched, frame k + 1 has been pulled from the queue (one frame
-  // per pull: frames of this size are never cheap enough for the queue atomic to matter) and is on its way from HBM
-  // into the spare LDS buffer
-  if (tid == 0) {
-    const int it = q_add(&q.counters[QC_NEXT_FRAME], 1);
-    st.misc[MI_ITEM] = it < frame_count(p) ? it : -1;
-  }
-  if (tid < 10) st.bt[(size_t)st.cn() * st.M * 10 + tid] = 0.0;  // the table's record of zeros (never overwritten)
-  __syncthreads();
-  int item = st.misc[MI_ITEM];
-  if (item >= 0) st.prefetch_lds(item);
-  wait_own_stores();
-  __syncthreads();
-  while (item >= 0) {
-    const int64_t frame = item;
-    bb_prio<kPrioPhase>();
-    st.stage(frame);
-    st.match();
-    bb_prio<kPrioEval>();
-    const int next = st.misc[MI_NEXT];
-    if (next >= 0) st.prefetch_lds(next);  // in flight during the search
-    if (tid == 0) {
-      const int status = st.misc[MI_STATUS];
-      p.n_out[frame] = status ? 0 : st.misc[MI_NOUT];
-      p.status[frame] = status;
-      if (p.n_cand) p.n_cand[frame] = st.misc[MI_G];
-    }
-    const uint32_t G = (uint32_t)st.misc[MI_G];
-    if (G) {
-      // the bound tests pay their fixed cost (seed pass + a test per block) only on frames with enough candidates;
-      // smaller frames queue every block -- same evaluation rounds, same result
-      st.search(G >= (uint32_t)p.bb_min_g);
-      bb_prio<kPrioPhase>();
-      const int nroots = st.misc[MI_NROOTS];
-      st.fresh_tid();
-      for (int r = st.tid; r < nroots; r += kBBThreads) {
-        if (st.outslot[r] < 0) continue;
-        double e;
-        uint32_t gl;
-        if (st.root_winner(r, e, gl)) st.write_point(frame, r, e, gl);
-      }
-    }
-    wait_own_stores();  // ... and loads: the next frame's blobs are in LDS
-    bb_prio<kPrioEval>();
-    __syncthreads();  // the frame's LDS state is dead: the next one may be staged
-    item = next;
-  }
-  // the last workgroup to leave puts the queue counters back to zero: the next launch needs no memset
-  if (tid == 0 && q_add(&q.counters[QC_EXITED], 1) == (int)gridDim.x - 1)
-    for (int c = 0; c < QC_COUNT; c++) q_store(&q.counters[c], 0);
+#define BB_STATE BBState<F32R, CW, CT, ML, RL>
+#include "frame_bb_body.inc"
+#undef BB_STATE
+}
+
+// The same search for rigs whose cameras have intrinsics of their own (every K plain, no two need be equal): BBState's PERK
+// paths.  A kernel name of its own rather than a sixth template parameter: the identical-K instantiations keep their symbols.
+template <bool F32R, int CW, int CT, int ML, int RL>
+__global__ __launch_bounds__(kBBThreads, bb_wg_per_cu(RL)) void frame_bb_calib_kernel(FrameArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#define BB_STATE BBState<F32R, CW, CT, ML, RL, true>
+#include "frame_bb_body.inc"
+#undef BB_STATE
 }
 
 int frame_bb_wg_per_cu_cap(int C, int M, int R) { return bb_wg_per_cu(bb_fixed_slots(C, M, R)); }
@@ -1308,24 +1298,22 @@ size_t frame_bb_ws_bytes(int) { return 0; }  // (no per-workgroup HBM workspace:
 
 hipError_t launch_frame_bb(const FrameArgs& a, int grid, hipStream_t stream) {
   const size_t lds = frame_bb_lds_bytes(a.cv.C, a.M, a.K_max);
-  // the kernel addresses the tables from one base (BBCamTables): identical intrinsics, the block layout of mocap_set_cameras
-  if (!a.cv.uniformK || a.cv.RT != a.cv.Pq + 12 * a.cv.C || a.cv.K4 != a.cv.Pq + 24 * a.cv.C || a.cv.F != a.cv.Pq + 28 * a.cv.C)
-    return hipErrorInvalidValue;
+  // the kernel addresses the tables from one base (BBCamTables): the block layout of mocap_set_cameras, whose Pq is 12 C
+  // doubles for identical intrinsics and 12 C C otherwise
+  const size_t nPq = a.cv.uniformK ? (size_t)12 * a.cv.C : (size_t)12 * a.cv.C * a.cv.C;
+  if (a.cv.RT != a.cv.Pq + nPq || a.cv.K4 != a.cv.RT + 12 * a.cv.C || a.cv.F != a.cv.K4 + 4 * a.cv.C) return hipErrorInvalidValue;
   void (*k)(FrameArgs);
   const bool f32 = a.cv.f32_rounding != 0;
   const int fixed = bb_fixed_slots(a.cv.C, a.M, a.K_max);
-  if (fixed == 48)
-    k = f32 ? frame_bb_kernel<true, 1, 8, 16, 48> : frame_bb_kernel<false, 1, 8, 16, 48>;
-  else if (fixed == 64)
-    k = f32 ? frame_bb_kernel<true, 1, 8, 16, 64> : frame_bb_kernel<false, 1, 8, 16, 64>;
-  else if (fixed)
-    return hipErrorInvalidValue;
-  else if (a.cv.C == 8)
-    k = f32 ? frame_bb_kernel<true, 1, 8, 0, 0> : frame_bb_kernel<false, 1, 8, 0, 0>;
-  else if (a.cv.C <= 8)
-    k = f32 ? frame_bb_kernel<true, 1, 0, 0, 0> : frame_bb_kernel<false, 1, 0, 0, 0>;
-  else
-    k = f32 ? frame_bb_kernel<true, 2, 0, 0, 0> : frame_bb_kernel<false, 2, 0, 0, 0>;
+  if (fixed && fixed != 48 && fixed != 64) return hipErrorInvalidValue;
+#define BB_PICK(KERNEL)                                                                             \
+  (fixed == 48       ? (f32 ? KERNEL<true, 1, 8, 16, 48> : KERNEL<false, 1, 8, 16, 48>)             \
+   : fixed == 64     ? (f32 ? KERNEL<true, 1, 8, 16, 64> : KERNEL<false, 1, 8, 16, 64>)             \
+   : a.cv.C == 8     ? (f32 ? KERNEL<true, 1, 8, 0, 0> : KERNEL<false, 1, 8, 0, 0>)                 \
+   : a.cv.C <= 8     ? (f32 ? KERNEL<true, 1, 0, 0, 0> : KERNEL<false, 1, 0, 0, 0>)                 \
+                     : (f32 ? KERNEL<true, 2, 0, 0, 0> : KERNEL<false, 2, 0, 0, 0>))
+  k = a.cv.uniformK ? BB_PICK(frame_bb_kernel) : BB_PICK(frame_bb_calib_kernel);
+#undef BB_PICK
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -56,11 +56,11 @@ FramePlan plan_frame(const mocap_ctx* ctx, int M_max, int K_max, int hit_cap_ove
   pl.hit_cap = cap < 1 ? 1 : (cap > M_max ? M_max : cap);
   // (a narrow frame with identical intrinsics keeps blob indices in one byte with 0xFF = none: 256 slots go wide)
   pl.wide = must_go_wide(ctx, M_max);
-  // The realistic rigs go to their own kernel (csrc/frame_bb.hip: exact branch and bound): identical plain intrinsics
-  // (the eigenvalue bounds need K = [[fx,0,cx],[0,fy,cy],[0,0,1]]), <= 16 cameras, <= 64 blobs per camera, <= 255 roots,
+  // The realistic rigs go to their own kernel (csrc/frame_bb.hip: exact branch and bound): plain intrinsics, identical or one
+  // matrix per camera (the eigenvalue bounds need every K = [[fx,0,cx],[0,fy,cy],[0,0,1]]: p3max2 > 0 says so), <= 16 cameras, <= 64 blobs per camera, <= 255 roots,
   // frames big enough for a 256-lane workgroup (or 256 lanes asked for: MOCAP_FRAME_THREADS / mocap_set_tuning).  Everything
   // else -- and MOCAP_EVAL_BB=0 -- takes the exhaustive walk.  (Decided before narrow / wide: its layout has no odometer columns and fits where the general narrow one does not.)
-  pl.use_bb = ctx->eval_bb && !ctx->exhaustive && !pl.wide && ctx->cv.uniformK && ctx->prune && ctx->eigcut && ctx->p3max2 > 0.0 && ctx->p3max2c > 0.0 &&
+  pl.use_bb = ctx->eval_bb && !ctx->exhaustive && !pl.wide && ctx->prune && ctx->eigcut && ctx->p3max2 > 0.0 && ctx->p3max2c > 0.0 &&
               (ctx->frame_threads == 256 || (ctx->frame_threads == 0 && ctx->C * M_max > 32)) && ctx->frame_launches != 3 &&
               frame_bb_fits(ctx->C, M_max, K_max);
   if (pl.use_bb) {
@@ -95,7 +95,7 @@ FramePlan plan_frame(const mocap_ctx* ctx, int M_max, int K_max, int hit_cap_ove
 // lists uncapped (M_max, whatever the context's cap) and at the smallest workgroup plan_frame would come down to
 // (whatever frame_threads asks for).
 bool frame_shape_fits(const mocap_ctx* ctx, int M_max, int K) {
-  if (frame_bb_fits(ctx->C, M_max, K) && ctx->cv.uniformK && !ctx->force_wide && M_max <= 255) return true;
+  if (frame_bb_fits(ctx->C, M_max, K) && (ctx->cv.uniformK || ctx->p3max2 > 0.0) && !ctx->force_wide && M_max <= 255) return true;  // (one K per camera: the search takes them when all are plain)
   if (!must_go_wide(ctx, M_max) && frame_lds(ctx, M_max, K, 64, M_max, false) <= kLdsBytes) return true;
   return frame_lds(ctx, M_max, K, kWideThreads, M_max, true) <= kLdsBytes;
 }
@@ -225,7 +225,8 @@ int launch_frames(mocap_ctx* ctx, const FrameArgs& a, const FramePlan& pl, int64
   const int64_t grid = full_grid < a.n_frames ? full_grid : a.n_frames;
   if (pl.use_bb) {
     // frames only: a frame's cost follows its surviving blocks, not its candidate count -- no heavy list, no slices
-    ctx->last_frame_kernel = ctx->C <= 8 ? "frame_bb_kernel<CW=1>" : "frame_bb_kernel<CW=2>";
+    ctx->last_frame_kernel = ctx->cv.uniformK ? (ctx->C <= 8 ? "frame_bb_kernel<CW=1>" : "frame_bb_kernel<CW=2>")
+                                              : (ctx->C <= 8 ? "frame_bb_kernel<CW=1, per-camera K>" : "frame_bb_kernel<CW=2, per-camera K>");
     HIP_TRY(ctx, launch_frame_bb(a, (int)grid, ctx->stream));
     ctx->frame_q_clean[qs] = true;
     return MOCAP_OK;

@@ -100,6 +100,23 @@ def ring_rig(num_cameras, radius=3.0, height=1.5, K=None, image_size=None):
             "image_size": image_size, "centre": centre, "R0": R0}
 
 
+def calibrated_ring_rig(num_cameras, seed=0, K=None, **kw):
+    """ring_rig with per-camera intrinsics as a calibration would give them: fx, fy within +-1 % and cx, cy within
+    +-15 px of the nominal matrix, each camera drawn on its own (the spread of the three calibrated matrices the
+    reference ships in its camera-parameter file).  Every K stays plain ([[fx,0,cx],[0,fy,cy],[0,0,1]]), no two are
+    equal.  Seeded: the same (num_cameras, seed, K) give the same rig."""
+    rig = ring_rig(num_cameras, K=K, **kw)
+    rng = np.random.default_rng([int(seed), 0xCA11B])
+    Ks = rig["K"].copy()
+    for c in range(len(Ks)):
+        Ks[c, 0, 0] *= 1.0 + rng.uniform(-0.01, 0.01)
+        Ks[c, 1, 1] *= 1.0 + rng.uniform(-0.01, 0.01)
+        Ks[c, 0, 2] += rng.uniform(-15.0, 15.0)
+        Ks[c, 1, 2] += rng.uniform(-15.0, 15.0)
+    rig["K"] = Ks
+    return rig
+
+
 def rig_to_pose_dicts(rig):
     """Poses in the JSON shape the reference's socket API carries ({"R": 3x3, "t": 3})."""
     return [{"R": rig["R"][i].tolist(), "t": rig["t"][i].tolist()} for i in range(len(rig["R"]))]
