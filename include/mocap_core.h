@@ -52,7 +52,10 @@ enum {
   MOCAP_ST_INTRACTABLE = 16,  /* set WITH MOCAP_ST_CAND_OVERFLOW by the re-submit pass: a root of the frame has more than 2^24
                                  candidate groups and the exact search over its multi-hit cameras (csrc/heavy_bb.hip) could not
                                  bound it -- no enumeration reaches it, the reference's own (helpers.py:394-400) included;
-                                 bits 20..28 of the status word then hold ceil(log2(groups)) of the largest such root */
+                                 bits 20..28 of the status word then hold ceil(log2(groups)) of the largest such root.  The
+                                 search runs wherever every intrinsic matrix is plain ([[fx,0,cx],[0,fy,cy],[0,0,1]]), one
+                                 matrix for all cameras or one per camera; with a skewed matrix such a root keeps
+                                 MOCAP_ST_CAND_OVERFLOW | MOCAP_ST_FINAL alone */
   MOCAP_ST_FINAL = 32         /* set by the re-submit pass on a frame it leaves flagged: larger caps do not exist, a repeated
                                  re-submit skips the frame (frames WITHOUT this bit that are still flagged were not reached:
                                  scratch batch full -- mocap_resubmit_dev continues with them) */
@@ -76,7 +79,8 @@ enum {
                                    exact search gives up on (2^16 .. 2^24 groups: ~3 ms of the whole GPU each, csrc/heavy_bb.hip
                                    heavy_enum_kernel); their frames keep MOCAP_ST_CAND_OVERFLOW | MOCAP_ST_FINAL instead.  For
                                    callers that prefer a bounded step time to the last 0.1 % of the frames of a stress batch;
-                                   every frame that is returned is still exact. */
+                                   every frame that is returned is still exact.  Means the same on every rig the search runs on
+                                   (every intrinsic matrix plain, identical or one per camera). */
 };
 
 /* ---------------------------------------------------------------- lifetime */
@@ -188,7 +192,13 @@ int mocap_resubmit_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float*
  * {frames flagged by the first pass, frames re-run}; the two differ only when the scratch batch could not hold every flagged
  * frame (the whole batch while that takes at most 256 MB, else one frame in eight, within MOCAP_RESUBMIT_SCRATCH_MB, default 8192; halved
  * until the allocation succeeds) -- those keep their status WITHOUT MOCAP_ST_FINAL: mocap_resubmit_dev continues with them
- * (the host-buffer entry points loop until none is left). */
+ * (the host-buffer entry points loop until none is left).
+ * Where the second pass runs the wide variant and every intrinsic matrix is plain ([[fx,0,cx],[0,fy,cy],[0,0,1]]: one matrix
+ * for all cameras or one per camera, as a calibration gives them), a root above 4 096 groups (MOCAP_RESUBMIT_G_CAP) is not
+ * enumerated but handed to the exact search of csrc/heavy_bb.hip, which also solves roots no enumeration reaches (above 2^24
+ * groups: two markers behind each other as seen from the root's camera); what it cannot bound is enumerated up to 2^24 groups
+ * (unless MOCAP_OPT_BOUNDED_RESUBMIT) and flagged MOCAP_ST_INTRACTABLE above.  With a skewed matrix the pass enumerates up to
+ * 2^24 groups per root and flags what is larger. */
 int mocap_match_triangulate_dev_auto(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
                                      const int32_t* d_counts, double gate_px, int K_max, int64_t G_cap,
                                      double* d_xyz, double* d_err, int16_t* d_corr, int32_t* d_n_out,

@@ -406,10 +406,12 @@ int resubmit_dev_locked(mocap_ctx* ctx, const FrameBatch& b, int K_max, const Fr
   ra.info = d_info;
   // Roots whose product no enumeration reaches (two markers behind each other from the root's camera: 2^60 groups at 64
   // cameras) go to the heavy-root search (csrc/heavy_bb.hip) where the second pass runs the wide variant on cameras of the
-  // form EigCut needs: the pass enumerates up to MOCAP_RESUBMIT_G_CAP groups per root (default 4096) and exports the
-  // roots above it; elsewhere it enumerates up to 2^24 per root and flags what is larger, as before.
+  // form EigCut needs -- every intrinsic matrix plain, one for all cameras or one per camera (p3max2c > 0 says so; the kernels
+  // take their variant from CamView::uniformK, which travels in HeavyArgs::cv) --: the pass enumerates up to
+  // MOCAP_RESUBMIT_G_CAP groups per root (default 4096) and exports the roots above it; elsewhere (a skewed matrix, the
+  // exhaustive walk, MOCAP_NO_HEAVY_BB) it enumerates up to 2^24 per root and flags what is larger, as before.
   const FramePlan pl2 = plan_frame(ctx, M_max, K_big, M_max);
-  const bool heavy_ok = pl2.wide && ctx->cv.uniformK && ctx->prune && ctx->eigcut && ctx->p3max2 > 0.0 && !ctx->exhaustive && !getenv("MOCAP_NO_HEAVY_BB");
+  const bool heavy_ok = pl2.wide && (ctx->cv.uniformK || ctx->p3max2c > 0.0) && ctx->prune && ctx->eigcut && ctx->p3max2 > 0.0 && !ctx->exhaustive && !getenv("MOCAP_NO_HEAVY_BB");
   int64_t G2 = (int64_t)1 << 24;
   HeavyHook hk{nullptr, nullptr, 0};
   HeavyArgs ha;

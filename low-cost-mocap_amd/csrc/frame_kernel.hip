@@ -2006,9 +2006,11 @@ static hipError_t launch_TM(const FrameArgs& a, int grid, size_t lds, hipStream_
   else
     k = a.cv.uniformK ? frame_kernel<T, true, false, WIDE, MODE> : frame_kernel<T, false, false, WIDE, MODE>;
   if constexpr (WIDE && MODE == MODE_ALL) {
-    if (a.heavy_bb) {  // (identical intrinsics only: the host asks for it nowhere else)
-      if (!a.cv.uniformK) return hipErrorInvalidValue;
-      k = a.cv.f32_rounding ? frame_kernel<T, true, true, true, MODE_ALL, true> : frame_kernel<T, true, false, true, MODE_ALL, true>;
+    if (a.heavy_bb) {  // (plain intrinsics, one matrix or one per camera: the host asks for it nowhere else; the record carries nothing that depends on K)
+      if (a.cv.uniformK)
+        k = a.cv.f32_rounding ? frame_kernel<T, true, true, true, MODE_ALL, true> : frame_kernel<T, true, false, true, MODE_ALL, true>;
+      else
+        k = a.cv.f32_rounding ? frame_kernel<T, false, true, true, MODE_ALL, true> : frame_kernel<T, false, false, true, MODE_ALL, true>;
     }
   } else if (a.heavy_bb) {
     return hipErrorInvalidValue;

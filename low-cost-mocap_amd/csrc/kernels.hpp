@@ -88,7 +88,7 @@ __host__ __device__ inline size_t heavy_rec_bytes(int C, int Hs) { return (heavy
 // level, for roots whose product no enumeration reaches (two markers behind each other as seen from the root's camera:
 // two hits in nearly every camera, 2^60 groups)
 struct HeavyArgs {
-  CamView cv;
+  CamView cv;                  // cv.uniformK picks the variant: the identical-K kernels, or the per-camera-K ones (Pq is [position][camera][12])
   int M, K_big;
   double bb_c0[3], p3max2c, p3max2;
   const float* blobs;          // [frames][C][M][2] the batch the records' frame indices refer to

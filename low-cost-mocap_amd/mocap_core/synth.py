@@ -117,6 +117,12 @@ def calibrated_ring_rig(num_cameras, seed=0, K=None, **kw):
     return rig
 
 
+def calibrated_stress_rig(num_cameras=64, seed=0):
+    """stress_rig with per-camera intrinsics spread like calibrated_ring_rig's (fx, fy within +-1 %, cx, cy within +-15 px of
+    STRESS_K, every K plain, no two equal): the large calibrated rig.  Seeded like calibrated_ring_rig."""
+    return calibrated_ring_rig(num_cameras, seed=seed, K=STRESS_K, image_size=(16000, 16000))
+
+
 def rig_to_pose_dicts(rig):
     """Poses in the JSON shape the reference's socket API carries ({"R": 3x3, "t": 3})."""
     return [{"R": rig["R"][i].tolist(), "t": rig["t"][i].tolist()} for i in range(len(rig["R"]))]
