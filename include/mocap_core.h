@@ -328,6 +328,51 @@ int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const flo
                           int32_t* d_n_pts, int32_t* d_status, int O_max, double* d_pos, double* d_heading,
                           double* d_oerr, int32_t* d_drone, int32_t* d_n_obj);
 
+/* ---------------------------------------------------------------- object filter
+ * `filtered_objects` of the live loop (helpers.py:109, self.kalman_filter.predict_location(objects)): per drone index a
+ * cv.KalmanFilter(9, 6) in float32 (constant acceleration, measurement = position and finite-difference velocity, nearest
+ * candidate to the prediction wins) whose PREDICTED state is reported, the velocity and the chosen object's heading passed
+ * through the reference's LowPassFilter (lfilter from a zero state over a buffer that is cut back to its newer half whenever
+ * it reaches buffer_size, last sample kept).  computer_code/api/KalmanFilter.py and LowPassFilter.py, quirks included; the
+ * one difference is that the time stamp is an argument instead of time.time().  The state (Kalman vectors and matrices,
+ * previous positions, previous time, low-pass buffers) lives on the device, in the context.
+ *
+ * mocap_set_object_filter: allocates and zeroes the state (KalmanFilter.__init__).  num_objects = drone indices filtered
+ * (<= 8; 0 switches the filter off); b, a [n_taps] = the low-pass coefficients, e.g. scipy.signal.butter(5, 20 / 30)
+ * (n_taps <= 16); buffer_size as LowPassFilter's (2 .. 1024, reference 300); process_noise / measurement_noise = the
+ * diagonals of Q and R (reference 1e-2 and 1).  Beyond the limits: MOCAP_E_LIMIT. */
+int mocap_set_object_filter(mocap_ctx* ctx, int num_objects, int n_taps, const double* b, const double* a, int buffer_size,
+                            double process_noise, double measurement_noise);
+/* KalmanFilter.reset (KalmanFilter.py:103-108) at time `now`: the previous time becomes now - 20, every statePost and previous
+ * position is zeroed; covariances and low-pass buffers are NOT cleared.  Enqueued on the context's stream. */
+int mocap_reset_object_filter(mocap_ctx* ctx, double now);
+/* mocap_filter_objects: predict_location for n_frames consecutive frames, in order.
+ *   t [F] f64          the frames' time stamps (what time.time() returned in the reference)
+ *   O_max, pos [F][O_max][3], heading [F][O_max], drone [F][O_max], n_obj [F]   exactly mocap_locate_objects*'s outputs
+ *                      (n_obj > O_max counts as O_max; O_max <= 64)
+ *   fpos [F][D][3] f32, fvel [F][D][3] f32, fheading [F][D] f64   "pos", "vel", "heading" of drone index d (D = num_objects)
+ *   chosen [F][D] i32  index of the object the drone was associated with; -1 = the drone is not in `filtered_objects` this
+ *                      frame (no object carried its index): its state is untouched and fpos / fvel / fheading are NaN
+ * Cutting a session into calls of any lengths gives bit-identical outputs.  Before mocap_set_object_filter: MOCAP_E_ARG. */
+int mocap_filter_objects(mocap_ctx* ctx, int64_t n_frames, const double* t, int O_max, const double* pos, const double* heading,
+                         const int32_t* drone, const int32_t* n_obj, float* fpos, float* fvel, double* fheading, int32_t* chosen);
+int mocap_filter_objects_dev(mocap_ctx* ctx, int64_t n_frames, const double* d_t, int O_max, const double* d_pos,
+                             const double* d_heading, const int32_t* d_drone, const int32_t* d_n_obj, float* d_fpos,
+                             float* d_fvel, double* d_fheading, int32_t* d_chosen);
+/* mocap_track_frame / mocap_track_frame_dev with the filter behind the object search (O_max >= 1): t [F] in, the four filter
+ * outputs out, everything else as there.  The host form queues the filter's two kernels directly behind the export, their
+ * outputs land in the same pinned block as the rest of the payload: still one enqueue and one event wait. */
+int mocap_track_frame_filtered(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                               double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr,
+                               int32_t* n_pts, int32_t* status, int O_max, double* pos, double* heading, double* oerr,
+                               int32_t* drone, int32_t* n_obj, const double* t, float* fpos, float* fvel, double* fheading,
+                               int32_t* chosen);
+int mocap_track_frame_filtered_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs, const int32_t* d_counts,
+                                   double gate_px, int K_max, int64_t G_cap, double* d_xyz, double* d_err, int16_t* d_corr,
+                                   int32_t* d_n_pts, int32_t* d_status, int O_max, double* d_pos, double* d_heading,
+                                   double* d_oerr, int32_t* d_drone, int32_t* d_n_obj, const double* d_t, float* d_fpos,
+                                   float* d_fvel, double* d_fheading, int32_t* d_chosen);
+
 /* ---------------------------------------------------------------- initial poses
  * The pose-chaining loop of the `calculate-camera-pose` handler (index.py:229-270), i.e. the caller of
  * bundle_adjustment: per neighbouring camera pair cv.findFundamentalMat(FM_RANSAC, threshold, confidence)

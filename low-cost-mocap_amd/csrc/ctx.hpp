@@ -128,6 +128,12 @@ struct mocap_ctx {
   DevBuf heavy_enum;        // ... queue + per-workgroup winners of the roots enumerated over the whole GPU (heavy_enum_kernel)
   uint32_t resub_calls = 0; // ... parity selects the counter of the current call
   DevBuf scratch[4];        // [0] host-API staging, [1..3] bundle adjustment workspace
+  // object filter (mocap_set_object_filter): num_objects == 0 = off
+  int objf_D = 0, objf_B = 0;
+  float objf_q = 0.f, objf_r = 0.f;
+  DevBuf objf_state;        // ObjFilterState | h [B] | low-pass history [2][D][4][B] (a call reads one half and writes the other)
+  DevBuf objf_ws;           // per call: samples [D][4][F] | slots [F][D][2] | samples appended [D]
+  uint32_t objf_calls = 0;  // ... parity selects the half that holds the history
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);
@@ -144,3 +150,14 @@ int mocap_blob_stage_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_i
 int locate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const double* d_err,
                       const int32_t* d_n_pts, int O_max, double* d_pos, double* d_heading, double* d_oerr,
                       int32_t* d_drone, int32_t* d_lead, int32_t* d_n_obj);
+// object filter over the locator's outputs (object_filter_capi.hip); every pointer device-accessible; `who` names the entry point
+struct FilterIO {
+  const double* t;  // [F]
+  float* fpos;      // [F][D][3]
+  float* fvel;      // [F][D][3]
+  double* fheading; // [F][D]
+  int32_t* chosen;  // [F][D]
+};
+int filter_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int O_max, const FilterIO& io);
+int filter_dev_locked(mocap_ctx* ctx, int64_t n_frames, int O_max, const double* d_pos, const double* d_heading,
+                      const int32_t* d_drone, const int32_t* d_n_obj, const FilterIO& io);

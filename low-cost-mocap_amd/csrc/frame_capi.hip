@@ -732,7 +732,10 @@ struct TrackOut {
 };
 
 // images != null: raw frames [F][C][rows][cols][3] (host); else b.blobs / b.counts (host) are the input
-int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o) {
+// fo != null (mocap_track_frame_filtered): host time stamps in, the object filter's outputs out -- its two kernels are queued
+// behind the export and write into the same pinned block, the call still waits for one event
+int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o,
+                 const FilterIO* fo = nullptr) {
   const int64_t n_frames = b.n_frames;
   const int M_max = b.M_max;
   if (!ctx->C) return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_cameras has not been called");
@@ -747,15 +750,20 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (images && (!ctx->img_C || ctx->img_C != ctx->C))
     return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_image_params has not been called for this camera set");
   if (images && (!o.blobs || !o.counts || !o.blob_status)) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images: null blob buffer");
+  if (fo) {
+    const int rc = filter_check(ctx, "mocap_track_frame_filtered", n_frames, o.O_max, *fo);
+    if (rc) return rc;
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int C = ctx->C, O = o.O_max > 0 ? o.O_max : 1;
-  const size_t F = (size_t)n_frames;
+  const size_t F = (size_t)n_frames, FD = fo ? F * ctx->objf_D : 0;
   const size_t n_raw = images ? F * C * (size_t)ctx->img_rows * ctx->img_cols * 3 : 0;
   // caller-visible side (pinned host memory): inputs | frame outputs | objects
   float* h_blobs;
   int32_t *h_counts, *h_bstat, *h_drone, *h_nobj;
   FrameOut h;
   double *h_pos, *h_head, *h_oerr;
+  FilterIO hf{};
   auto lay_host = [&](void* base) {
     Carver c(base);
     h_blobs = c.take<float>(F * C * M_max * 2);
@@ -772,6 +780,13 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     h_oerr = c.take<double>(F * O);
     h_drone = c.take<int32_t>(F * O);
     h_nobj = c.take<int32_t>(F);
+    if (fo) {
+      hf.t = c.take<double>(F);
+      hf.fpos = c.take<float>(FD * 3);
+      hf.fvel = c.take<float>(FD * 3);
+      hf.fheading = c.take<double>(FD);
+      hf.chosen = c.take<int32_t>(FD);
+    }
     return c.off;
   };
   const size_t host_total = lay_host(nullptr);
@@ -875,6 +890,11 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     rc = resubmit_dev_locked(ctx, in, K_max, d, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, launch_track_export(la, ea, ctx->stream));
+    if (fo) {
+      memcpy(const_cast<double*>(hf.t), fo->t, sizeof(double) * F);
+      rc = filter_dev_locked(ctx, n_frames, O, h_pos, h_head, h_drone, h_nobj, hf);
+      if (rc) return rc;
+    }
     rc = spin_wait(ctx, ctx->live_event);
     if (rc) return rc;
   }
@@ -886,6 +906,12 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     memcpy(o.heading + f * O, h_head + f * O, sizeof(double) * no);
     memcpy(o.oerr + f * O, h_oerr + f * O, sizeof(double) * no);
     memcpy(o.drone + f * O, h_drone + f * O, sizeof(int32_t) * no);
+  }
+  if (fo) {
+    memcpy(fo->fpos, hf.fpos, sizeof(float) * FD * 3);
+    memcpy(fo->fvel, hf.fvel, sizeof(float) * FD * 3);
+    memcpy(fo->fheading, hf.fheading, sizeof(double) * FD);
+    memcpy(fo->chosen, hf.chosen, sizeof(int32_t) * FD);
   }
   if (images) {
     memcpy(o.counts, h_counts, sizeof(int32_t) * F * C);
@@ -940,4 +966,40 @@ extern "C" int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max
     if (rc) return rc;
   }
   return ctx->mark_enqueued();
+}
+
+extern "C" int mocap_track_frame_filtered(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                                          double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr,
+                                          int32_t* n_pts, int32_t* status, int O_max, double* pos, double* heading, double* oerr,
+                                          int32_t* drone, int32_t* n_obj, const double* t, float* fpos, float* fvel,
+                                          double* fheading, int32_t* chosen) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
+  const FilterIO fo{t, fpos, fvel, fheading, chosen};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, &fo);
+}
+
+extern "C" int mocap_track_frame_filtered_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
+                                              const int32_t* d_counts, double gate_px, int K_max, int64_t G_cap, double* d_xyz,
+                                              double* d_err, int16_t* d_corr, int32_t* d_n_pts, int32_t* d_status, int O_max,
+                                              double* d_pos, double* d_heading, double* d_oerr, int32_t* d_drone,
+                                              int32_t* d_n_obj, const double* d_t, float* d_fpos, float* d_fvel,
+                                              double* d_fheading, int32_t* d_chosen) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const FilterIO fo{d_t, d_fpos, d_fvel, d_fheading, d_chosen};
+  int rc = filter_check(ctx, "mocap_track_frame_filtered_dev", n_frames, O_max, fo);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
+  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
+  rc = match_dev_locked(ctx, b, K_max, G_cap, o);
+  if (rc) return rc;
+  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
+  if (rc) return rc;
+  rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
+  if (rc) return rc;
+  rc = filter_dev_locked(ctx, n_frames, O_max, d_pos, d_heading, d_drone, d_n_obj, fo);
+  return rc ? rc : ctx->mark_enqueued();
 }

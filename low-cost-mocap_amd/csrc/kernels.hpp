@@ -175,6 +175,44 @@ struct TrackExportArgs {
 };
 hipError_t launch_track_export(const LocateArgs& a, const TrackExportArgs& e, hipStream_t stream);
 
+// object filter over the locator's output (reference KalmanFilter.py + LowPassFilter.py: the `filtered_objects` of
+// helpers.py:109), csrc/object_filter.hip.  The state of the recurrence lives in one device record per context.
+constexpr int kObjFilterMaxObjects = 8, kObjFilterMaxTaps = 16, kObjFilterMaxBuffer = 1024, kObjFilterMaxSlots = 64;
+struct ObjFilterDrone {
+  float x[9];           // statePost
+  float P[81];          // errorCovPost
+  float prev_pos[3];
+  int32_t buf_len;      // rows the reference's low-pass buffers hold (the three filters of a drone share it)
+};
+struct ObjFilterState {
+  double prev_time;
+  ObjFilterDrone drone[kObjFilterMaxObjects];
+};
+struct ObjFilterArgs {
+  int64_t n_frames;
+  int D, O_max;             // drone indices filtered; object slots per frame
+  int B, keep;              // low-pass buffer_size; rows kept when the buffer reaches it (ceil(B / 2))
+  float q, r;               // process / measurement noise (diagonal)
+  const double* t;          // [F] time stamps
+  const double* pos;        // [F][O_max][3]   the locator's outputs
+  const double* heading;    // [F][O_max]
+  const int32_t* drone;     // [F][O_max]
+  const int32_t* n_obj;     // [F]
+  ObjFilterState* state;
+  const double* h;          // [B] impulse response of the low-pass
+  const double* hist_in;    // [D][4][B] the last B low-pass inputs before this call (channel: heading, vx, vy, vz)
+  double* hist_out;         // [D][4][B] ... after it
+  double* samp;             // [D][4][F] this call's low-pass inputs, appended per drone
+  int32_t* slot;            // [F][D][2] {index of the frame's sample in samp (-1 = drone absent), window length}
+  int32_t* n_samp;          // [D] samples appended by this call
+  float* fpos;              // [F][D][3]
+  float* fvel;              // [F][D][3]
+  double* fheading;         // [F][D]
+  int32_t* chosen;          // [F][D]
+};
+hipError_t launch_object_filter(const ObjFilterArgs& a, hipStream_t stream);  // scan kernel, then low-pass kernel
+hipError_t launch_object_filter_reset(ObjFilterState* state, int D, double now, hipStream_t stream);
+
 // compaction of a frame batch's valid points into fixed-stride records (the payload of the multi-GPU exchange)
 struct CompactArgs {
   int64_t n_frames;

@@ -18,6 +18,8 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("MOCAP_CORE_LIB") or os.path.join(_PKG_ROOT, "lib", "libmocap_core.so")
 
 MOCAP_OK = 0
+MOCAP_E_ARG = -1
+MOCAP_E_LIMIT = -4
 MOCAP_E_NOCONV = -5
 ST_ROOT_OVERFLOW = 1
 ST_CAND_OVERFLOW = 2
@@ -61,6 +63,14 @@ SIGNATURES = {
     "mocap_track_frame_images": (_i32, [_vp, _i64, _vp, _i32, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                         _vp, _vp, _vp]),
     "mocap_track_frame_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_set_object_filter": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _dbl, _dbl]),
+    "mocap_reset_object_filter": (_i32, [_vp, _dbl]),
+    "mocap_filter_objects": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_filter_objects_dev": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_filtered": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_filtered_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_image_params": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mocap_set_blob_options": (_i32, [_vp, _i32]),
     "mocap_get_undistort_map": (_i32, [_vp, _i32, _vp]),
@@ -87,7 +97,7 @@ _lib = None
 
 
 class MocapError(RuntimeError):
-    pass
+    code = None   # the MOCAP_E_* value, when the core returned one
 
 
 def load_library(path=None):
@@ -128,6 +138,7 @@ class MocapCore:
         self.C = 0
         self._hit_cap, self._force_wide = 32, False
         self.f32_rounding = True     # MOCAP_OPT_F32_ROUNDING, the library's default
+        self.filter_objects_n = 0    # drone indices of the object filter (set_object_filter), 0 = off
 
     def close(self):
         if getattr(self, "_h", None):
@@ -142,7 +153,9 @@ class MocapCore:
 
     def _check(self, rc, allow=()):
         if rc != MOCAP_OK and rc not in allow:
-            raise MocapError(f"mocap_core error {rc}: {self.lib.mocap_last_error(self._h).decode()}")
+            e = MocapError(f"mocap_core error {rc}: {self.lib.mocap_last_error(self._h).decode()}")
+            e.code = rc
+            raise e
         return rc
 
     def last_frame_kernel(self):
@@ -406,6 +419,76 @@ class MocapCore:
                                                   _p(out["pos"]), _p(out["heading"]), _p(out["error"]),
                                                   _p(out["droneIndex"]), _p(out["lead"]), _p(out["n_obj"])))
         return out
+
+    # ------------------------------------------------------------------ object filter (`filtered_objects`)
+    def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):
+        """mocap_set_object_filter: the reference's KalmanFilter(num_objects) on the device (KalmanFilter.py, LowPassFilter.py).
+        b, a: low-pass coefficients; default = the reference's butter(5, 20 / (60 / 2))."""
+        if b is None or a is None:
+            from scipy.signal import butter
+            b, a = butter(5, 20 / (60.0 / 2), btype="low")
+        b = np.ascontiguousarray(b, dtype=np.float64).ravel()
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        assert b.size == a.size
+        self._check(self.lib.mocap_set_object_filter(self._h, int(num_objects), b.size, _p(b), _p(a), int(buffer_size),
+                                                     float(process_noise), float(measurement_noise)))
+        self.filter_objects_n = int(num_objects)
+
+    def reset_object_filter(self, now):
+        self._check(self.lib.mocap_reset_object_filter(self._h, float(now)))
+
+    def _filter_outputs(self, F):
+        D = self.filter_objects_n
+        return {"fpos": np.full((F, D, 3), np.nan, dtype=np.float32), "fvel": np.full((F, D, 3), np.nan, dtype=np.float32),
+                "fheading": np.full((F, D), np.nan), "chosen": np.full((F, D), -1, dtype=np.int32)}
+
+    def filter_objects(self, t, pos, heading, drone, n_obj):
+        """mocap_filter_objects: t [F], and locate_objects' pos [F][O][3], heading [F][O], droneIndex [F][O], n_obj [F] ->
+        {"fpos", "fvel" float32 [F][D][3], "fheading" [F][D], "chosen" [F][D] (-1 = drone not in filtered_objects)}."""
+        t = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        F = t.size
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        O = pos.shape[1]
+        assert pos.shape == (F, O, 3)
+        heading = np.ascontiguousarray(heading, dtype=np.float64).reshape(F, O)
+        drone = np.ascontiguousarray(drone, dtype=np.int32).reshape(F, O)
+        n_obj = np.ascontiguousarray(n_obj, dtype=np.int32).reshape(F)
+        o = self._filter_outputs(F)
+        self._check(self.lib.mocap_filter_objects(self._h, F, _p(t), O, _p(pos), _p(heading), _p(drone), _p(n_obj), _p(o["fpos"]),
+                                                  _p(o["fvel"]), _p(o["fheading"]), _p(o["chosen"])))
+        return o
+
+    def filter_objects_dev(self, n_frames, d_t, O_max, d_pos, d_heading, d_drone, d_n_obj, d_fpos, d_fvel, d_fheading, d_chosen):
+        self._check(self.lib.mocap_filter_objects_dev(self._h, int(n_frames), _vp(d_t), int(O_max), _vp(d_pos), _vp(d_heading),
+                                                      _vp(d_drone), _vp(d_n_obj), _vp(d_fpos), _vp(d_fvel), _vp(d_fheading),
+                                                      _vp(d_chosen)))
+
+    def track_frame_filtered(self, blobs, counts, t, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8):
+        """mocap_track_frame_filtered: track_frame with the object filter behind the object search, t [F] = the frames' time
+        stamps.  A frame that needs more than K_max slots is reported like track_frame reports it (status, n_pts) and NOT
+        re-run here: the filter has consumed the call's time stamps."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        F, C, M, _ = blobs.shape
+        assert C == self.C and counts.shape == (F, C)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        K_max = min(C * M, 64) if K_max is None else int(K_max)
+        o = self._track_outputs(F, K_max, O_max)
+        o.update(self._filter_outputs(F))
+        self._check(self.lib.mocap_track_frame_filtered(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
+                                                        _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
+                                                        int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
+                                                        _p(o["droneIndex"]), _p(o["n_obj"]), _p(t), _p(o["fpos"]), _p(o["fvel"]),
+                                                        _p(o["fheading"]), _p(o["chosen"])))
+        return o
+
+    def track_frame_filtered_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
+                                 d_status, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj, d_t, d_fpos, d_fvel, d_fheading,
+                                 d_chosen):
+        self._check(self.lib.mocap_track_frame_filtered_dev(
+            self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), float(gate_px), int(K_max), int(G_cap), _vp(d_xyz),
+            _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos), _vp(d_heading), _vp(d_oerr), _vp(d_drone),
+            _vp(d_n_obj), _vp(d_t), _vp(d_fpos), _vp(d_fvel), _vp(d_fheading), _vp(d_chosen)))
 
     # ------------------------------------------------------------------ device-pointer entry points
     def match_triangulate_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err,

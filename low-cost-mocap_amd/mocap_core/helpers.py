@@ -355,6 +355,67 @@ def track_frame(image_points, camera_poses, is_locating_objects=True, O_max=8):
     return res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else [])
 
 
+def _filtered_list(res, f=0):
+    """One frame's `filtered_objects` as the reference builds it (KalmanFilter.py:93-98): drones in ascending index, absent ones left out."""
+    return [{"pos": res["fpos"][f, d].copy(), "vel": res["fvel"][f, d].copy(), "heading": float(res["fheading"][f, d]),
+             "droneIndex": int(d)}
+            for d in range(res["chosen"].shape[1]) if res["chosen"][f, d] >= 0]
+
+
+class KalmanFilter:
+    """The reference's KalmanFilter (computer_code/api/KalmanFilter.py) with its state on the device: same constructor, same
+    predict_location(objects) / reset() seam, so it drops into Cameras.kalman_filter (helpers.py:175).  The filter lives in the
+    core's context (one per context: constructing another one re-initialises it); `now` defaults to time.time() like the
+    reference, pass it for a reproducible run.  Constructor defaults as there: 5th-order Butterworth, 20 Hz cut-off at 60 Hz,
+    buffers of 300."""
+
+    def __init__(self, num_objects, cutoff_frequency=20, sampling_frequency=60.0, order=5, buffer_size=300):
+        from scipy.signal import butter
+        self.num_objects = int(num_objects)
+        b, a = butter(order, cutoff_frequency / (sampling_frequency / 2), btype="low")
+        with _state["lock"]:
+            get_core().set_object_filter(self.num_objects, b, a, buffer_size=buffer_size)
+
+    def predict_location(self, objects, now=None):
+        """objects: locate_objects' list for one frame -> [{"pos" float32[3], "vel" float32[3], "heading" float, "droneIndex" int}]."""
+        now = time.time() if now is None else float(now)
+        O = max(1, len(objects))
+        pos = np.zeros((1, O, 3))
+        heading = np.zeros((1, O))
+        drone = np.full((1, O), -1, dtype=np.int32)
+        for j, obj in enumerate(objects):
+            pos[0, j] = np.asarray(obj["pos"], dtype=np.float64).reshape(3)
+            heading[0, j] = float(obj["heading"])
+            drone[0, j] = int(obj["droneIndex"])
+        with _state["lock"]:
+            res = get_core().filter_objects([now], pos, heading, drone, [len(objects)])
+        return _filtered_list(res)
+
+    def reset(self, now=None):
+        with _state["lock"]:
+            get_core().reset_object_filter(time.time() if now is None else float(now))
+
+
+def track_frame_filtered(image_points, camera_poses, now=None, O_max=8):
+    """track_frame() plus helpers.py:109 in the same core call: returns (errors, object_points, objects, filtered_objects), the
+    four values object_points_payload() takes.  Needs a KalmanFilter(num_objects) to have been constructed (Cameras.
+    start_trangulating_points does, helpers.py:175); `now` defaults to time.time()."""
+    now = time.time() if now is None else float(now)
+    for image_points_i in image_points:
+        try:
+            image_points_i.remove([None, None])
+        except Exception:
+            pass
+    with _state["lock"]:
+        core = _upload_cameras(camera_poses)
+        blobs, counts, _ = pack_frame(image_points)
+        res = core.track_frame_filtered(blobs, counts, [now], gate_px=5.0, O_max=O_max)
+    if int(res["status"][0]) != 0:
+        raise capi.MocapError(_status_message(int(res["status"][0])))
+    k = int(res["n_pts"][0])
+    return res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), _objects_list(res), _filtered_list(res)
+
+
 def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=True, O_max=8):
     """Raw camera frames -> (image_points, errors, object_points, objects): Cameras._camera_read's preprocessing,
     _find_dot, the frame path, the world transform and locate_objects (helpers.py:68-108) in one core call; nothing but the
@@ -397,13 +458,15 @@ def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=Tr
 
 def object_points_payload(errors, object_points, objects, filtered_objects=()):
     """The dict the reference emits as the `object-points` socket event (helpers.py:128-133), built from what
-    track_frame() / camera_read_track() return.  `filtered_objects` is the caller's Kalman output
-    (helpers.py:109-126: already .tolist()-ed there), passed through."""
+    track_frame() / camera_read_track() / track_frame_filtered() return.  `filtered_objects` is KalmanFilter.predict_location's
+    list (or track_frame_filtered's fourth value); its "pos" and "vel" arrays are .tolist()-ed like helpers.py:124-126 does,
+    entries a caller has already converted pass through."""
+    as_json = lambda d: {k: (v.tolist() if isinstance(v, np.ndarray) else v) for (k, v) in d.items()}   # noqa: E731
     return {
         "object_points": np.asarray(object_points).tolist(),
         "errors": np.asarray(errors).tolist(),
-        "objects": [{k: (v.tolist() if isinstance(v, np.ndarray) else v) for (k, v) in obj.items()} for obj in objects],
-        "filtered_objects": list(filtered_objects),
+        "objects": [as_json(obj) for obj in objects],
+        "filtered_objects": [as_json(obj) for obj in filtered_objects],
     }
 
 
