@@ -373,6 +373,49 @@ int mocap_track_frame_filtered_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, 
                                    double* d_oerr, int32_t* d_drone, int32_t* d_n_obj, const double* d_t, float* d_fpos,
                                    float* d_fvel, double* d_fheading, int32_t* d_chosen);
 
+/* ---------------------------------------------------------------- calibration tail
+ * The three handlers a user runs after `calculate-camera-pose` and before flying, over a whole capture as the frame path
+ * leaves it on the device (the UI's objectPoints.current, App.tsx:458,475,492):
+ *   xyz [F][K_max][3], n_pts [F] (mocap_match_triangulate's n_out), status [F] (may be NULL)
+ * A frame contributes when status[f] == 0 (if status is given) and 0 <= n_pts[f] <= K_max -- the "no valid slot" rule of
+ * mocap_locate_objects; slots >= n_pts[f] are never read.  Results are bit-identical from run to run, between the host and
+ * the _dev form, and from machine to machine: the reductions have one fixed shape that depends on F alone.
+ *
+ * mocap_determine_scale: `determine-scale` (index.py:290-309).  Every frame with exactly two points yields
+ * d = sqrt(sum((p0 - p1)^2)), bit-exact against NumPy; result [4] = {scale_factor = actual_distance / mean(d), mean(d),
+ * pairs used, frames skipped as invalid}.  The caller multiplies every pose's t by scale_factor (index.py:306-307).  No pair at
+ * all: scale_factor and mean are NaN (np.mean of an empty list) and the call returns MOCAP_OK.
+ *   actual_distance   the reference hard-codes 0.15
+ *   pair_dist [F]     (may be NULL) d per frame, NaN where the frame yields no pair
+ *   d_result          device-accessible (device or pinned host memory), written by the last kernel */
+int mocap_determine_scale(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int32_t* n_pts,
+                          const int32_t* status, double actual_distance, double* pair_dist, double* result);
+int mocap_determine_scale_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts,
+                              const int32_t* d_status, double actual_distance, double* d_pair_dist, double* d_result);
+/* mocap_floor_factor: the reduction of `acquire-floor` (index.py:158-172).  factor [17] = the 4 x 4 upper-triangular R of the
+ * QR factorisation of the rows [x, y, 1 | z] of every valid point (row-major, zeros below the diagonal, diagonal >= 0),
+ * then the number of points.  Built by Givens rotations per lane and combined pairwise (TSQR): backward stable like the
+ * reference's scipy.linalg.lstsq, where a sum of normal equations would square the condition number of [x y 1] (captures taken
+ * before set-origin sit metres from the origin).  |R[3][3]| / sqrt(points) is the RMS residual of the plane. */
+int mocap_floor_factor(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int32_t* n_pts,
+                       const int32_t* status, double* factor);
+int mocap_floor_factor_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts,
+                           const int32_t* d_status, double* d_factor);
+/* mocap_floor_from_factor: the rest of `acquire-floor` (index.py:172-192) from the 17 doubles above.  Host-only arithmetic,
+ * ctx may be NULL (like mocap_ba_trust_region_step).  Back-substitutes the fit z = a x + b y + c, then restates the handler:
+ * normal (a, b, -1), up (0, 0, 1), G, F, R = F G F^-1, R diag(1, -1, 1); to_world [16] = [[R, 0], [0, 0, 0, 1]] row-major.
+ *   info [6] (may be NULL) = {a, b, c, points, RMS residual, tilt of the plane against z = const in rad}
+ * Deviations from the reference, both on inputs where its answer means nothing:
+ *   - fewer than 3 points, or a pivot |R_ii| <= points * eps * max |R_jj| (i, j < 3: collinear or coincident points):
+ *     MOCAP_E_ARG, nothing written.  The reference returns gelsd's minimum-norm fit of the rank-deficient system.
+ *   - a floor parallel to the xy-plane: `up - (up.n) n` has norm ~ 0 and the reference's F is noise divided by noise.  The
+ *     matrix is written as the arithmetic gives it (NaN when the norm is exactly 0) and the call returns MOCAP_E_NOCONV
+ *     ("result still written") when that norm is below 1e-8. */
+int mocap_floor_from_factor(mocap_ctx* ctx, const double* factor, double* to_world, double* info);
+/* mocap_world_set_origin: `set-origin` (index.py:200-207): y and z of `point` [3] swapped, to_world_out = T(-p) to_world_in.
+ * Host-only arithmetic, ctx may be NULL; in and out may be the same buffer. */
+int mocap_world_set_origin(mocap_ctx* ctx, const double* to_world_in, const double* point, double* to_world_out);
+
 /* ---------------------------------------------------------------- initial poses
  * The pose-chaining loop of the `calculate-camera-pose` handler (index.py:229-270), i.e. the caller of
  * bundle_adjustment: per neighbouring camera pair cv.findFundamentalMat(FM_RANSAC, threshold, confidence)

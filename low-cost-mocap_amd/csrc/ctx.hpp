@@ -134,6 +134,7 @@ struct mocap_ctx {
   DevBuf objf_state;        // ObjFilterState | h [B] | low-pass history [2][D][4][B] (a call reads one half and writes the other)
   DevBuf objf_ws;           // per call: samples [D][4][F] | slots [F][D][2] | samples appended [D]
   uint32_t objf_calls = 0;  // ... parity selects the half that holds the history
+  DevBuf calib_ws;          // calibration tail: one partial per workgroup (pair sums | floor factors), csrc/calib_tail.hip
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);

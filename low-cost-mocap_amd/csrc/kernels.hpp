@@ -213,6 +213,24 @@ struct ObjFilterArgs {
 hipError_t launch_object_filter(const ObjFilterArgs& a, hipStream_t stream);  // scan kernel, then low-pass kernel
 hipError_t launch_object_filter_reset(ObjFilterState* state, int D, double now, hipStream_t stream);
 
+// calibration tail over a capture's frame-path outputs (reference index.py:158-194, :290-309), csrc/calib_tail.hip
+constexpr int kCalibThreads = 256;      // frames per workgroup: the grid is ceil(F / 256), a function of F alone
+constexpr int kPairSlabDoubles = 3;     // per workgroup: sum of pair distances, pairs, frames skipped
+constexpr int kFloorSlabDoubles = 11;   // per workgroup: upper triangle of the 4 x 4 factor (row-major), points
+inline int64_t calib_partials(int64_t n_frames) { return (n_frames + kCalibThreads - 1) / kCalibThreads; }
+struct CalibTailArgs {
+  int64_t n_frames;
+  int K_max;
+  const double* xyz;      // [F][K_max][3]
+  const int32_t* n_pts;   // [F]
+  const int32_t* status;  // [F] or null
+  double* pair_dist;      // pair scale only: [F] or null
+  double* slab;           // [calib_partials(F)][kPairSlabDoubles | kFloorSlabDoubles]
+};
+// result [4] = {scale factor, mean pair distance, pairs, frames skipped}; factor [17] = R row-major, points (device-accessible)
+hipError_t launch_pair_scale(const CalibTailArgs& a, double actual_distance, double* result, hipStream_t stream);
+hipError_t launch_floor_factor(const CalibTailArgs& a, double* factor, hipStream_t stream);
+
 // compaction of a frame batch's valid points into fixed-stride records (the payload of the multi-GPU exchange)
 struct CompactArgs {
   int64_t n_frames;

@@ -71,6 +71,12 @@ SIGNATURES = {
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_track_frame_filtered_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_determine_scale": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _dbl, _vp, _vp]),
+    "mocap_determine_scale_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _dbl, _vp, _vp]),
+    "mocap_floor_factor": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "mocap_floor_factor_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "mocap_floor_from_factor": (_i32, [_vp, _vp, _vp, _vp]),
+    "mocap_world_set_origin": (_i32, [_vp, _vp, _vp, _vp]),
     "mocap_set_image_params": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mocap_set_blob_options": (_i32, [_vp, _i32]),
     "mocap_get_undistort_map": (_i32, [_vp, _i32, _vp]),
@@ -121,6 +127,33 @@ def load_library(path=None):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def floor_from_factor(factor, ctx=None, lib=None):
+    """mocap_floor_from_factor (host-only arithmetic, no GPU): factor [17] -> (to_world 4x4, info dict, rc).  rc is MOCAP_OK or
+    MOCAP_E_NOCONV (floor parallel to the xy-plane: the matrix is written as the arithmetic gives it); MOCAP_E_ARG raises."""
+    lib = lib or load_library()
+    factor = np.ascontiguousarray(factor, dtype=np.float64).reshape(17)
+    W = np.zeros((4, 4))
+    info = np.zeros(6)
+    rc = lib.mocap_floor_from_factor(ctx, _p(factor), _p(W), _p(info))
+    if rc not in (MOCAP_OK, MOCAP_E_NOCONV):
+        e = MocapError(f"mocap_floor_from_factor: error {rc} (fewer than 3 points, or points that do not span a plane over x, y)")
+        e.code = rc
+        raise e
+    return W, dict(zip(("a", "b", "c", "points", "rms_residual", "tilt"), info.tolist())), rc
+
+
+def world_set_origin(to_world, point, ctx=None, lib=None):
+    """mocap_world_set_origin (host-only arithmetic, no GPU): `set-origin`, index.py:200-207."""
+    lib = lib or load_library()
+    W = np.ascontiguousarray(to_world, dtype=np.float64).reshape(16)
+    p = np.ascontiguousarray(point, dtype=np.float64).reshape(3)
+    out = np.zeros((4, 4))
+    rc = lib.mocap_world_set_origin(ctx, _p(W), _p(p), _p(out))
+    if rc != MOCAP_OK:
+        raise MocapError(f"mocap_world_set_origin: error {rc}")
+    return out
 
 
 class MocapCore:
@@ -419,6 +452,53 @@ class MocapCore:
                                                   _p(out["pos"]), _p(out["heading"]), _p(out["error"]),
                                                   _p(out["droneIndex"]), _p(out["lead"]), _p(out["n_obj"])))
         return out
+
+    # ------------------------------------------------------------------ calibration tail (scale, floor plane, origin)
+    @staticmethod
+    def _capture(xyz, n_pts, status):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        F, K_max, _ = xyz.shape
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(F)
+        return xyz, n_pts, status, F, K_max
+
+    def determine_scale(self, xyz, n_pts, status=None, actual_distance=0.15, want_pair_dist=False):
+        """mocap_determine_scale over host arrays xyz [F][K_max][3], n_pts [F], status [F] or None ->
+        {"scale_factor", "mean_distance", "pairs", "skipped"[, "pair_dist" [F]]}."""
+        xyz, n_pts, status, F, K_max = self._capture(xyz, n_pts, status)
+        res = np.zeros(4)
+        pd = np.full(F, np.nan) if want_pair_dist else None
+        self._check(self.lib.mocap_determine_scale(self._h, F, K_max, _p(xyz), _p(n_pts), _p(status), float(actual_distance),
+                                                   _p(pd), _p(res)))
+        out = {"scale_factor": float(res[0]), "mean_distance": float(res[1]), "pairs": int(res[2]), "skipped": int(res[3])}
+        if want_pair_dist:
+            out["pair_dist"] = pd
+        return out
+
+    def determine_scale_dev(self, n_frames, K_max, d_xyz, d_n_pts, d_status, actual_distance, d_pair_dist, d_result):
+        """Device pointers (ints; d_status, d_pair_dist may be 0); d_result: device-accessible double[4]."""
+        self._check(self.lib.mocap_determine_scale_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_n_pts),
+                                                       _vp(d_status or 0), float(actual_distance), _vp(d_pair_dist or 0),
+                                                       _vp(d_result)))
+
+    def floor_factor(self, xyz, n_pts, status=None):
+        """mocap_floor_factor over host arrays -> factor [17] (R of [x y 1 | z] row-major, then the point count)."""
+        xyz, n_pts, status, F, K_max = self._capture(xyz, n_pts, status)
+        factor = np.zeros(17)
+        self._check(self.lib.mocap_floor_factor(self._h, F, K_max, _p(xyz), _p(n_pts), _p(status), _p(factor)))
+        return factor
+
+    def floor_factor_dev(self, n_frames, K_max, d_xyz, d_n_pts, d_status, d_factor):
+        """Device pointers (ints; d_status may be 0); d_factor: device-accessible double[17]."""
+        self._check(self.lib.mocap_floor_factor_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_n_pts),
+                                                    _vp(d_status or 0), _vp(d_factor)))
+
+    def floor_from_factor(self, factor):
+        """-> (to_world 4x4, info dict, rc); see the module-level floor_from_factor."""
+        return floor_from_factor(factor, ctx=self._h, lib=self.lib)
+
+    def world_set_origin(self, to_world, point):
+        return world_set_origin(to_world, point, ctx=self._h, lib=self.lib)
 
     # ------------------------------------------------------------------ object filter (`filtered_objects`)
     def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):

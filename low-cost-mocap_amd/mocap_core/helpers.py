@@ -504,6 +504,99 @@ def calculate_camera_pose(data, socketio):
     return camera_poses, error
 
 
+# ----------------------------------------------------------------------------- calibration tail (scale, floor, origin)
+def _pack_object_points(object_points):
+    """The UI's ragged objectPoints (per frame a list of [x, y, z]) -> (xyz [F][K_max][3] NaN-padded, n_pts [F])."""
+    F = len(object_points)
+    K_max = max([1] + [len(frame) for frame in object_points])
+    xyz = np.full((F, K_max, 3), np.nan)
+    n_pts = np.zeros(F, dtype=np.int32)
+    for f, frame in enumerate(object_points):
+        if len(frame):
+            xyz[f, :len(frame)] = np.asarray(frame, dtype=np.float64).reshape(-1, 3)
+        n_pts[f] = len(frame)
+    return xyz, n_pts
+
+
+def _capture_call(object_points, host_fn, dev_fn, n_result):
+    """Runs one of the calibration-tail reductions over a capture and returns its `n_result` doubles (host_fn and dev_fn both
+    produce exactly that many).  object_points: the UI's
+    ragged list, or a dict {"xyz" [F][K_max][3], "n_out" | "n_pts" [F], "status" [F] (optional)} as
+    find_point_correspondance_and_object_points_batch returns it (NumPy arrays), or the same dict of torch tensors on the GPU
+    (the buffers track_frame_dev wrote): those are read in place, only the result crosses PCIe."""
+    if not isinstance(object_points, dict):
+        xyz, n_pts = _pack_object_points(object_points)
+        return host_fn(xyz, n_pts, None)
+    xyz = object_points["xyz"]
+    n_pts = object_points["n_pts"] if "n_pts" in object_points else object_points["n_out"]
+    status = object_points.get("status")
+    if not getattr(xyz, "is_cuda", False):
+        return host_fn(np.asarray(xyz), np.asarray(n_pts), None if status is None else np.asarray(status))
+    import torch
+    assert xyz.dtype == torch.float64 and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3
+    assert n_pts.dtype == torch.int32 and n_pts.is_contiguous() and n_pts.is_cuda and n_pts.numel() == xyz.shape[0]
+    assert status is None or (status.dtype == torch.int32 and status.is_contiguous() and status.is_cuda and status.numel() == xyz.shape[0])
+    core = get_core()
+    if xyz.device.index != core.device_id or n_pts.device != xyz.device or (status is not None and status.device != xyz.device):
+        raise ValueError(f"the capture lives on {xyz.device}, the core on GPU {core.device_id}: a resident capture is read in place")
+    torch.cuda.current_stream(xyz.device).synchronize()      # whatever torch itself still has queued on these buffers
+    result = torch.empty(n_result, dtype=torch.float64, device=xyz.device)
+    dev_fn(core, xyz.shape[0], xyz.shape[1], xyz.data_ptr(), n_pts.data_ptr(), 0 if status is None else status.data_ptr(),
+           result.data_ptr())
+    core.synchronize()
+    return result.cpu().numpy()
+
+
+def _scale_result(res):
+    """MocapCore.determine_scale's dict -> the 4 doubles of mocap_determine_scale's `result`."""
+    return np.array([res["scale_factor"], res["mean_distance"], res["pairs"], res["skipped"]], dtype=np.float64)
+
+
+def determine_scale(data, socketio, actual_distance=0.15):
+    """index.py:290-309, the `determine-scale` handler: data = {"objectPoints", "cameraPoses"}; emits `camera-pose` with
+    {"error": None, "camera_poses": ...}, every t multiplied by actual_distance / mean(pair distance).  Returns
+    (camera_poses, scale_factor).  No two-point frame at all: the factor is NaN, as in the reference."""
+    camera_poses = data["cameraPoses"]
+    with _state["lock"]:
+        res = _capture_call(
+            data["objectPoints"],
+            lambda xyz, n, st: _scale_result(get_core().determine_scale(xyz, n, st, actual_distance)),
+            lambda core, F, K, d_xyz, d_n, d_st, d_res: core.determine_scale_dev(F, K, d_xyz, d_n, d_st, actual_distance, 0, d_res), 4)
+    scale_factor = float(res[0])
+    for i in range(0, len(camera_poses)):
+        camera_poses[i]["t"] = (np.array(camera_poses[i]["t"]) * scale_factor).tolist()     # index.py:307
+    if socketio is not None:
+        socketio.emit("camera-pose", {"error": None, "camera_poses": camera_poses})
+    return camera_poses, scale_factor
+
+
+def acquire_floor(data, socketio):
+    """index.py:158-194, the `acquire-floor` handler: data = {"objectPoints"}; the plane through every captured point, the
+    rotation that lays it flat -> set_to_world_coords_matrix + the `to-world-coords-matrix` event.  Returns (matrix, info) with
+    info = {"a", "b", "c", "points", "rms_residual", "tilt", "degenerate"}; "degenerate" is True when the floor is parallel to
+    the xy-plane (the reference's rotation is then noise-determined; the matrix is emitted as the arithmetic gives it).  Fewer
+    than 3 points or collinear points raise MocapError (include/mocap_core.h, mocap_floor_from_factor)."""
+    with _state["lock"]:
+        factor = _capture_call(data["objectPoints"], lambda xyz, n, st: get_core().floor_factor(xyz, n, st),
+                               lambda core, F, K, d_xyz, d_n, d_st, d_res: core.floor_factor_dev(F, K, d_xyz, d_n, d_st, d_res), 17)
+        to_world, info, rc = get_core().floor_from_factor(factor)
+    info["degenerate"] = rc != capi.MOCAP_OK
+    set_to_world_coords_matrix(to_world)
+    if socketio is not None:
+        socketio.emit("to-world-coords-matrix", {"to_world_coords_matrix": to_world.tolist()})
+    return to_world, info
+
+
+def set_origin(data, socketio):
+    """index.py:197-210, the `set-origin` handler: data = {"objectPoint", "toWorldCoordsMatrix"}; the matrix translated by the
+    point (y and z swapped) -> set_to_world_coords_matrix + the `to-world-coords-matrix` event.  Returns the matrix."""
+    to_world = capi.world_set_origin(data["toWorldCoordsMatrix"], data["objectPoint"])
+    set_to_world_coords_matrix(to_world)
+    if socketio is not None:
+        socketio.emit("to-world-coords-matrix", {"to_world_coords_matrix": to_world.tolist()})
+    return to_world
+
+
 # ----------------------------------------------------------------------------- bundle adjustment
 def _ba_x0(camera_poses):
     """helpers.py:278-285 (including its focal-length indexing: entry i+1 takes camera i's focal)."""
