@@ -181,7 +181,8 @@ def compute_error(m1, m2, F):
     s1 = 1.0 / (a * a + b * b)
     d1 = x1 * a + y1 * b + c
     with np.errstate(invalid="ignore", over="ignore"):
-        return np.maximum(d1 * d1 * s1, d2 * d2 * s2).astype(np.float32)
+        e1, e2 = d1 * d1 * s1, d2 * d2 * s2
+        return np.where(e1 < e2, e2, e1).astype(np.float32)      # std::max(e1, e2): e1 unless e1 < e2, so a NaN e1 stays
 
 
 def ransac_update_num_iters(p, ep, model_points, max_iters):
