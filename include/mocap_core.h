@@ -273,6 +273,44 @@ int mocap_find_blobs(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, in
 int mocap_find_blobs_dev(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_images, int M_max, float* d_blobs,
                          int32_t* d_counts, int32_t* d_status, uint8_t* d_processed);
 
+/* ---------------------------------------------------------------- preview stream
+ * The MJPEG preview of the reference (index.py:55-56): frames = cameras.get_frames() (helpers.py:137-141, np.hstack of the
+ * processed frames), cv.imencode('.jpg', frames).  The encoder writes the file libjpeg writes with its defaults, byte for
+ * byte: baseline sequential, quality as given, YCbCr 4:2:0, JDCT_ISLOW, the standard Huffman tables, no restart markers,
+ * JFIF 1.01 APP0 with density 1:1 (SOI, APP0, DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, SOS, scan, EOI).
+ *   bgr      [n_images][T][H][W][3] uint8 BGR: the blob stage's `processed` layout for T tiles.  Image f is the H x T*W
+ *            picture whose columns t*W .. (t+1)*W-1 are tile t; the hstack is never materialised.  4-byte aligned.
+ *   T >= 1; H and W multiples of 16; T*W and H <= 65520; the stream's own shape is 320 x 320*C.  Anything else: MOCAP_E_ARG.
+ *   quality  1 .. 100, else MOCAP_E_ARG (libjpeg clamps; this encoder refuses)
+ *   jpeg     [n_images][capacity]: every image is an independent file at the start of its slot
+ *   sizes    [n_images] bytes the image needs.  An image that needs more than `capacity` writes nothing at or beyond the end of
+ *            its slot (the bytes in front are the file's first `capacity` bytes), sets MOCAP_JPEG_ST_OVERFLOW and still
+ *            reports the size it needed
+ *   status   [n_images] MOCAP_JPEG_ST_* bits (0 = the slot holds the whole file)
+ * The output is bit-reproducible from run to run.  The "_dev" form enqueues on the context's stream without any host
+ * synchronisation; its workspace lives in the context and grows on demand.
+ *
+ * mocap_jpeg_bound: an upper bound on one image's bytes, -1 for a size the encoder does not take.  A coded block takes at
+ * most 22 bits of DC (an 11-bit code at most, 11 value bits) and 63 x 26 bits of AC (a 16-bit code at most, 10 value bits; zero
+ * runs only shorten this): 1660 bits.  With B = 6 * (H / 16) * (W_total / 16) blocks the scan has at most ceil(1660 B / 8) bytes,
+ * every one of which may be 0xFF and then carries a stuffed 0x00:  623 (header) + 2 * ceil(1660 B / 8) + 2 (EOI). */
+enum {
+  MOCAP_JPEG_ST_OVERFLOW = 1 /* the image needs more than `capacity` bytes: sizes[f] says how many */
+};
+int64_t mocap_jpeg_bound(int H, int W_total);
+int mocap_encode_jpeg_dev(mocap_ctx* ctx, int64_t n_images, int T, int H, int W, const uint8_t* d_bgr, int quality,
+                          uint8_t* d_jpeg, int64_t capacity, int64_t* d_sizes, int32_t* d_status);
+int mocap_encode_jpeg(mocap_ctx* ctx, int64_t n_images, int T, int H, int W, const uint8_t* bgr, int quality, uint8_t* jpeg,
+                      int64_t capacity, int64_t* sizes, int32_t* status);
+/* mocap_find_blobs with the preview stream instead of `processed`: per frame set one JPEG of its C processed frames side by
+ * side (S x S*C, S = cols), encoded where the blob stage left them -- the processed frames never leave the device.
+ *   quality, jpeg [F][capacity], capacity   as mocap_encode_jpeg
+ *   jpeg_size [F]   bytes the frame set's file needs; > capacity = the slot holds only its first `capacity` bytes
+ * everything else as mocap_find_blobs. */
+int mocap_find_blobs_jpeg(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, int M_max, float* blobs, int32_t* counts,
+                          int32_t* status, int32_t* n_contours, int quality, uint8_t* jpeg, int64_t capacity,
+                          int64_t* jpeg_size);
+
 /* ---------------------------------------------------------------- after the path
  * World-coordinate epilogue of the frame loop (helpers.py:96-103), fused into the frame path's store:
  * with a matrix set, `xyz` of mocap_match_triangulate* leaves the kernel as
@@ -321,6 +359,14 @@ int mocap_track_frame_images(mocap_ctx* ctx, int64_t n_frames, const uint8_t* im
                              int K_max, int64_t G_cap, float* blobs, int32_t* counts, int32_t* blob_status,
                              double* xyz, double* err, int16_t* corr, int32_t* n_pts, int32_t* status, int O_max,
                              double* pos, double* heading, double* oerr, int32_t* drone, int32_t* n_obj);
+/* mocap_track_frame_images with the preview stream (quality, jpeg, capacity, jpeg_size as mocap_find_blobs_jpeg): the
+ * encoder is queued behind the export, its bytes land in the same pinned block as the rest of the payload: still one enqueue
+ * and one event wait, and what crosses PCIe is the file, not the frames. */
+int mocap_track_frame_images_jpeg(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, int M_max, double gate_px,
+                                  int K_max, int64_t G_cap, float* blobs, int32_t* counts, int32_t* blob_status,
+                                  double* xyz, double* err, int16_t* corr, int32_t* n_pts, int32_t* status, int O_max,
+                                  double* pos, double* heading, double* oerr, int32_t* drone, int32_t* n_obj, int quality,
+                                  uint8_t* jpeg, int64_t capacity, int64_t* jpeg_size);
 /* device-pointer form for batches: frame kernel, device-side re-submission of the frames that hit a cap (as
  * mocap_match_triangulate_dev_auto) and object search, all enqueued on the context's stream. */
 int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs, const int32_t* d_counts,

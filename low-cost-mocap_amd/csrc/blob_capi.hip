@@ -160,10 +160,10 @@ int find_blobs_dev_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_ima
 
 }  // namespace
 
-// internal (ctx.hpp): the blob stage enqueued on device pointers, context lock held by the caller (mocap_track_frame_images)
+// internal (ctx.hpp): the blob stage enqueued on device pointers, context lock held by the caller (mocap_track_frame_images*, mocap_find_blobs_jpeg)
 int mocap_blob_stage_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_images, int M_max, float* d_blobs,
-                            int32_t* d_counts, int32_t* d_status) {
-  return find_blobs_dev_locked(ctx, n_frames, d_images, M_max, d_blobs, d_counts, d_status, nullptr, nullptr);
+                            int32_t* d_counts, int32_t* d_status, uint8_t* d_processed, int32_t* d_n_contours) {
+  return find_blobs_dev_locked(ctx, n_frames, d_images, M_max, d_blobs, d_counts, d_status, d_processed, d_n_contours);
 }
 
 extern "C" int mocap_set_image_params(mocap_ctx* ctx, int C, int rows, int cols, const double* K, const double* dist,

@@ -135,6 +135,11 @@ struct mocap_ctx {
   DevBuf objf_ws;           // per call: samples [D][4][F] | slots [F][D][2] | samples appended [D]
   uint32_t objf_calls = 0;  // ... parity selects the half that holds the history
   DevBuf calib_ws;          // calibration tail: one partial per workgroup (pair sums | floor factors), csrc/calib_tail.hip
+  // preview-stream JPEG encoder (csrc/jpeg_capi.hip): header and divisors of the last (H, T * W, quality), workspace of a chunk
+  int jpeg_key[3] = {0, 0, 0};
+  mocap::JpegParams jpeg_params{};
+  DevBuf jpeg_ws;           // per image of a chunk: coefficients | AC bits | bit offsets | total bits | unstuffed scan
+  DevBuf jpeg_stage;        // host-buffer entry points: frames in, [F][capacity] streams, sizes and status out
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);
@@ -147,7 +152,17 @@ int spin_wait(mocap_ctx* ctx, Event& event);
 
 // internal entry points shared between the translation units of the C ABI (context lock held by the caller)
 int mocap_blob_stage_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_images, int M_max, float* d_blobs,
-                            int32_t* d_counts, int32_t* d_status);
+                            int32_t* d_counts, int32_t* d_status, uint8_t* d_processed = nullptr, int32_t* d_n_contours = nullptr);
+// JPEG encoder on device pointers (jpeg_capi.hip): arguments checked, kernels enqueued on the context's stream
+int jpeg_dev_locked(mocap_ctx* ctx, const char* who, int64_t n_images, int T, int H, int W, const uint8_t* d_bgr, int quality,
+                    uint8_t* d_jpeg, int64_t capacity, int64_t* d_sizes, int32_t* d_status, int64_t out_stride = 0);
+// the preview stream of the chained live call (mocap_track_frame_images_jpeg)
+struct JpegOut {
+  int quality;
+  uint8_t* jpeg;      // [F][capacity]
+  int64_t capacity;
+  int64_t* size;      // [F]
+};
 int locate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const double* d_err,
                       const int32_t* d_n_pts, int O_max, double* d_pos, double* d_heading, double* d_oerr,
                       int32_t* d_drone, int32_t* d_lead, int32_t* d_n_obj);

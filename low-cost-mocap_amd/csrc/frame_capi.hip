@@ -11,6 +11,7 @@
 
 #include "../../include/mocap_core.h"
 #include "ctx.hpp"
+#include "jpeg_tables.hpp"
 
 using namespace mocap;
 
@@ -735,7 +736,7 @@ struct TrackOut {
 // fo != null (mocap_track_frame_filtered): host time stamps in, the object filter's outputs out -- its two kernels are queued
 // behind the export and write into the same pinned block, the call still waits for one event
 int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o,
-                 const FilterIO* fo = nullptr) {
+                 const FilterIO* fo = nullptr, const JpegOut* jo = nullptr) {
   const int64_t n_frames = b.n_frames;
   const int M_max = b.M_max;
   if (!ctx->C) return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_cameras has not been called");
@@ -754,10 +755,18 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     const int rc = filter_check(ctx, "mocap_track_frame_filtered", n_frames, o.O_max, *fo);
     if (rc) return rc;
   }
+  if (jo) {  // the preview stream: the processed frames of the blob stage as one JPEG per frame set
+    const char* bad = jpeg::check_args(n_frames, ctx->img_C, ctx->img_S, ctx->img_S, jo->quality, jo->capacity);
+    if (bad) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images_jpeg: %s", bad);
+    if (!jo->jpeg || !jo->size) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images_jpeg: null stream buffer");
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int C = ctx->C, O = o.O_max > 0 ? o.O_max : 1;
   const size_t F = (size_t)n_frames, FD = fo ? F * ctx->objf_D : 0;
   const size_t n_raw = images ? F * C * (size_t)ctx->img_rows * ctx->img_cols * 3 : 0;
+  const size_t j_stride = jo ? ((size_t)jo->capacity + 15) / 16 * 16 : 0;  // slots the export kernel copies 16 bytes at a time
+  uint8_t* h_jpeg = nullptr;
+  int64_t* h_jsize = nullptr;
   // caller-visible side (pinned host memory): inputs | frame outputs | objects
   float* h_blobs;
   int32_t *h_counts, *h_bstat, *h_drone, *h_nobj;
@@ -787,6 +796,10 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
       hf.fheading = c.take<double>(FD);
       hf.chosen = c.take<int32_t>(FD);
     }
+    if (jo) {
+      h_jpeg = c.take<uint8_t>(F * j_stride);
+      h_jsize = c.take<int64_t>(F);
+    }
     return c.off;
   };
   const size_t host_total = lay_host(nullptr);
@@ -796,7 +809,9 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   // device side: [raw images | blobs | counts | blob status |] frame outputs
   uint8_t* d_raw = nullptr;
   float* d_blobs = nullptr;
-  int32_t *d_counts = nullptr, *d_bstat = nullptr;
+  int32_t *d_counts = nullptr, *d_bstat = nullptr, *d_jstat = nullptr;
+  uint8_t *d_proc = nullptr, *d_jpeg = nullptr;
+  int64_t* d_jsize = nullptr;
   FrameOut d;
   auto lay_dev = [&](void* base) {
     Carver c(base);
@@ -812,6 +827,12 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     d.n_out = c.take<int32_t>(F);
     d.status = c.take<int32_t>(F);
     d.n_cand = c.take<int32_t>(F);
+    if (jo) {
+      d_proc = c.take<uint8_t>(F * C * (size_t)ctx->img_S * ctx->img_S * 3);
+      d_jpeg = c.take<uint8_t>(F * j_stride);
+      d_jsize = c.take<int64_t>(F);
+      d_jstat = c.take<int32_t>(F);
+    }
     return c.off;
   };
   const size_t dev_total = lay_dev(nullptr);
@@ -821,7 +842,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
 
   if (images) {
     HIP_TRY(ctx, hipMemcpyAsync(d_raw, images, n_raw, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = mocap_blob_stage_locked(ctx, n_frames, d_raw, M_max, d_blobs, d_counts, d_bstat);
+    const int rc = mocap_blob_stage_locked(ctx, n_frames, d_raw, M_max, d_blobs, d_counts, d_bstat, d_proc);
     if (rc) return rc;
   } else {
     memcpy(h_blobs, b.blobs, sizeof(float) * F * C * M_max * 2);
@@ -895,6 +916,12 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
       rc = filter_dev_locked(ctx, n_frames, O, h_pos, h_head, h_drone, h_nobj, hf);
       if (rc) return rc;
     }
+    if (jo) {  // encoded in device memory, then the bytes that exist travel into the pinned block 16 at a time
+      rc = jpeg_dev_locked(ctx, "mocap_track_frame_images_jpeg", n_frames, C, ctx->img_S, ctx->img_S, d_proc, jo->quality, d_jpeg,
+                           jo->capacity, d_jsize, d_jstat, (int64_t)j_stride);
+      if (rc) return rc;
+      HIP_TRY(ctx, launch_jpeg_export(n_frames, d_jpeg, (int64_t)j_stride, d_jsize, jo->capacity, h_jpeg, (int64_t)j_stride, h_jsize, ctx->stream));
+    }
     rc = spin_wait(ctx, ctx->live_event);
     if (rc) return rc;
   }
@@ -912,6 +939,10 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     memcpy(fo->fvel, hf.fvel, sizeof(float) * FD * 3);
     memcpy(fo->fheading, hf.fheading, sizeof(double) * FD);
     memcpy(fo->chosen, hf.chosen, sizeof(int32_t) * FD);
+  }
+  for (size_t f = 0; f < F && jo; f++) {
+    jo->size[f] = h_jsize[f];
+    memcpy(jo->jpeg + f * (size_t)jo->capacity, h_jpeg + f * j_stride, (size_t)(h_jsize[f] < jo->capacity ? h_jsize[f] : jo->capacity));
   }
   if (images) {
     memcpy(o.counts, h_counts, sizeof(int32_t) * F * C);
@@ -945,6 +976,19 @@ extern "C" int mocap_track_frame_images(mocap_ctx* ctx, int64_t n_frames, const 
   if (!images) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images: null image buffer");
   const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, blobs, counts, blob_status};
   return track_locked(ctx, images, FrameBatch{n_frames, M_max, nullptr, nullptr, gate_px}, K_max, G_cap, o);
+}
+
+extern "C" int mocap_track_frame_images_jpeg(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, int M_max, double gate_px,
+                                             int K_max, int64_t G_cap, float* blobs, int32_t* counts, int32_t* blob_status,
+                                             double* xyz, double* err, int16_t* corr, int32_t* n_pts, int32_t* status, int O_max,
+                                             double* pos, double* heading, double* oerr, int32_t* drone, int32_t* n_obj,
+                                             int quality, uint8_t* jpeg, int64_t capacity, int64_t* jpeg_size) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!images) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images_jpeg: null image buffer");
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, blobs, counts, blob_status};
+  const JpegOut jo{quality, jpeg, capacity, jpeg_size};
+  return track_locked(ctx, images, FrameBatch{n_frames, M_max, nullptr, nullptr, gate_px}, K_max, G_cap, o, nullptr, &jo);
 }
 
 extern "C" int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,

@@ -231,6 +231,34 @@ struct CalibTailArgs {
 hipError_t launch_pair_scale(const CalibTailArgs& a, double actual_distance, double* result, hipStream_t stream);
 hipError_t launch_floor_factor(const CalibTailArgs& a, double* factor, hipStream_t stream);
 
+// baseline JPEG encoder for the preview stream (reference index.py:55-56: np.hstack of the processed frames, cv.imencode),
+// csrc/jpeg_kernels.hip.  Tile t of image f is columns t*W .. (t+1)*W-1 of one H x T*W picture; the hstack is never built.
+struct JpegParams {          // passed by value: depends on (H, T*W, quality) only, built on the host (csrc/jpeg_tables.hpp)
+  uint8_t header[624];       // the 623 bytes in front of the scan
+  uint16_t quant[2][64];     // divisors, natural order: [0] luminance, [1] chrominance
+};
+struct JpegArgs {
+  int64_t n_images;
+  int T, H, W;               // tiles per image, tile size (multiples of 16)
+  int mcu_x, mcu_y;          // 16 x 16 MCUs per image row / column: T*W/16, H/16
+  const uint8_t* bgr;        // [F][T][H][W][3], 4-byte aligned
+  int16_t* coef;             // [F][blocks][64] quantised coefficients, zigzag order, blocks in scan order (6 per MCU)
+  int32_t* acbits;           // [F][blocks] coded bits of a block's AC part
+  uint32_t* bitoff;          // [F][blocks] first bit of the block in the image's scan
+  uint32_t* total_bits;      // [F]
+  uint32_t* scan;            // [F][scan_words] unstuffed scan, MSB-first inside big-endian 32-bit words
+  int64_t scan_words;        // per image, a multiple of 4
+  uint8_t* out;              // [F][out_stride]; bytes at or beyond `capacity` of a slot are never written
+  int64_t capacity, out_stride;
+  int64_t* sizes;            // [F] bytes the image needs
+  int32_t* status;           // [F] MOCAP_JPEG_ST_* bits
+};
+hipError_t launch_jpeg_encode(const JpegArgs& a, const JpegParams& p, hipStream_t stream);  // transform, size, emit, stuff
+// copies every image's min(size, capacity) bytes from [F][src_stride] to [F][dst_stride] (strides multiples of 16, e.g. device
+// memory to pinned host memory) and the sizes with them
+hipError_t launch_jpeg_export(int64_t n_images, const uint8_t* src, int64_t src_stride, const int64_t* sizes, int64_t capacity,
+                              uint8_t* dst, int64_t dst_stride, int64_t* dst_sizes, hipStream_t stream);
+
 // compaction of a frame batch's valid points into fixed-stride records (the payload of the multi-GPU exchange)
 struct CompactArgs {
   int64_t n_frames;

@@ -30,6 +30,7 @@ ST_LOG2_GROUPS_SHIFT, ST_LOG2_GROUPS_MASK = 20, 0x1FF
 ST_ROUNDED = 8          # informational (mocap_match_triangulate_f64): a coordinate was rounded to float32
 BLOB_ST_POINT_OVERFLOW = 1
 BLOB_ST_CAP_OVERFLOW = 2
+JPEG_ST_OVERFLOW = 1      # mocap_encode_jpeg*: the image needs more than `capacity` bytes
 OPT_F32_ROUNDING = 1
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
@@ -82,6 +83,12 @@ SIGNATURES = {
     "mocap_get_undistort_map": (_i32, [_vp, _i32, _vp]),
     "mocap_find_blobs": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mocap_find_blobs_dev": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "mocap_jpeg_bound": (_i64, [_i32, _i32]),
+    "mocap_encode_jpeg": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "mocap_encode_jpeg_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "mocap_find_blobs_jpeg": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "mocap_track_frame_images_jpeg": (_i32, [_vp, _i64, _vp, _i32, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
+                                             _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "mocap_set_world_transform": (_i32, [_vp, _vp]),
     "mocap_locate_objects": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_locate_objects_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -381,6 +388,36 @@ class MocapCore:
                 continue
             return o
 
+    def track_frame_images_jpeg(self, images, M_max=16, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8, quality=95, capacity=None):
+        """mocap_track_frame_images_jpeg: track_frame_images plus the preview stream: "jpeg" = one bytes object per frame set
+        (its C processed frames side by side, the file cv.imencode('.jpg') writes), "jpeg_size" the bytes each needed."""
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        F, C = images.shape[:2]
+        assert images.shape == (F, C, self.img_rows, self.img_cols, 3) and C == self.img_C == self.C
+        K_max = min(C * M_max, 64) if K_max is None else int(K_max)
+        S = self.img_cols
+        cap = self.jpeg_default_capacity(S, S * C) if capacity is None else int(capacity)
+        while True:
+            o = self._track_outputs(F, K_max, O_max)
+            o.update(blobs=np.zeros((F, C, M_max, 2), dtype=np.float32), counts=np.zeros((F, C), dtype=np.int32),
+                     blob_status=np.zeros((F, C), dtype=np.int32))
+            buf, size = np.zeros((F, cap), dtype=np.uint8), np.zeros(F, dtype=np.int64)
+            self._check(self.lib.mocap_track_frame_images_jpeg(
+                self._h, F, _p(images), int(M_max), float(gate_px), K_max, int(G_cap), _p(o["blobs"]), _p(o["counts"]),
+                _p(o["blob_status"]), _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]), int(O_max),
+                _p(o["pos"]), _p(o["heading"]), _p(o["error"]), _p(o["droneIndex"]), _p(o["n_obj"]), int(quality), _p(buf), cap,
+                _p(size)))
+            need = (o["status"] & ST_ROOT_OVERFLOW).astype(bool) & (o["n_pts"] > K_max)
+            if need.any() and K_max < min(C * M_max, 256 if O_max else 1024):
+                K_max = min(int(o["n_pts"][need].max()), 256 if O_max else 1024)
+                continue
+            if capacity is None and (size > cap).any():   # a frame set that does not compress: once more with room for it
+                cap = int(size.max())
+                continue
+            o["jpeg"] = [buf[f, :min(int(size[f]), cap)].tobytes() for f in range(F)]
+            o["jpeg_size"] = size
+            return o
+
     def track_frame_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts, d_status,
                         O_max=0, d_pos=0, d_heading=0, d_oerr=0, d_drone=0, d_n_obj=0):
         self._check(self.lib.mocap_track_frame_dev(
@@ -429,6 +466,57 @@ class MocapCore:
     def find_blobs_dev(self, n_frames, d_images, M_max, d_blobs, d_counts, d_status, d_processed=0):
         self._check(self.lib.mocap_find_blobs_dev(self._h, int(n_frames), _vp(d_images), int(M_max), _vp(d_blobs),
                                                   _vp(d_counts), _vp(d_status), _vp(d_processed or 0)))
+
+    # ------------------------------------------------------------------ preview stream
+    def jpeg_bound(self, H, W_total):
+        """mocap_jpeg_bound: upper bound on the bytes of one H x W_total image (-1: not a size the encoder takes)."""
+        return int(self.lib.mocap_jpeg_bound(int(H), int(W_total)))
+
+    def jpeg_default_capacity(self, H, W_total):
+        """Slot size the Python layer starts with: a quarter of the raw frame (camera frames compress to a few per cent of
+        it), never more than the bound; a call that overflows it is repeated with the size the core reported."""
+        return min(self.jpeg_bound(H, W_total), 1024 + H * W_total * 3 // 4)
+
+    def encode_jpeg(self, bgr, quality=95, capacity=None):
+        """mocap_encode_jpeg: bgr [F][T][H][W][3] uint8 (the blob stage's `processed`) -> per image the JPEG of its T tiles
+        side by side.  Returns {"jpeg": [bytes per image], "sizes", "status"}; with an explicit `capacity` an image that
+        needs more keeps its first `capacity` bytes and JPEG_ST_OVERFLOW in status."""
+        bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+        assert bgr.ndim == 5 and bgr.shape[4] == 3
+        F, T, H, W = bgr.shape[:4]
+        cap = max(1, self.jpeg_default_capacity(H, T * W)) if capacity is None else int(capacity)
+        while True:
+            buf = np.zeros((F, max(cap, 1)), dtype=np.uint8)
+            sizes, status = np.zeros(F, dtype=np.int64), np.zeros(F, dtype=np.int32)
+            self._check(self.lib.mocap_encode_jpeg(self._h, F, T, H, W, _p(bgr), int(quality), _p(buf), cap, _p(sizes), _p(status)))
+            if capacity is None and (status & JPEG_ST_OVERFLOW).any():
+                cap = int(sizes.max())
+                continue
+            return {"jpeg": [buf[f, :min(int(sizes[f]), cap)].tobytes() for f in range(F)], "sizes": sizes, "status": status}
+
+    def encode_jpeg_dev(self, n_images, T, H, W, d_bgr, quality, d_jpeg, capacity, d_sizes, d_status):
+        self._check(self.lib.mocap_encode_jpeg_dev(self._h, int(n_images), int(T), int(H), int(W), _vp(d_bgr), int(quality),
+                                                   _vp(d_jpeg), int(capacity), _vp(d_sizes), _vp(d_status)))
+
+    def find_blobs_jpeg(self, images, M_max=16, quality=95, capacity=None):
+        """mocap_find_blobs_jpeg: find_blobs with the preview stream ("jpeg": bytes per frame set, "jpeg_size") in place of
+        the processed frames, which stay on the device."""
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        F, C = images.shape[:2]
+        assert images.shape == (F, C, self.img_rows, self.img_cols, 3) and C == self.img_C
+        S = self.img_cols
+        cap = self.jpeg_default_capacity(S, S * C) if capacity is None else int(capacity)
+        while True:
+            blobs = np.zeros((F, C, M_max, 2), dtype=np.float32)
+            counts, status, ncont = (np.zeros((F, C), dtype=np.int32) for _ in range(3))
+            buf, size = np.zeros((F, max(cap, 1)), dtype=np.uint8), np.zeros(F, dtype=np.int64)
+            self._check(self.lib.mocap_find_blobs_jpeg(self._h, F, _p(images), int(M_max), _p(blobs), _p(counts), _p(status),
+                                                       _p(ncont), int(quality), _p(buf), cap, _p(size)))
+            if capacity is None and (size > cap).any():
+                cap = int(size.max())
+                continue
+            return {"blobs": blobs, "counts": counts, "status": status, "n_contours": ncont,
+                    "jpeg": [buf[f, :min(int(size[f]), cap)].tobytes() for f in range(F)], "jpeg_size": size}
 
     # ------------------------------------------------------------------ after the path
     def set_world_transform(self, to_world):

@@ -304,6 +304,40 @@ def camera_read_find_dots(raw_frames, M_max=64, want_frames=True):
     return frames, image_points
 
 
+def get_frames_jpeg(raw_frames, M_max=64, quality=95):
+    """The MJPEG preview of the reference (index.py:55-56: cameras.get_frames(), i.e. np.hstack of the processed frames,
+    then cv.imencode('.jpg', frames)) for one set of raw frames: returns (jpeg_bytes, image_points).  The processed frames
+    are encoded where the blob stage leaves them, on the device; only the file (about 1 % of the frames) comes back.
+    jpeg_bytes is what the generator yields in place of cv.imencode(...)[1].tostring() (without the reference's debug
+    drawings, as camera_read_find_dots); image_points as camera_read_find_dots."""
+    raw = np.ascontiguousarray(np.asarray(raw_frames, dtype=np.uint8))
+    C, rows, cols = raw.shape[0], raw.shape[1], raw.shape[2]
+    params = _state["camera_params"]
+    if params is None or len(params) < C:
+        raise RuntimeError("set_camera_params() has not been called with one entry per camera")
+    K = np.array([np.array(params[i]["intrinsic_matrix"], dtype=np.float64) for i in range(C)])
+    dist = np.array([np.array(params[i]["distortion_coef"], dtype=np.float64).ravel()[:5] for i in range(C)])
+    rot = np.array([int(params[i].get("rotation", 0)) for i in range(C)], dtype=np.int32)
+    with _state["lock"]:
+        core = get_core()
+        key = (rows, cols, K.tobytes(), dist.tobytes(), rot.tobytes())
+        if _state["img_key"] != key:
+            core.set_image_params(rows, cols, K, dist, rot)
+            _state["img_key"] = key
+        res = core.find_blobs_jpeg(raw[None], M_max=M_max, quality=quality)
+        if (res["status"] & capi.BLOB_ST_POINT_OVERFLOW).any():     # more dots than slots: ask again
+            res = core.find_blobs_jpeg(raw[None], M_max=int(res["n_contours"].max()) + 1, quality=quality)
+    if (res["status"] & capi.BLOB_ST_CAP_OVERFLOW).any():
+        cams = np.nonzero(res["status"][0] & capi.BLOB_ST_CAP_OVERFLOW)[0].tolist()
+        raise capi.MocapError(f"camera(s) {cams}: more contours than the blob stage's largest tables hold "
+                              "(BLOB_ST_CAP_OVERFLOW); no centroids were produced for them")
+    image_points = []
+    for c in range(C):
+        n = int(res["counts"][0, c])
+        image_points.append(res["blobs"][0, c, :n].astype(np.int64).tolist() if n else [[None, None]])
+    return res["jpeg"][0], image_points
+
+
 def set_to_world_coords_matrix(to_world_coords_matrix):
     """Cameras.to_world_coords_matrix (helpers.py:40,100): with a matrix set, the frame path returns
     world coordinates -- the loop at helpers.py:96-103 runs fused in the kernel's store.  None = off
@@ -416,11 +450,12 @@ def track_frame_filtered(image_points, camera_poses, now=None, O_max=8):
     return res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), _objects_list(res), _filtered_list(res)
 
 
-def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=True, O_max=8):
+def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=True, O_max=8, want_jpeg=False, quality=95):
     """Raw camera frames -> (image_points, errors, object_points, objects): Cameras._camera_read's preprocessing,
     _find_dot, the frame path, the world transform and locate_objects (helpers.py:68-108) in one core call; nothing but the
     payload crosses PCIe on the way back.  image_points is what _find_dot returns per camera ([[None, None]] when a
-    camera saw nothing)."""
+    camera saw nothing).  want_jpeg=True appends the preview stream's frame (get_frames_jpeg's bytes, same call, same wait)
+    as a fifth element."""
     raw = np.ascontiguousarray(np.asarray(raw_frames, dtype=np.uint8))
     C, rows, cols = raw.shape[0], raw.shape[1], raw.shape[2]
     params = _state["camera_params"]
@@ -436,7 +471,10 @@ def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=Tr
             core.set_image_params(rows, cols, K, dist, rot)
             _state["img_key"] = key
         while True:
-            res = core.track_frame_images(raw[None], M_max=M_max, O_max=O_max if is_locating_objects else 0)
+            if want_jpeg:
+                res = core.track_frame_images_jpeg(raw[None], M_max=M_max, O_max=O_max if is_locating_objects else 0, quality=quality)
+            else:
+                res = core.track_frame_images(raw[None], M_max=M_max, O_max=O_max if is_locating_objects else 0)
             if (res["blob_status"] & capi.BLOB_ST_POINT_OVERFLOW).any() and M_max < 256:   # more dots than slots: ask again
                 M_max = min(256, 4 * M_max)
                 continue
@@ -449,11 +487,12 @@ def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=Tr
     for c in range(C):
         n = int(res["counts"][0, c])
         image_points.append(res["blobs"][0, c, :n].astype(np.int64).tolist() if n else [[None, None]])
+    tail = (res["jpeg"][0],) if want_jpeg else ()
     k = int(res["n_pts"][0])
     if k == 0:
-        return image_points, np.array([]), np.array([]), []
+        return (image_points, np.array([]), np.array([]), []) + tail
     return (image_points, res["err"][0, :k].copy(), res["xyz"][0, :k].copy(),
-            _objects_list(res) if is_locating_objects else [])
+            _objects_list(res) if is_locating_objects else []) + tail
 
 
 def object_points_payload(errors, object_points, objects, filtered_objects=()):
