@@ -266,7 +266,9 @@ enum {
  *   counts    [F][C] centroids per camera (0 = the reference's [[None, None]], helpers.py:158-159)
  *   status    [F][C] MOCAP_BLOB_ST_* bits
  *   processed [F][C][cols][cols][3] (may be NULL) the BGR frame the reference streams to the UI
- *             (helpers.py:82,141; without the debug drawings of helpers.py:148,155-156)
+ *             (helpers.py:82,141).  Bare by default; with mocap_set_preview_overlay the contours (helpers.py:148) and
+ *             centre marks (helpers.py:157) are painted into it on the device -- the coordinate label of helpers.py:156
+ *             (cv.putText) is the one drawing that is not.  blobs, counts, status and n_contours never depend on the option.
  *   n_contours [F][C] (may be NULL) contours found, including the zero-area ones the reference skips */
 int mocap_find_blobs(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, int M_max, float* blobs,
                      int32_t* counts, int32_t* status, uint8_t* processed, int32_t* n_contours);
@@ -310,6 +312,45 @@ int mocap_encode_jpeg(mocap_ctx* ctx, int64_t n_images, int T, int H, int W, con
 int mocap_find_blobs_jpeg(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, int M_max, float* blobs, int32_t* counts,
                           int32_t* status, int32_t* n_contours, int quality, uint8_t* jpeg, int64_t capacity,
                           int64_t* jpeg_size);
+
+/* ---------------------------------------------------------------- preview overlays
+ * The drawings the reference puts on its preview, painted on the device into pictures of the blob stage's `processed` layout
+ * ([F][C][S][S][3] uint8 BGR, S = cols).  Off by default: with flags 0 every entry point writes the bytes it wrote before.
+ *   MOCAP_OVERLAY_CONTOURS  cv.drawContours(img, contours, -1, (0,255,0), 1) (helpers.py:148): every pixel a border trace of
+ *                           findContours visits, outer or hole -- a mask pixel with one of its four edge neighbours off, the
+ *                           outside of the picture counting as off -- becomes (0,255,0)
+ *   MOCAP_OVERLAY_CENTRES   cv.circle(img, (cx,cy), 1, (100,255,100), -1) (helpers.py:157): the pixel and its four edge
+ *                           neighbours of every stored centroid (the first `counts` of M_max), clipped to the picture; over
+ *                           the contours
+ *   MOCAP_OVERLAY_EPILINES  one epipolar line per point and camera (drawlines, helpers.py:365), see mocap_draw_epilines
+ * Bits 1 and 2 are honoured by the calls that produce a picture: mocap_find_blobs (processed != NULL), mocap_find_blobs_dev
+ * (d_processed != NULL), mocap_find_blobs_jpeg and mocap_track_frame_images_jpeg; bit 4 by mocap_track_frame_images_jpeg, which
+ * queues the line kernel between its export and the encoder (still one enqueue and one event wait).  A picture whose status
+ * carries MOCAP_BLOB_ST_CAP_OVERFLOW is left undrawn.  Any other bit: MOCAP_E_ARG, nothing changes. */
+enum {
+  MOCAP_OVERLAY_CONTOURS = 1,
+  MOCAP_OVERLAY_CENTRES = 2,
+  MOCAP_OVERLAY_EPILINES = 4
+};
+int mocap_set_preview_overlay(mocap_ctx* ctx, uint32_t flags);
+/* mocap_draw_epilines: the epipolar lines of a frame batch's points, with the cameras of mocap_set_cameras.
+ *   bgr [F][C][S][S][3] in and out; S <= 65535
+ *   blobs [F][C][M_max][2], counts [F][C]                          the frame path's inputs
+ *   corr [F][K_max][C], n_pts [F] (its n_out), status [F]          its outputs
+ * For every point k < n_pts[f] of a frame with status == 0, r = the lowest camera with corr[k][r] >= 0; in the picture of every
+ * camera i > r the line (a, b, c) = computeCorrespondEpilines of blob corr[k][r] of camera r under
+ * fundamentalFromProjections(P_r, P_i) -- the line the frame kernels gate on, float32 under MOCAP_OPT_F32_ROUNDING -- is
+ * painted, in double: |b| >= |a| and b != 0: y = rint(-(a x + c) / b) for every column x; else a != 0: x = rint(-(b y + c) / a)
+ * for every row y (rint = to nearest, ties to even); else nothing; pixels outside the picture are dropped.  Point k has colour
+ * palette[k % 6], BGR (255,0,0) (0,0,255) (255,255,0) (255,0,255) (0,255,255) (255,128,0); lines are applied in ascending k.
+ * (The reference draws, in random colours, the lines of every root alive at camera i, including roots that end with fewer
+ * than two views, and raises on a vertical line: this contract is the core's own.)
+ * The "_dev" form enqueues on the context's stream; the host form uploads, draws and downloads. */
+int mocap_draw_epilines_dev(mocap_ctx* ctx, int64_t n_frames, int S, uint8_t* d_bgr, int M_max, const float* d_blobs,
+                            const int32_t* d_counts, int K_max, const int16_t* d_corr, const int32_t* d_n_pts,
+                            const int32_t* d_status);
+int mocap_draw_epilines(mocap_ctx* ctx, int64_t n_frames, int S, uint8_t* bgr, int M_max, const float* blobs,
+                        const int32_t* counts, int K_max, const int16_t* corr, const int32_t* n_pts, const int32_t* status);
 
 /* ---------------------------------------------------------------- after the path
  * World-coordinate epilogue of the frame loop (helpers.py:96-103), fused into the frame path's store:

@@ -155,6 +155,9 @@ int find_blobs_dev_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_ima
   // images whose border tables overflowed run again with the largest tables LDS holds; the launch is
   // a no-op (one status read per workgroup) for every other image
   HIP_TRY(ctx, launch_blob_contours(a, p_large, n_large, 1, ctx->stream));
+  // the preview's drawings (mocap_set_preview_overlay), over the finished frames: centroids and mask come from the undrawn frame
+  if (d_processed && (ctx->preview_overlay & (kOverlayContours | kOverlayCentres)))
+    return overlay_blobs_locked(ctx, ctx->preview_overlay, n_frames * C, S, M_max, d_blobs, d_counts, d_status, d_processed);
   return MOCAP_OK;
 }
 

@@ -140,6 +140,8 @@ struct mocap_ctx {
   mocap::JpegParams jpeg_params{};
   DevBuf jpeg_ws;           // per image of a chunk: coefficients | AC bits | bit offsets | total bits | unstuffed scan
   DevBuf jpeg_stage;        // host-buffer entry points: frames in, [F][capacity] streams, sizes and status out
+  uint32_t preview_overlay = 0;  // MOCAP_OVERLAY_* bits (mocap_set_preview_overlay): drawings on the processed frames, off by default
+  DevBuf overlay_stage;     // mocap_draw_epilines: pictures | blobs | counts | corr | n_pts | status
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);
@@ -156,6 +158,12 @@ int mocap_blob_stage_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_i
 // JPEG encoder on device pointers (jpeg_capi.hip): arguments checked, kernels enqueued on the context's stream
 int jpeg_dev_locked(mocap_ctx* ctx, const char* who, int64_t n_images, int T, int H, int W, const uint8_t* d_bgr, int quality,
                     uint8_t* d_jpeg, int64_t capacity, int64_t* d_sizes, int32_t* d_status, int64_t out_stride = 0);
+// preview overlays (overlay_capi.hip): contours and centre marks over the blob stage's outputs (n_images pictures of edge S, the
+// mask in ctx->img_mask), and the epipolar lines of a frame batch's points; `flags` = the bits the calling entry point read
+int overlay_blobs_locked(mocap_ctx* ctx, uint32_t flags, int64_t n_images, int S, int M_max, const float* d_blobs,
+                         const int32_t* d_counts, const int32_t* d_status, uint8_t* d_bgr);
+int epilines_dev_locked(mocap_ctx* ctx, const char* who, int64_t n_frames, int S, uint8_t* d_bgr, int M_max, const float* d_blobs,
+                        const int32_t* d_counts, int K_max, const int16_t* d_corr, const int32_t* d_n_pts, const int32_t* d_status);
 // the preview stream of the chained live call (mocap_track_frame_images_jpeg)
 struct JpegOut {
   int quality;

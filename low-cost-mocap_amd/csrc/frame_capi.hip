@@ -917,6 +917,11 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
       if (rc) return rc;
     }
     if (jo) {  // encoded in device memory, then the bytes that exist travel into the pinned block 16 at a time
+      if (ctx->preview_overlay & kOverlayEpilines) {  // the points' epipolar lines, over the blob stage's own drawings
+        rc = epilines_dev_locked(ctx, "mocap_track_frame_images_jpeg", n_frames, ctx->img_S, d_proc, M_max, d_blobs, d_counts, K_max,
+                                 d.corr, d.n_out, d.status);
+        if (rc) return rc;
+      }
       rc = jpeg_dev_locked(ctx, "mocap_track_frame_images_jpeg", n_frames, C, ctx->img_S, ctx->img_S, d_proc, jo->quality, d_jpeg,
                            jo->capacity, d_jsize, d_jstat, (int64_t)j_stride);
       if (rc) return rc;

@@ -355,6 +355,33 @@ hipError_t launch_blob_mask(const BlobArgs& a, hipStream_t stream);
 hipError_t launch_blob_contours(const BlobArgs& a, int P_cap, int N_cap, int only_overflowed, hipStream_t stream);
 size_t blob_contour_lds_bytes(int S, int P_cap, int N_cap);
 
+// preview overlays (reference helpers.py:148,157,365), csrc/overlay_kernels.hip; bits mirrored from include/mocap_core.h (MOCAP_OVERLAY_*)
+constexpr uint32_t kOverlayContours = 1, kOverlayCentres = 2, kOverlayEpilines = 4;
+struct OverlayArgs {         // contours and centre marks, from what the blob stage left behind
+  int64_t n_images;
+  int S, M_max;
+  uint32_t flags;
+  const unsigned long long* mask;  // [n_images][S][ceil(S / 64)] (BlobArgs::mask)
+  const float* blobs;        // [n_images][M_max][2]
+  const int32_t* counts;     // [n_images]
+  const int32_t* status;     // [n_images] pictures with BLOB_ST_CAP_OVERFLOW_ are left undrawn
+  uint8_t* bgr;              // [n_images][S][S][3]
+};
+hipError_t launch_overlay_blobs(const OverlayArgs& a, hipStream_t stream);
+struct EpilineArgs {         // one line per output point and camera behind the point's root camera
+  int64_t n_frames;
+  int C, S, M_max, K_max;
+  int f32_rounding;          // the line's coefficients rounded to float32 as the frame kernels round them (CamView::f32_rounding)
+  const double* F;           // [C][C][9] (CamView::F)
+  const float* blobs;        // [F][C][M_max][2]
+  const int32_t* counts;     // [F][C]
+  const int16_t* corr;       // [F][K_max][C]
+  const int32_t* n_pts;      // [F]
+  const int32_t* status;     // [F] frames with status != 0 are left undrawn
+  uint8_t* bgr;              // [F][C][S][S][3]
+};
+hipError_t launch_overlay_epilines(const EpilineArgs& a, hipStream_t stream);
+
 // explicit-correspondence triangulation, optionally batched over P camera sets (bundle adjustment)
 struct TriArgs {
   CamView cv;             // tables of camera set 0; set p is offset by the strides below

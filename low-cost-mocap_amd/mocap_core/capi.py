@@ -31,6 +31,9 @@ ST_ROUNDED = 8          # informational (mocap_match_triangulate_f64): a coordin
 BLOB_ST_POINT_OVERFLOW = 1
 BLOB_ST_CAP_OVERFLOW = 2
 JPEG_ST_OVERFLOW = 1      # mocap_encode_jpeg*: the image needs more than `capacity` bytes
+OVERLAY_CONTOURS = 1      # mocap_set_preview_overlay: every contour pixel green (cv.drawContours, helpers.py:148)
+OVERLAY_CENTRES = 2       # ... a filled radius-1 circle on every stored centroid (cv.circle, helpers.py:157)
+OVERLAY_EPILINES = 4      # ... one epipolar line per point and later camera (drawlines, helpers.py:365)
 OPT_F32_ROUNDING = 1
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
@@ -89,6 +92,9 @@ SIGNATURES = {
     "mocap_find_blobs_jpeg": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "mocap_track_frame_images_jpeg": (_i32, [_vp, _i64, _vp, _i32, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                                              _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "mocap_set_preview_overlay": (_i32, [_vp, _u32]),
+    "mocap_draw_epilines": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "mocap_draw_epilines_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "mocap_set_world_transform": (_i32, [_vp, _vp]),
     "mocap_locate_objects": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_locate_objects_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -179,6 +185,7 @@ class MocapCore:
         self._hit_cap, self._force_wide = 32, False
         self.f32_rounding = True     # MOCAP_OPT_F32_ROUNDING, the library's default
         self.filter_objects_n = 0    # drone indices of the object filter (set_object_filter), 0 = off
+        self.preview_overlay = 0     # OVERLAY_* bits (set_preview_overlay), the library's default
 
     def close(self):
         if getattr(self, "_h", None):
@@ -517,6 +524,36 @@ class MocapCore:
                 continue
             return {"blobs": blobs, "counts": counts, "status": status, "n_contours": ncont,
                     "jpeg": [buf[f, :min(int(size[f]), cap)].tobytes() for f in range(F)], "jpeg_size": size}
+
+    # ------------------------------------------------------------------ preview overlays
+    def set_preview_overlay(self, flags):
+        """mocap_set_preview_overlay: OVERLAY_* bits.  Contours and centre marks are painted into every picture the blob
+        stage hands out (find_blobs(want_processed=True), find_blobs_dev with d_processed, find_blobs_jpeg,
+        track_frame_images_jpeg), epipolar lines into the stream of track_frame_images_jpeg.  0 (default) = bare frames."""
+        self._check(self.lib.mocap_set_preview_overlay(self._h, int(flags)))
+        self.preview_overlay = int(flags)
+
+    def draw_epilines(self, bgr, blobs, counts, corr, n_pts, status):
+        """mocap_draw_epilines: bgr [F][C][S][S][3] uint8 (copied, the drawn copy is returned), blobs [F][C][M][2], counts
+        [F][C] = the frame path's inputs, corr [F][K][C], n_pts [F], status [F] = its outputs, cameras of set_cameras."""
+        bgr = np.array(bgr, dtype=np.uint8, order="C")
+        F, C, S = bgr.shape[:3]
+        assert bgr.shape == (F, C, S, S, 3) and C == self.C
+        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
+        M = blobs.shape[2]
+        assert blobs.shape == (F, C, M, 2)
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(F, C)
+        corr = np.ascontiguousarray(corr, dtype=np.int16)
+        K = corr.shape[1]
+        assert corr.shape == (F, K, C)
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        status = np.ascontiguousarray(status, dtype=np.int32).reshape(F)
+        self._check(self.lib.mocap_draw_epilines(self._h, F, S, _p(bgr), M, _p(blobs), _p(counts), K, _p(corr), _p(n_pts), _p(status)))
+        return bgr
+
+    def draw_epilines_dev(self, n_frames, S, d_bgr, M_max, d_blobs, d_counts, K_max, d_corr, d_n_pts, d_status):
+        self._check(self.lib.mocap_draw_epilines_dev(self._h, int(n_frames), int(S), _vp(d_bgr), int(M_max), _vp(d_blobs),
+                                                     _vp(d_counts), int(K_max), _vp(d_corr), _vp(d_n_pts), _vp(d_status)))
 
     # ------------------------------------------------------------------ after the path
     def set_world_transform(self, to_world):

@@ -46,6 +46,7 @@ _state = {
     "ba_blas_threads": None,      # None: the process's BLAS settings are left alone (as the reference does); n: pinned for the solve
     "img_key": None,         # (rows, cols, K, dist, rot) of the lens model currently uploaded
     "to_world": None,        # last Cameras.to_world_coords_matrix handed to set_to_world_coords_matrix
+    "overlay": 0,            # capi.OVERLAY_* bits of set_preview_overlay: the drawings on the preview, off by default
 }
 
 
@@ -53,6 +54,26 @@ def get_core(device_id=0):
     if _state["core"] is None:
         _state["core"] = capi.MocapCore(device_id)
     return _state["core"]
+
+
+def set_preview_overlay(flags):
+    """The reference's drawings on the preview, painted on the device: capi.OVERLAY_CONTOURS (cv.drawContours,
+    helpers.py:148) | capi.OVERLAY_CENTRES (cv.circle, helpers.py:157) | capi.OVERLAY_EPILINES (drawlines, helpers.py:365).
+    0 (default) = bare frames.  camera_read_find_dots, get_frames_jpeg and camera_read_track then return annotated pictures;
+    with OVERLAY_EPILINES find_point_correspondance_and_object_points draws the lines into the frames it is handed.  The
+    coordinate label of helpers.py:156 (cv.putText) is not drawn."""
+    flags = int(flags)
+    if flags & ~(capi.OVERLAY_CONTOURS | capi.OVERLAY_CENTRES | capi.OVERLAY_EPILINES):
+        raise ValueError(f"unknown preview overlay bit in {flags:#x}")
+    with _state["lock"]:
+        _state["overlay"] = flags
+
+
+def _apply_overlay(core):
+    """The module switch -> the context (callers hold the lock); a core handed over by set_core gets it on first use."""
+    if getattr(core, "preview_overlay", 0) != _state["overlay"]:
+        core.set_preview_overlay(_state["overlay"])
+    return core
 
 
 def _ba_core():
@@ -236,8 +257,10 @@ def pack_frame(image_points, M_max=None, strict=False):
 
 def find_point_correspondance_and_object_points(image_points, camera_poses, frames):
     """helpers.py:339-421.  `image_points` is mutated like the reference does (the [None, None]
-    sentinel of an empty camera is removed, helpers.py:342-346).  `frames` is returned untouched:
-    the reference only draws debug epipolar lines into it (helpers.py:365)."""
+    sentinel of an empty camera is removed, helpers.py:342-346).  `frames` is returned as it came -- the very
+    objects -- unless set_preview_overlay has capi.OVERLAY_EPILINES on: then the points' epipolar lines are drawn into
+    the frames on the device (helpers.py:365, drawlines; contract in include/mocap_core.h, mocap_draw_epilines) and the
+    drawn copies are returned; entries that are None are skipped."""
     for image_points_i in image_points:
         try:
             image_points_i.remove([None, None])
@@ -247,6 +270,8 @@ def find_point_correspondance_and_object_points(image_points, camera_poses, fram
         core = _upload_cameras(camera_poses)
         blobs, counts, _ = pack_frame(image_points)
         res = core.match_triangulate_auto(blobs, counts, gate_px=5.0)
+        if _state["overlay"] & capi.OVERLAY_EPILINES and int(res["status"][0]) == 0:
+            frames = _draw_epilines(core, frames, blobs, counts, res)
     if int(res["status"][0]) != 0:
         # still over a cap after the worst-case re-submit (> 2^24 candidate groups for one root, > 2^32 per
         # frame, C*M > 1024 roots): the reference would enumerate the full product; an empty answer would be
@@ -256,6 +281,19 @@ def find_point_correspondance_and_object_points(image_points, camera_poses, fram
     if k == 0:
         return np.array([]), np.array([]), frames
     return res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), frames
+
+
+def _draw_epilines(core, frames, blobs, counts, res):
+    """frames: one S x S x 3 BGR picture or None per camera -> the list with the frame's epipolar lines drawn."""
+    have = [i for i, f in enumerate(frames) if f is not None]
+    if not have or len(frames) != core.C:
+        return frames
+    shape = np.asarray(frames[have[0]]).shape
+    bgr = np.zeros((1, core.C) + shape, dtype=np.uint8)
+    for i in have:
+        bgr[0, i] = frames[i]
+    drawn = core.draw_epilines(bgr, blobs, counts, res["corr"], res["n_out"], res["status"])
+    return [drawn[0, i] if f is not None else None for i, f in enumerate(frames)]
 
 
 def find_point_correspondance_and_object_points_batch(blobs, counts, camera_poses, gate_px=5.0, K_max=None):
@@ -271,7 +309,8 @@ def camera_read_find_dots(raw_frames, M_max=64, want_frames=True):
     """The per-camera body of Cameras._camera_read (helpers.py:71-82) + Cameras._find_dot
     (helpers.py:143-163) for one set of raw frames (what pseyepy's Camera.read() returns):
     returns (frames, image_points) with frames = the processed BGR frames the reference streams
-    (without its debug drawings) and image_points = per camera [[x, y], ...] or [[None, None]]
+    (bare by default; with the contours and centre marks of helpers.py:148,157 under set_preview_overlay,
+    never with the coordinate label of helpers.py:156) and image_points = per camera [[x, y], ...] or [[None, None]]
     (helpers.py:158-159) -- ready for find_point_correspondance_and_object_points.
     Lens model and rotation come from set_camera_params() (camera-params.json entries)."""
     raw = np.ascontiguousarray(np.asarray(raw_frames, dtype=np.uint8))
@@ -283,7 +322,7 @@ def camera_read_find_dots(raw_frames, M_max=64, want_frames=True):
     dist = np.array([np.array(params[i]["distortion_coef"], dtype=np.float64).ravel()[:5] for i in range(C)])
     rot = np.array([int(params[i].get("rotation", 0)) for i in range(C)], dtype=np.int32)
     with _state["lock"]:
-        core = get_core()
+        core = _apply_overlay(get_core())
         key = (rows, cols, K.tobytes(), dist.tobytes(), rot.tobytes())
         if _state["img_key"] != key:
             core.set_image_params(rows, cols, K, dist, rot)
@@ -308,8 +347,8 @@ def get_frames_jpeg(raw_frames, M_max=64, quality=95):
     """The MJPEG preview of the reference (index.py:55-56: cameras.get_frames(), i.e. np.hstack of the processed frames,
     then cv.imencode('.jpg', frames)) for one set of raw frames: returns (jpeg_bytes, image_points).  The processed frames
     are encoded where the blob stage leaves them, on the device; only the file (about 1 % of the frames) comes back.
-    jpeg_bytes is what the generator yields in place of cv.imencode(...)[1].tostring() (without the reference's debug
-    drawings, as camera_read_find_dots); image_points as camera_read_find_dots."""
+    jpeg_bytes is what the generator yields in place of cv.imencode(...)[1].tostring() (with the drawings
+    set_preview_overlay has switched on, as camera_read_find_dots); image_points as camera_read_find_dots."""
     raw = np.ascontiguousarray(np.asarray(raw_frames, dtype=np.uint8))
     C, rows, cols = raw.shape[0], raw.shape[1], raw.shape[2]
     params = _state["camera_params"]
@@ -319,7 +358,7 @@ def get_frames_jpeg(raw_frames, M_max=64, quality=95):
     dist = np.array([np.array(params[i]["distortion_coef"], dtype=np.float64).ravel()[:5] for i in range(C)])
     rot = np.array([int(params[i].get("rotation", 0)) for i in range(C)], dtype=np.int32)
     with _state["lock"]:
-        core = get_core()
+        core = _apply_overlay(get_core())
         key = (rows, cols, K.tobytes(), dist.tobytes(), rot.tobytes())
         if _state["img_key"] != key:
             core.set_image_params(rows, cols, K, dist, rot)
@@ -465,7 +504,7 @@ def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=Tr
     dist = np.array([np.array(params[i]["distortion_coef"], dtype=np.float64).ravel()[:5] for i in range(C)])
     rot = np.array([int(params[i].get("rotation", 0)) for i in range(C)], dtype=np.int32)
     with _state["lock"]:
-        core = _upload_cameras(camera_poses)
+        core = _apply_overlay(_upload_cameras(camera_poses))
         key = (rows, cols, K.tobytes(), dist.tobytes(), rot.tobytes())
         if _state["img_key"] != key:
             core.set_image_params(rows, cols, K, dist, rot)

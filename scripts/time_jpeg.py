@@ -3,9 +3,11 @@
    python scripts/time_jpeg.py [--calls N] [--cameras C] [--frame-sets 1,64]
 
 For 8 cameras x 320 x 320 (raw 240 x 320 frames of the synthetic ring rig, dots on black) and every batch size asked for,
-three routes take turns, `calls` each after 10 warm-up calls each, host wall clock per call (Python binding included):
+four routes take turns, `calls` each after 10 warm-up calls each, host wall clock per call (Python binding included):
   track_frame_images        the chained call without the stream
   track_frame_images_jpeg   the same with the JPEG of the processed frames in its payload (quality 95)
+  ... with overlays         the same call with mocap_set_preview_overlay(7): contours, centre marks and epipolar lines painted
+                            into the frames before the encoder (the option is set outside the timed window)
   today's route             track_frame_images, then find_blobs(want_processed=True) to bring `processed` to the host
                             (a second blob pass: the chained call has no `processed` output), then PIL's encoder on one core
                             as the stand-in for cv.imencode -- reported split into download and encode
@@ -55,6 +57,9 @@ def main():
         def with_jpeg():
             sizes["jpeg"] = core.track_frame_images_jpeg(images, quality=95, **kw)["jpeg_size"]
 
+        def with_overlays():
+            sizes["overlay"] = core.track_frame_images_jpeg(images, quality=95, **kw)["jpeg_size"]
+
         def download():
             return core.find_blobs(images, M_max=16, want_processed=True)["processed"]
 
@@ -67,13 +72,20 @@ def main():
         for _ in range(10):
             plain()
             with_jpeg()
+            core.set_preview_overlay(7)
+            with_overlays()
+            core.set_preview_overlay(0)
             proc = download()
-        ts = {"track_frame_images": [], "track_frame_images_jpeg": [], "processed to the host": [], "PIL encode, one core": []}
+        ts = {"track_frame_images": [], "track_frame_images_jpeg": [], "... with overlays (7)": [], "processed to the host": [],
+              "PIL encode, one core": []}
         for _ in range(a.calls):
-            for name, fn in (("track_frame_images", plain), ("track_frame_images_jpeg", with_jpeg), ("processed to the host", download)):
+            for name, fn, flags in (("track_frame_images", plain, 0), ("track_frame_images_jpeg", with_jpeg, 0),
+                                    ("... with overlays (7)", with_overlays, 7), ("processed to the host", download, 0)):
+                core.set_preview_overlay(flags)
                 t0 = time.perf_counter()
                 fn()
                 ts[name].append((time.perf_counter() - t0) * 1e3)
+            core.set_preview_overlay(0)
             if Image is not None:
                 t0 = time.perf_counter()
                 pil_encode(proc)
@@ -86,6 +98,8 @@ def main():
             else:
                 print(f"{k:26s} skipped (PIL is not installed)")
         print(f"added by the JPEG          {med['track_frame_images_jpeg'] - med['track_frame_images']:9.3f} ms per call")
+        print(f"added by the overlays      {med['... with overlays (7)'] - med['track_frame_images_jpeg']:9.3f} ms per call "
+              f"(JPEG {int(np.mean(sizes['overlay']))} bytes per frame set with them)")
         print(f"today's route adds         {med['processed to the host'] + med.get('PIL encode, one core', 0.0):9.3f} ms per call "
               "(second blob pass + download" + (" + PIL)" if Image is not None else "; encode not measured)"))
         print(f"bytes over PCIe per frame set: JPEG {int(np.mean(sizes['jpeg']))}, processed {C * 320 * 320 * 3}")
