@@ -146,20 +146,32 @@ __device__ __forceinline__ double div_by(double a, double b, double r) {
 //   dominate the candidate set, so shift 0 alone is never enough, and one Laguerre step always
 //   is); max 2.3e-14 relative on X against LAPACK dgesdd.
 constexpr int kInvIters = 5;
+// Factorisations at most.  Laguerre's climb is cubic once the shift is closer to lam1 than lam2 - lam1 is, but only linear
+// (the distance shrinks by ~0.27 per step) before that: lam1 / lam2 = 1 - 1e-k takes about 3 + 1.8 k factorisations, 8 at 1 - 1e-3,
+// 10 at 1 - 1e-4, 28 for a double eigenvalue, where rounding ends the climb through the clamped pivot.  With 8 (until the
+// per-sample tests of the core) a matrix with lam1 / lam2 = 1 - 1e-4 left the loop unconverged and the inverse iteration
+// returned a mixture of the two lowest eigenvectors (backward error 1e-5).  32 lets the loop end through its convergence
+// test for every lam1 / lam2 <= 1 - 1e-13; beyond that any mixture has a backward error of (lam2 - lam1) / lam4 <= 1e-13.
+// Lanes that converge earlier (every lane of the bench stream: two factorisations) compute what they always computed.
+constexpr int kMaxFactorisations = 32;
 // lamcut / lam_lb: the exact cut-off of candidate selection (EigCut below).  trace((B - lam I)^-1) = s1 >= 1/(lam1 - lam),
 // so every factorisation yields the rigorous lower bound lam1 >= lam + 1/s1.  After the FIRST factorisation (lam = 0)
 // the candidate is dropped when s1 * lamcut < 1 (returns false, `out` untouched); otherwise lam_lb receives the bound
 // of the last factorisation, shrunk by the rounding allowance (Cholesky backward error and the rounding of B itself
-// are O(1e-15 tr); 2e-12 tr is charged).  lamcut = +inf switches the cut off.
+// are O(1e-15 tr); 2e-12 tr is charged).  The bound is taken at lam_last, the shift s1_last was computed at: when the loop
+// runs out of factorisations its last pass has already advanced lam, and lam_new + 1/s1(lam_old) lies ABOVE lam1 (by
+// 2.4e-6 tr on a double eigenvalue with 8 factorisations, measured).  When the loop ends through its convergence test, lam_last == lam.
+// (Written as a second variable, not as an exit test before the step: that form doubled the spills of heavy_bb_kernel.)
+// lamcut = +inf switches the cut off.
 __device__ __forceinline__ bool smallest_eigvec4(const double (&a)[10], double (&out)[4], double lamcut, double& lam_lb) {
   const double tr = (a[0] + a[4]) + (a[7] + a[9]);
   // pivots are clamped from below (fmax also swallows NaN): a shift that rounding pushed past lam1
   // yields one tiny pivot, i.e. a huge last row of M -- still the wanted vector -- and s2/s1^2 -> 1,
   // which ends the loop through the ordinary convergence test
   const double floor_piv = tr * 1e-30 + 1e-300;
-  double lam = 0.0, piv3 = 1.0, s1_last = 1.0;
+  double lam = 0.0, piv3 = 1.0, s1_last = 1.0, lam_last = 0.0;
   double m[10];  // M = L^{-1}, lower triangular, packed like sidx with (row >= col) -> sidx(col,row)
-  for (int it = 0; it < 8; it++) {
+  for (int it = 0; it < kMaxFactorisations; it++) {
     // ---- Cholesky of B - lam I; r_i = 1 / l_ii
     const double r0 = rsqrt_pos(fmax(a[0] - lam, floor_piv));
     const double l10 = a[1] * r0, l20 = a[2] * r0, l30 = a[3] * r0;
@@ -187,6 +199,7 @@ __device__ __forceinline__ bool smallest_eigvec4(const double (&a)[10], double (
     const double s1 = (w00 + w11) + (w22 + w33);
     if (it == 0 && s1 * fma(2e-12, tr, lamcut) < 1.0) return false;
     s1_last = s1;
+    lam_last = lam;  // the shift s1_last and m[] belong to
     const double w01 = fma(m10, m11, fma(m20, m21, m30 * m31));
     const double w02 = fma(m20, m22, m30 * m32);
     const double w03 = m30 * m33;
@@ -224,7 +237,7 @@ __device__ __forceinline__ bool smallest_eigvec4(const double (&a)[10], double (
   out[1] = x1;
   out[2] = x2;
   out[3] = x3;
-  lam_lb = fma(1.0 - 1e-5, __builtin_amdgcn_rcp(s1_last), lam) - 2e-12 * tr;
+  lam_lb = fma(1.0 - 1e-5, __builtin_amdgcn_rcp(s1_last), lam_last) - 2e-12 * tr;
   return true;
 }
 
