@@ -275,6 +275,36 @@ int mocap_find_blobs(mocap_ctx* ctx, int64_t n_frames, const uint8_t* images, in
 int mocap_find_blobs_dev(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_images, int M_max, float* d_blobs,
                          int32_t* d_counts, int32_t* d_status, uint8_t* d_processed);
 
+/* ---------------------------------------------------------------- sub-pixel centroids (the core's own contract)
+ * The reference's centroid is int(m10 / m00) of the contour polygon (helpers.py:152-155): the truncation discards most of a
+ * pixel before the FP64 geometry sees the point.  mocap_set_centroid_mode chooses what the blob stage stores in `blobs`:
+ *   MOCAP_CENTROID_REFERENCE = 0  (default) the reference's value: every entry point writes the bytes it wrote before
+ *   MOCAP_CENTROID_WEIGHTED  = 1  the grey-weighted centroid defined below
+ * Any other value: MOCAP_E_ARG, nothing changes.  The mode is honoured by every call that makes blobs from images:
+ * mocap_find_blobs, mocap_find_blobs_dev, mocap_find_blobs_jpeg, mocap_track_frame_images, mocap_track_frame_images_jpeg.
+ * The weighted mode leaves the contours, their order and the rule "a slot per contour with m00 != 0, the first M_max kept"
+ * as they are: counts, status, n_contours, the mask, `processed` and the JPEG bytes do not change, only the values in
+ * `blobs`.  Hole contours are treated like any other contour.  A picture with MOCAP_BLOB_ST_CAP_OVERFLOW keeps count 0, one
+ * with MOCAP_BLOB_ST_POINT_OVERFLOW its first M_max slots.  The value of a slot:
+ *   window   the inclusive bounding box [x0..x1] x [y0..y1] of the contour's points as findContours(RETR_TREE,
+ *            CHAIN_APPROX_SIMPLE) returns them (the extremes of the simplified vertices are those of the full trace)
+ *   pixels   those of the window whose mask bit is on: grey > 51, grey = the plane the threshold is applied to
+ *            (COLOR_RGB2GRAY of the BGR frame, helpers.py:145-146)
+ *   weight   w = grey - 51, an integer in 1 .. 204
+ *   sums     sum(w), sum(w x), sum(w y): exact integers, held in 64 bits (one saturated 320 x 320 picture: sum(w x) = 3.3e9)
+ *   x = (double)sum(w x) / (double)sum(w), y likewise: IEEE division, rounded once to float32.  sum(w) > 0 always: the
+ *            contour's own points are on.
+ * Integer sums make the value independent of the order of the reduction: it is bit-reproducible and equals
+ * np.float32(np.float64(swx) / np.float64(sw)).  Where two windows of a picture overlap, each takes every mask pixel inside
+ * it, its neighbour's included.
+ * The preview overlay is not touched: MOCAP_OVERLAY_CENTRES keeps truncating the stored centroid, so in weighted mode the
+ * mark sits at the truncated weighted centroid. */
+enum {
+  MOCAP_CENTROID_REFERENCE = 0,
+  MOCAP_CENTROID_WEIGHTED = 1
+};
+int mocap_set_centroid_mode(mocap_ctx* ctx, int mode);
+
 /* ---------------------------------------------------------------- preview stream
  * The MJPEG preview of the reference (index.py:55-56): frames = cameras.get_frames() (helpers.py:137-141, np.hstack of the
  * processed frames), cv.imencode('.jpg', frames).  The encoder writes the file libjpeg writes with its defaults, byte for

@@ -94,6 +94,11 @@ int find_blobs_dev_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_ima
   if (ctx->img_act.reserve((size_t)want * bands * segs * 2)) return ctx->fail(MOCAP_E_HIP, "hipMalloc(activity map) failed");
   const size_t words = (size_t)(S + 63) / 64;
   if (ctx->img_mask.reserve((size_t)n_frames * C * S * words * 8)) return ctx->fail(MOCAP_E_HIP, "hipMalloc(mask) failed");
+  // weighted centroids: the mask kernel keeps its grey plane, the contour kernel the kept slots' bounding boxes
+  const bool weighted = ctx->centroid_mode == kCentroidWeighted;
+  if (weighted && (ctx->img_grey.reserve((size_t)n_frames * C * S * S) ||
+                   ctx->img_bbox.reserve((size_t)n_frames * C * M_max * 4 * sizeof(int16_t))))
+    return ctx->fail(MOCAP_E_HIP, "hipMalloc(grey plane, slot windows) failed");
   for (int64_t f0 = 0; f0 < n_frames; f0 += chunk_frames) {
     const int64_t nf = n_frames - f0 < chunk_frames ? n_frames - f0 : chunk_frames;
     const size_t i0 = (size_t)f0 * C;
@@ -123,6 +128,8 @@ int find_blobs_dev_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_ima
     a.counts = d_counts + i0;
     a.status = d_status + i0;
     a.n_contours = d_n_contours ? d_n_contours + i0 : nullptr;
+    a.grey = weighted ? (uint8_t*)ctx->img_grey.ptr + i0 * S * S : nullptr;
+    a.bbox = nullptr;
     if (a.skip_dark == 1 && !a.processed) HIP_TRY(ctx, launch_blob_activity(a, ctx->stream));  // the map's only reader
     HIP_TRY(ctx, launch_blob_mask(a, ctx->stream));
   }
@@ -138,6 +145,8 @@ int find_blobs_dev_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_ima
   a.counts = d_counts;
   a.status = d_status;
   a.n_contours = d_n_contours;
+  a.grey = weighted ? (uint8_t*)ctx->img_grey.ptr : nullptr;
+  a.bbox = weighted ? (int16_t*)ctx->img_bbox.ptr : nullptr;
   // table sizes that fit LDS next to the padded mask of this frame size (the mask grows with S^2 / 8)
   int p_small = kPCapSmall, n_small = kNCapSmall, p_large = kPCapLarge, n_large = kNCapLarge;
   const size_t lds_cap = 160 * 1024;
@@ -155,6 +164,8 @@ int find_blobs_dev_locked(mocap_ctx* ctx, int64_t n_frames, const uint8_t* d_ima
   // images whose border tables overflowed run again with the largest tables LDS holds; the launch is
   // a no-op (one status read per workgroup) for every other image
   HIP_TRY(ctx, launch_blob_contours(a, p_large, n_large, 1, ctx->stream));
+  // sub-pixel mode: every kept slot is overwritten with the grey-weighted centroid of its contour's window
+  if (weighted) HIP_TRY(ctx, launch_blob_weighted_centroids(a, ctx->stream));
   // the preview's drawings (mocap_set_preview_overlay), over the finished frames: centroids and mask come from the undrawn frame
   if (d_processed && (ctx->preview_overlay & (kOverlayContours | kOverlayCentres)))
     return overlay_blobs_locked(ctx, ctx->preview_overlay, n_frames * C, S, M_max, d_blobs, d_counts, d_status, d_processed);
@@ -367,6 +378,18 @@ extern "C" int mocap_set_blob_options(mocap_ctx* ctx, int skip_dark_tiles) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->blob_skip_dark = skip_dark_tiles == 2 ? 2 : (skip_dark_tiles ? 1 : 0);
+  return MOCAP_OK;
+}
+
+static_assert(MOCAP_CENTROID_REFERENCE == kCentroidReference && MOCAP_CENTROID_WEIGHTED == kCentroidWeighted,
+              "the modes of include/mocap_core.h and csrc/kernels.hpp must agree");
+
+extern "C" int mocap_set_centroid_mode(mocap_ctx* ctx, int mode) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (mode != MOCAP_CENTROID_REFERENCE && mode != MOCAP_CENTROID_WEIGHTED)
+    return ctx->fail(MOCAP_E_ARG, "mocap_set_centroid_mode: unknown mode %d", mode);
+  ctx->centroid_mode = mode;
   return MOCAP_OK;
 }
 

@@ -417,9 +417,12 @@ __global__ __launch_bounds__(kBlobThreads) void blob_mask_kernel(BlobArgs a) {
 #pragma unroll
   for (int j = 0; j < 16; j++) {
     const int y = 16 * wv + j;
-    const bool on = ((grey[j] + 16384) >> 15) > 51 && tx0 + px < S;
+    const int g = (grey[j] + 16384) >> 15;
+    const bool on = g > kGreyThreshold && tx0 + px < S;
     const unsigned long long w = __ballot(on);
     if (px == 0 && ty0 + y < S) mask[(size_t)(ty0 + y) * words + tx0 / 64] = w;
+    // the grey plane of the weighted centroids (null in reference mode): one 64-byte row segment per wave
+    if (a.grey && ty0 + y < S && tx0 + px < S) a.grey[((size_t)img * S + ty0 + y) * S + tx0 + px] = (uint8_t)g;
   }
 }
 
@@ -474,13 +477,21 @@ __device__ __forceinline__ uint32_t pair_key(int y, int x, int type) { return ((
 // came from (OpenCV's icvFetchContour order) -- until it crosses the NEXT horizontal pair, whose key it
 // returns.  With MOMENTS also the polygon sums of cv::moments (contourMoments) over the moves made on the
 // way, in original pixel coordinates: every move of a border lies between two consecutive pair crossings, so
-// the segment sums of a cycle's pairs add up to the contour's sums (exact integers, any order).
-template <bool MOMENTS>
-__device__ uint32_t trace_segment(const uint32_t* msk, int stride, int y0, int x0, int t0, long long* a) {
+// the segment sums of a cycle's pairs add up to the contour's sums (exact integers, any order).  With BOX the bounding box
+// {x0, y0, x1, y1} of the pixels the segment visits, both ends included, in original pixel coordinates.
+template <bool MOMENTS, bool BOX = false>
+__device__ uint32_t trace_segment(const uint32_t* msk, int stride, int y0, int x0, int t0, long long* a, int* box = nullptr) {
   int y = y0, x = x0, d = t0;
   long long a00 = 0, a10 = 0, a01 = 0;
+  int bx0 = x0, by0 = y0, bx1 = x0, by1 = y0;
   uint32_t next_key;
   for (;;) {
+    if (BOX) {
+      bx0 = min(bx0, x);
+      by0 = min(by0, y);
+      bx1 = max(bx1, x);
+      by1 = max(by1, y);
+    }
     const uint32_t nb = ring8(msk, stride, y, x);
     // scan s = d+1, d+2, ... : rotate so that bit 0 = direction d+1
     const uint32_t rot = ((nb | (nb << 8)) >> ((d + 1) & 7)) & 0xffu;
@@ -512,6 +523,12 @@ __device__ uint32_t trace_segment(const uint32_t* msk, int stride, int y0, int x
     a[0] = a00;
     a[1] = a10;
     a[2] = a01;
+  }
+  if (BOX) {
+    box[0] = bx0 - 1;
+    box[1] = by0 - 1;
+    box[2] = bx1 - 1;
+    box[3] = by1 - 1;
   }
   return next_key;
 }
@@ -679,6 +696,11 @@ __global__ __launch_bounds__(kBlobThreads) void blob_contour_kernel(BlobArgs a, 
   for (int i = p_lo; i < p_hi; i++)
     if (pmin[i] == i) L.ckey[coff++] = L.pkey[i];
   for (int c = tid; c < 3 * n_cont; c += kBlobThreads) L.ca[c] = 0;
+  // weighted centroids: the contours' bounding boxes, int32 [n_cont][4] in the link tables (dead since 2b; the launch checks
+  // that 4 N_cap <= P_cap)
+  int* cbox = (int*)L.pnext[0];
+  if (a.bbox)
+    for (int c = tid; c < 4 * n_cont; c += kBlobThreads) cbox[c] = (c & 2) ? -1 : 0x7fff;  // x0, y0 | x1, y1
   __syncthreads();
 
   // ---- 4a: polygon sums: every pair adds the sums of its segment to its contour (integer atomics: exact)
@@ -693,6 +715,19 @@ __global__ __launch_bounds__(kBlobThreads) void blob_contour_kernel(BlobArgs a, 
     if (sg[1]) atomicAdd(dst + 1, (unsigned long long)sg[1]);
     if (sg[2]) atomicAdd(dst + 2, (unsigned long long)sg[2]);
   }
+  // ---- 4a': the same walk for the boxes (weighted centroids only): every pixel of a border lies on one of its segments
+  if (a.bbox)
+    for (int i = tid; i < n_pairs; i += kBlobThreads) {
+      const uint32_t key = L.pkey[i];
+      const int y = (int)(key >> 1) / 1024, x = (int)(key >> 1) % 1024;
+      int sb[4];
+      trace_segment<false, true>(L.msk, stride, y, x, (key & 1u) ? 0 : 4, nullptr, sb);
+      int* dst = cbox + 4 * lower_bound_u32(L.ckey, n_cont, L.pkey[pmin[i]]);
+      atomicMin(dst, sb[0]);
+      atomicMin(dst + 1, sb[1]);
+      atomicMax(dst + 2, sb[2]);
+      atomicMax(dst + 3, sb[3]);
+    }
   // ---- 4b: per contour: the border met by walking left on the start row
   for (int c = tid; c < n_cont; c += kBlobThreads) {
     const uint32_t key = L.ckey[c];
@@ -749,6 +784,10 @@ __global__ __launch_bounds__(kBlobThreads) void blob_contour_kernel(BlobArgs a, 
         if (n < a.M_max) {
           out[2 * n] = (float)(int)(m10 / m00);  // int(): helpers.py:153-154
           out[2 * n + 1] = (float)(int)(m01 / m00);
+          if (a.bbox) {  // the slot's window (csrc/blob_centroid.hip overwrites the slot)
+            int16_t* b = a.bbox + ((size_t)img * a.M_max + n) * 4;
+            for (int k = 0; k < 4; k++) b[k] = (int16_t)cbox[4 * node + k];
+          }
         }
         n++;
       }
@@ -775,6 +814,7 @@ size_t blob_contour_lds_bytes(int S, int P_cap, int N_cap) {
 hipError_t launch_blob_contours(const BlobArgs& a, int P_cap, int N_cap, int only_overflowed, hipStream_t stream) {
   if (a.n_images <= 0) return hipSuccess;
   if (a.n_images > 0x7fffffffll) return hipErrorInvalidValue;
+  if (a.bbox && 4 * N_cap > P_cap) return hipErrorInvalidValue;  // the boxes borrow the link tables (4 P_cap bytes)
   const size_t lds = blob_contour_lds_bytes(a.S, P_cap, N_cap);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)blob_contour_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -117,6 +117,8 @@ struct mocap_ctx {
   DevBuf img_map, img_rot, img_mask, img_stage, img_tiles, img_lens, img_fix, img_fixidx, img_act, img_box, img_zero;
   int img_n_lt = 0;           // (lens, rotation) x tiles: entries of the fix-up index
   int blob_skip_dark = 1;     // exact early-out for tiles whose source bytes span a range <= 2 (mocap_set_blob_options)
+  int centroid_mode = 0;      // MOCAP_CENTROID_* (mocap_set_centroid_mode): 0 = the reference's int() polygon centroid
+  DevBuf img_grey, img_bbox;  // weighted mode only: grey plane [images][S][S], slot windows [images][M_max][4] int16
   DevBuf compact_ws;        // block totals of the track-compaction scan
   DevBuf frame_ws;          // wide-frame workspace: [workgroup][hit lists | group columns | ...]
   DevBuf live_stage;        // mocap_track_frame: device copy of a wide frame's blobs (narrow frames are read from pinned host memory in place)

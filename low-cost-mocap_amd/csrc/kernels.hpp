@@ -349,11 +349,17 @@ struct BlobArgs {
   int32_t* counts;         // [n_images]
   int32_t* status;         // [n_images]
   int32_t* n_contours;     // [n_images] or null
+  // grey-weighted centroids (MOCAP_CENTROID_WEIGHTED, csrc/blob_centroid.hip); both null in reference mode
+  uint8_t* grey;           // [n_images][S][S] the plane the mask thresholds; tiles a dark-tile early-out skips stay unwritten
+  int16_t* bbox;           // [n_images][M_max][4] x0, y0, x1, y1 (inclusive) of the contour behind each kept slot
 };
 hipError_t launch_blob_activity(const BlobArgs& a, hipStream_t stream);
 hipError_t launch_blob_mask(const BlobArgs& a, hipStream_t stream);
 hipError_t launch_blob_contours(const BlobArgs& a, int P_cap, int N_cap, int only_overflowed, hipStream_t stream);
 size_t blob_contour_lds_bytes(int S, int P_cap, int N_cap);
+constexpr int kCentroidReference = 0, kCentroidWeighted = 1;  // mirrored from include/mocap_core.h (MOCAP_CENTROID_*)
+constexpr int kGreyThreshold = 51;  // mask = grey > 51 (helpers.py:145-146: 255 * 0.2)
+hipError_t launch_blob_weighted_centroids(const BlobArgs& a, hipStream_t stream);
 
 // preview overlays (reference helpers.py:148,157,365), csrc/overlay_kernels.hip; bits mirrored from include/mocap_core.h (MOCAP_OVERLAY_*)
 constexpr uint32_t kOverlayContours = 1, kOverlayCentres = 2, kOverlayEpilines = 4;

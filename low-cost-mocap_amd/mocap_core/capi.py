@@ -34,6 +34,8 @@ JPEG_ST_OVERFLOW = 1      # mocap_encode_jpeg*: the image needs more than `capac
 OVERLAY_CONTOURS = 1      # mocap_set_preview_overlay: every contour pixel green (cv.drawContours, helpers.py:148)
 OVERLAY_CENTRES = 2       # ... a filled radius-1 circle on every stored centroid (cv.circle, helpers.py:157)
 OVERLAY_EPILINES = 4      # ... one epipolar line per point and later camera (drawlines, helpers.py:365)
+CENTROID_REFERENCE = 0    # mocap_set_centroid_mode: the reference's int(m10 / m00) (helpers.py:152-155), the default
+CENTROID_WEIGHTED = 1     # ... grey-weighted sub-pixel centroid over the contour's bounding box (include/mocap_core.h)
 OPT_F32_ROUNDING = 1
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
@@ -83,6 +85,7 @@ SIGNATURES = {
     "mocap_world_set_origin": (_i32, [_vp, _vp, _vp, _vp]),
     "mocap_set_image_params": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mocap_set_blob_options": (_i32, [_vp, _i32]),
+    "mocap_set_centroid_mode": (_i32, [_vp, _i32]),
     "mocap_get_undistort_map": (_i32, [_vp, _i32, _vp]),
     "mocap_find_blobs": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mocap_find_blobs_dev": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
@@ -186,6 +189,7 @@ class MocapCore:
         self.f32_rounding = True     # MOCAP_OPT_F32_ROUNDING, the library's default
         self.filter_objects_n = 0    # drone indices of the object filter (set_object_filter), 0 = off
         self.preview_overlay = 0     # OVERLAY_* bits (set_preview_overlay), the library's default
+        self.centroid_mode = CENTROID_REFERENCE   # CENTROID_* (set_centroid_mode), the library's default
 
     def close(self):
         if getattr(self, "_h", None):
@@ -446,6 +450,13 @@ class MocapCore:
     def set_blob_options(self, skip_dark_tiles=True):
         """True / 1: activity pre-pass + early-out; False / 0: every tile filtered; 2: early-out decided inside the mask pass."""
         self._check(self.lib.mocap_set_blob_options(self._h, 2 if skip_dark_tiles == 2 and skip_dark_tiles is not True else int(bool(skip_dark_tiles))))
+
+    def set_centroid_mode(self, mode):
+        """mocap_set_centroid_mode: CENTROID_REFERENCE (default, the reference's integer centroids) or CENTROID_WEIGHTED
+        (grey-weighted sub-pixel centroids; only the values in `blobs` change).  Honoured by find_blobs, find_blobs_dev,
+        find_blobs_jpeg, track_frame_images and track_frame_images_jpeg."""
+        self._check(self.lib.mocap_set_centroid_mode(self._h, int(mode)))
+        self.centroid_mode = int(mode)
 
     def undistort_map(self, camera=0):
         m = np.zeros((self.img_cols, self.img_cols), dtype=np.uint32)

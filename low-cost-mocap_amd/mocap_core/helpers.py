@@ -47,6 +47,7 @@ _state = {
     "img_key": None,         # (rows, cols, K, dist, rot) of the lens model currently uploaded
     "to_world": None,        # last Cameras.to_world_coords_matrix handed to set_to_world_coords_matrix
     "overlay": 0,            # capi.OVERLAY_* bits of set_preview_overlay: the drawings on the preview, off by default
+    "centroid": capi.CENTROID_REFERENCE,   # capi.CENTROID_* of set_centroid_mode: integer centroids by default
 }
 
 
@@ -69,11 +70,33 @@ def set_preview_overlay(flags):
         _state["overlay"] = flags
 
 
+def set_centroid_mode(mode):
+    """What camera_read_find_dots, get_frames_jpeg and camera_read_track return as image points: capi.CENTROID_REFERENCE
+    (default) = the reference's int(m10 / m00) as Python ints; capi.CENTROID_WEIGHTED = the grey-weighted sub-pixel centroid
+    of include/mocap_core.h (mocap_set_centroid_mode) as floats.  Contours, their order and the counts are the same."""
+    mode = int(mode)
+    if mode not in (capi.CENTROID_REFERENCE, capi.CENTROID_WEIGHTED):
+        raise ValueError(f"unknown centroid mode {mode}")
+    with _state["lock"]:
+        _state["centroid"] = mode
+
+
 def _apply_overlay(core):
-    """The module switch -> the context (callers hold the lock); a core handed over by set_core gets it on first use."""
+    """The module switches -> the context (callers hold the lock); a core handed over by set_core gets them on first use."""
     if getattr(core, "preview_overlay", 0) != _state["overlay"]:
         core.set_preview_overlay(_state["overlay"])
+    if getattr(core, "centroid_mode", capi.CENTROID_REFERENCE) != _state["centroid"]:
+        core.set_centroid_mode(_state["centroid"])
     return core
+
+
+def _points_list(core, blobs_c, n):
+    """One camera's stored centroids -> the list _find_dot returns: ints (helpers.py:153-154), floats in weighted mode."""
+    if not n:
+        return [[None, None]]
+    if core.centroid_mode == capi.CENTROID_WEIGHTED:
+        return blobs_c[:n].astype(np.float64).tolist()
+    return blobs_c[:n].astype(np.int64).tolist()
 
 
 def _ba_core():
@@ -336,9 +359,7 @@ def camera_read_find_dots(raw_frames, M_max=64, want_frames=True):
                               "(BLOB_ST_CAP_OVERFLOW); no centroids were produced for them")
     image_points = []
     for c in range(C):
-        n = int(res["counts"][0, c])
-        pts = res["blobs"][0, c, :n].astype(np.int64).tolist()
-        image_points.append(pts if n else [[None, None]])
+        image_points.append(_points_list(core, res["blobs"][0, c], int(res["counts"][0, c])))
     frames = [f for f in res["processed"][0]] if want_frames else [None] * C
     return frames, image_points
 
@@ -372,8 +393,7 @@ def get_frames_jpeg(raw_frames, M_max=64, quality=95):
                               "(BLOB_ST_CAP_OVERFLOW); no centroids were produced for them")
     image_points = []
     for c in range(C):
-        n = int(res["counts"][0, c])
-        image_points.append(res["blobs"][0, c, :n].astype(np.int64).tolist() if n else [[None, None]])
+        image_points.append(_points_list(core, res["blobs"][0, c], int(res["counts"][0, c])))
     return res["jpeg"][0], image_points
 
 
@@ -524,8 +544,7 @@ def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=Tr
         raise capi.MocapError(f"frame exceeds the core's limits (status {int(res['status'][0])})")
     image_points = []
     for c in range(C):
-        n = int(res["counts"][0, c])
-        image_points.append(res["blobs"][0, c, :n].astype(np.int64).tolist() if n else [[None, None]])
+        image_points.append(_points_list(core, res["blobs"][0, c], int(res["counts"][0, c])))
     tail = (res["jpeg"][0],) if want_jpeg else ()
     k = int(res["n_pts"][0])
     if k == 0:

@@ -1,4 +1,4 @@
-"""Register / spill / scratch budget of every kernel in lib/libmocap_core.so (llvm-objdump --offloading + llvm-readelf --notes);
+"""Register / spill / scratch / static LDS budget of every kernel in lib/libmocap_core.so (llvm-objdump --offloading + llvm-readelf --notes);
 no GPU needed.  usage: python scripts/kernel_budget.py [substring ...]"""
 import os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,5 +15,5 @@ for f in sorted(x for x in os.listdir(d) if "amdgcn" in x):
         if sys.argv[1:] and not any(a in dem for a in sys.argv[1:]):
             continue
         g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-        print(f"{dem[:110]:110s} vgpr {g('vgpr_count'):3d} spill {g('vgpr_spill_count'):3d} sgpr_spill {g('sgpr_spill_count'):3d} scratch {g('private_segment_fixed_size'):4d}")
+        print(f"{dem[:110]:110s} vgpr {g('vgpr_count'):3d} spill {g('vgpr_spill_count'):3d} sgpr_spill {g('sgpr_spill_count'):3d} scratch {g('private_segment_fixed_size'):4d} lds {g('group_segment_fixed_size'):6d}")
 shutil.rmtree(d)
