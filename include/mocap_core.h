@@ -445,6 +445,90 @@ int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const flo
                           int32_t* d_n_pts, int32_t* d_status, int O_max, double* d_pos, double* d_heading,
                           double* d_oerr, int32_t* d_drone, int32_t* d_n_obj);
 
+/* ---------------------------------------------------------------- rigid bodies (the core's own contract)
+ * 6-DoF poses of user-defined marker sets among a frame's 3-D points.  The reference's only object model is locate_objects
+ * (two hard-coded 3-LED drones, a position and a folded yaw, nothing when one LED is hidden); this stage is opt-in and the
+ * core's own: with no bodies registered nothing that existed before changes.
+ *
+ * mocap_set_rigid_bodies: registers B <= MOCAP_RB_MAX_BODIES bodies of 3 .. MOCAP_RB_MAX_MARKERS markers each.
+ *   n_markers [B], markers [B][8][3] f64 body coordinates (rows >= n_markers[b] are not read): host pointers, copied
+ *   tol      metres, > 0: gate on every pairwise distance
+ *   max_rms  metres, > 0: a fit whose residual is larger is rejected
+ *   work_cap gate-passing extensions one (frame, body) search may make; 0 = MOCAP_RB_DEFAULT_WORK_CAP; < 0 is MOCAP_E_ARG
+ * B = 0 clears the registration.  MOCAP_E_ARG, and NOTHING changes (the previous registration stays in force), for: B > 8; a
+ * body with fewer than 3 or more than 8 markers; a non-finite coordinate; tol or max_rms not > 0; two markers of one body
+ * less than 2 tol apart (D < 2 tol); a body whose full marker set is not posable.
+ *   D(p, q) = sqrt(dx dx + dy dy + dz dz), the sum taken in x, y, z order, no fused operation; d_ij = D(q_i, q_j) on the model.
+ *   A marker subset is POSABLE iff it has >= 3 markers and holds a triple (i < j < k) with
+ *     |(q_j - q_i) x (q_k - q_i)| >= 0.1 |q_j - q_i| |q_k - q_i|
+ *   (u = q_j - q_i, v = q_k - q_i, cross = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x), the three norms as D, the
+ *   right side as (0.1 |u|) |v|).  The host tabulates this once per body as a 256-bit mask over the subsets; the kernel looks it up.
+ *
+ * Result per (frame, body).  A frame's points are the first n_pts[f] of its K_max slots; K_max <= MOCAP_RB_MAX_POINTS (64), more
+ * is MOCAP_E_ARG; n_pts[f] outside 0 .. K_max counts as 0 (the "no valid slot" rule of mocap_locate_objects).  Bodies are taken in
+ * index order; the points claimed by an earlier FOUND body are removed first.  A point with a non-finite coordinate passes no gate.
+ *   An ASSIGNMENT is a tuple a[0..N), a[m] = a point index or -1, assigned points distinct, the assigned marker subset posable,
+ *   every assigned pair with | D(p_a[i], p_a[j]) - d_ij | < tol (strict).
+ *   score = sum over assigned pairs i < j of (D - d_ij)^2, added in (i, j) lexicographic order, unfused.
+ *   The winner is the lexicographic minimum of (-number assigned, score, tuple), tuples compared element-wise with -1 below every
+ *   index: the optimum over the whole search space, independent of the order of evaluation.  No assignment: not found, status 0.
+ *   (An exact duplicate of a point is a valid alternative with an equal score: the smaller index wins.  A body with a symmetry
+ *   has several equally good labellings: the one returned is deterministic but arbitrary.)
+ * Pose of the winner: centroids qb, pb of the assigned model points and their world points; S = sum (q_i - qb)(p_i - pb)^T; Horn's
+ * symmetric 4 x 4 matrix of S; its dominant eigenvector by cyclic Jacobi (accuracy does not rest on an eigen-gap) is the unit
+ * quaternion (w, x, y, z) of R; t = pb - R qb; rms = sqrt(mean |R q_i + t - p_i|^2), evaluated in centred coordinates.  R comes
+ * from a quaternion, so it is always proper: a mirrored match shows as a large rms.
+ *   rms > max_rms: not found, status MOCAP_RB_ST_RMS, nothing claimed.  There is NO second-best search: the body stays unfound for
+ *   this frame even if another assignment would have fitted.
+ * Work cap: the search is exponential on adversarial input (a lattice of points at the model's own spacings).  It is a depth-first
+ * walk over the markers in index order; at marker m the candidate points are those still free that pass the gate against every
+ * marker assigned so far, taken in ascending index, then "m unassigned".  A branch is left when the markers assigned plus those
+ * still to come cannot reach 3, or cannot reach the largest count of a complete assignment this same search has seen; there is no
+ * other pruning.  Every candidate point the walk puts a marker on is one EXTENSION.  The counter is per (frame, body) and starts
+ * at zero for each; when it would exceed work_cap the search stops: status MOCAP_RB_ST_WORK_CAP, not found, nothing claimed, later
+ * bodies still see the points.  Flag and outputs are a function of the frame's points and the registration alone.
+ *
+ * Outputs, all [F][B_max] (B_max = body slots per frame, >= the registered bodies, else MOCAP_E_ARG); the entries of a body that
+ * is not found, and the slots beyond the registered bodies, are ZERO-filled -- `assign` included: read it only where found = 1.
+ *   found i32    1 = found                      n_used i32   assigned markers
+ *   assign [8] i8  point index per marker, -1 = unassigned (markers >= N: -1)
+ *   R [9] f64 row-major, t [3] f64: world = R body + t      rms f64      score f64 (the winner's)
+ *   status i32   0 | MOCAP_RB_ST_RMS | MOCAP_RB_ST_WORK_CAP
+ * Out of scope: identity over time, filtering of the poses, a second-best search, more than 64 points per frame. */
+#define MOCAP_RB_MAX_BODIES 8
+#define MOCAP_RB_MAX_MARKERS 8
+#define MOCAP_RB_MAX_POINTS 64
+#define MOCAP_RB_DEFAULT_WORK_CAP 65536
+enum {
+  MOCAP_RB_ST_RMS = 1,      /* the winner's fit has rms > max_rms: not found */
+  MOCAP_RB_ST_WORK_CAP = 2  /* the search needed more than work_cap extensions: not found */
+};
+int mocap_set_rigid_bodies(mocap_ctx* ctx, int B, const int32_t* n_markers, const double* markers, double tol, double max_rms,
+                           int64_t work_cap);
+/* xyz [F][K_max][3], n_pts [F]: as the frame path writes them (mocap_match_triangulate's xyz and n_out).  One wave per frame,
+ * lane = point.  The "_dev" form enqueues on the context's stream (for batches); the host form uploads, runs and downloads. */
+int mocap_locate_rigid_bodies(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int32_t* n_pts, int B_max,
+                              int32_t* found, int32_t* n_used, int8_t* assign, double* R, double* t, double* rms, double* score,
+                              int32_t* status);
+int mocap_locate_rigid_bodies_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts,
+                                  int B_max, int32_t* d_found, int32_t* d_n_used, int8_t* d_assign, double* d_R, double* d_t,
+                                  double* d_rms, double* d_score, int32_t* d_status);
+/* mocap_track_frame / mocap_track_frame_dev with the body outputs appended (every other argument and every shared output as
+ * there, bit for bit).  The host form queues the rigid-body kernel behind the export; it reads the frame's points where the frame
+ * path left them and writes into the same pinned block as the rest of the payload: still one enqueue and one event wait.  With
+ * no bodies registered the body outputs are zero-filled (and K_max may exceed 64). */
+int mocap_track_frame_bodies(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                             double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr, int32_t* n_pts,
+                             int32_t* status, int O_max, double* pos, double* heading, double* oerr, int32_t* drone,
+                             int32_t* n_obj, int B_max, int32_t* rb_found, int32_t* rb_n_used, int8_t* rb_assign, double* rb_R,
+                             double* rb_t, double* rb_rms, double* rb_score, int32_t* rb_status);
+int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs, const int32_t* d_counts,
+                                 double gate_px, int K_max, int64_t G_cap, double* d_xyz, double* d_err, int16_t* d_corr,
+                                 int32_t* d_n_pts, int32_t* d_status, int O_max, double* d_pos, double* d_heading,
+                                 double* d_oerr, int32_t* d_drone, int32_t* d_n_obj, int B_max, int32_t* d_rb_found,
+                                 int32_t* d_rb_n_used, int8_t* d_rb_assign, double* d_rb_R, double* d_rb_t, double* d_rb_rms,
+                                 double* d_rb_score, int32_t* d_rb_status);
+
 /* ---------------------------------------------------------------- object filter
  * `filtered_objects` of the live loop (helpers.py:109, self.kalman_filter.predict_location(objects)): per drone index a
  * cv.KalmanFilter(9, 6) in float32 (constant acceleration, measurement = position and finite-difference velocity, nearest

@@ -144,6 +144,11 @@ struct mocap_ctx {
   DevBuf jpeg_stage;        // host-buffer entry points: frames in, [F][capacity] streams, sizes and status out
   uint32_t preview_overlay = 0;  // MOCAP_OVERLAY_* bits (mocap_set_preview_overlay): drawings on the processed frames, off by default
   DevBuf overlay_stage;     // mocap_draw_epilines: pictures | blobs | counts | corr | n_pts | status
+  // rigid bodies (mocap_set_rigid_bodies, csrc/rigid_body_capi.hip): rb_B == 0 = none registered
+  int rb_B = 0;
+  double rb_tol = 0.0, rb_max_rms = 0.0;
+  long long rb_work_cap = 0;
+  DevBuf rb_models;         // RigidBodyModel [rb_B]: markers, pair distances and the posability mask of every body
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);
@@ -187,3 +192,17 @@ struct FilterIO {
 int filter_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int O_max, const FilterIO& io);
 int filter_dev_locked(mocap_ctx* ctx, int64_t n_frames, int O_max, const double* d_pos, const double* d_heading,
                       const int32_t* d_drone, const int32_t* d_n_obj, const FilterIO& io);
+// rigid bodies over the frame path's points (rigid_body_capi.hip); every pointer device-accessible, arrays [F][B_max]; `who` names the entry point
+struct BodiesIO {
+  int B_max;        // body slots per frame (>= the registered bodies; the slots beyond them are zero-filled)
+  int32_t* found;
+  int32_t* n_used;
+  int8_t* assign;   // [F][B_max][8]
+  double* R;        // [F][B_max][9]
+  double* t;        // [F][B_max][3]
+  double* rms;
+  double* score;
+  int32_t* status;
+};
+int bodies_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const BodiesIO& io);
+int bodies_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const BodiesIO& io);

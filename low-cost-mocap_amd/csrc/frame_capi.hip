@@ -735,8 +735,9 @@ struct TrackOut {
 // images != null: raw frames [F][C][rows][cols][3] (host); else b.blobs / b.counts (host) are the input
 // fo != null (mocap_track_frame_filtered): host time stamps in, the object filter's outputs out -- its two kernels are queued
 // behind the export and write into the same pinned block, the call still waits for one event
+// bo != null (mocap_track_frame_bodies): the rigid-body kernel is queued behind the export in the same way
 int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o,
-                 const FilterIO* fo = nullptr, const JpegOut* jo = nullptr) {
+                 const FilterIO* fo = nullptr, const JpegOut* jo = nullptr, const BodiesIO* bo = nullptr) {
   const int64_t n_frames = b.n_frames;
   const int M_max = b.M_max;
   if (!ctx->C) return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_cameras has not been called");
@@ -753,6 +754,10 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (images && (!o.blobs || !o.counts || !o.blob_status)) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images: null blob buffer");
   if (fo) {
     const int rc = filter_check(ctx, "mocap_track_frame_filtered", n_frames, o.O_max, *fo);
+    if (rc) return rc;
+  }
+  if (bo) {
+    const int rc = bodies_check(ctx, "mocap_track_frame_bodies", n_frames, K_max, *bo);
     if (rc) return rc;
   }
   if (jo) {  // the preview stream: the processed frames of the blob stage as one JPEG per frame set
@@ -773,6 +778,8 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   FrameOut h;
   double *h_pos, *h_head, *h_oerr;
   FilterIO hf{};
+  const size_t FB = bo ? F * (size_t)bo->B_max : 0;
+  BodiesIO hb{bo ? bo->B_max : 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   auto lay_host = [&](void* base) {
     Carver c(base);
     h_blobs = c.take<float>(F * C * M_max * 2);
@@ -799,6 +806,16 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     if (jo) {
       h_jpeg = c.take<uint8_t>(F * j_stride);
       h_jsize = c.take<int64_t>(F);
+    }
+    if (bo) {
+      hb.found = c.take<int32_t>(FB);
+      hb.n_used = c.take<int32_t>(FB);
+      hb.assign = c.take<int8_t>(FB * kRbMaxMarkers);
+      hb.R = c.take<double>(FB * 9);
+      hb.t = c.take<double>(FB * 3);
+      hb.rms = c.take<double>(FB);
+      hb.score = c.take<double>(FB);
+      hb.status = c.take<int32_t>(FB);
     }
     return c.off;
   };
@@ -911,6 +928,10 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     rc = resubmit_dev_locked(ctx, in, K_max, d, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, launch_track_export(la, ea, ctx->stream));
+    if (bo) {  // the frame's points where the frame path left them (device memory), the bodies into the pinned block
+      rc = bodies_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hb);
+      if (rc) return rc;
+    }
     if (fo) {
       memcpy(const_cast<double*>(hf.t), fo->t, sizeof(double) * F);
       rc = filter_dev_locked(ctx, n_frames, O, h_pos, h_head, h_drone, h_nobj, hf);
@@ -944,6 +965,16 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     memcpy(fo->fvel, hf.fvel, sizeof(float) * FD * 3);
     memcpy(fo->fheading, hf.fheading, sizeof(double) * FD);
     memcpy(fo->chosen, hf.chosen, sizeof(int32_t) * FD);
+  }
+  if (bo && FB) {
+    memcpy(bo->found, hb.found, sizeof(int32_t) * FB);
+    memcpy(bo->n_used, hb.n_used, sizeof(int32_t) * FB);
+    memcpy(bo->assign, hb.assign, FB * kRbMaxMarkers);
+    memcpy(bo->R, hb.R, sizeof(double) * FB * 9);
+    memcpy(bo->t, hb.t, sizeof(double) * FB * 3);
+    memcpy(bo->rms, hb.rms, sizeof(double) * FB);
+    memcpy(bo->score, hb.score, sizeof(double) * FB);
+    memcpy(bo->status, hb.status, sizeof(int32_t) * FB);
   }
   for (size_t f = 0; f < F && jo; f++) {
     jo->size[f] = h_jsize[f];
@@ -1014,6 +1045,48 @@ extern "C" int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max
     rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
     if (rc) return rc;
   }
+  return ctx->mark_enqueued();
+}
+
+// mocap_track_frame / mocap_track_frame_dev with the rigid-body stage (csrc/rigid_body.hip) behind the object search
+extern "C" int mocap_track_frame_bodies(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                                        double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr,
+                                        int32_t* n_pts, int32_t* status, int O_max, double* pos, double* heading, double* oerr,
+                                        int32_t* drone, int32_t* n_obj, int B_max, int32_t* rb_found, int32_t* rb_n_used,
+                                        int8_t* rb_assign, double* rb_R, double* rb_t, double* rb_rms, double* rb_score,
+                                        int32_t* rb_status) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
+  const BodiesIO bo{B_max, rb_found, rb_n_used, rb_assign, rb_R, rb_t, rb_rms, rb_score, rb_status};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, nullptr, nullptr, &bo);
+}
+
+extern "C" int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
+                                            const int32_t* d_counts, double gate_px, int K_max, int64_t G_cap, double* d_xyz,
+                                            double* d_err, int16_t* d_corr, int32_t* d_n_pts, int32_t* d_status, int O_max,
+                                            double* d_pos, double* d_heading, double* d_oerr, int32_t* d_drone, int32_t* d_n_obj,
+                                            int B_max, int32_t* d_rb_found, int32_t* d_rb_n_used, int8_t* d_rb_assign,
+                                            double* d_rb_R, double* d_rb_t, double* d_rb_rms, double* d_rb_score,
+                                            int32_t* d_rb_status) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const BodiesIO bo{B_max, d_rb_found, d_rb_n_used, d_rb_assign, d_rb_R, d_rb_t, d_rb_rms, d_rb_score, d_rb_status};
+  int rc = bodies_check(ctx, "mocap_track_frame_bodies_dev", n_frames, K_max, bo);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
+  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
+  rc = match_dev_locked(ctx, b, K_max, G_cap, o);
+  if (rc) return rc;
+  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
+  if (rc) return rc;
+  if (O_max > 0) {
+    rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
+    if (rc) return rc;
+  }
+  rc = bodies_dev_locked(ctx, n_frames, K_max, d_xyz, d_n_pts, bo);
+  if (rc) return rc;
   return ctx->mark_enqueued();
 }
 

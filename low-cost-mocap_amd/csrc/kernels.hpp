@@ -175,6 +175,38 @@ struct TrackExportArgs {
 };
 hipError_t launch_track_export(const LocateArgs& a, const TrackExportArgs& e, hipStream_t stream);
 
+// rigid bodies (the core's own contract, include/mocap_core.h "rigid bodies"), csrc/rigid_body.hip: per (frame, body) the
+// optimal assignment of body markers to the frame's points, then the least-squares pose of the assigned markers
+constexpr int kRbMaxBodies = 8, kRbMaxMarkers = 8, kRbMaxPoints = 64, kRbPairs = 28;  // mirrored from include/mocap_core.h (MOCAP_RB_*)
+constexpr int RB_ST_RMS_ = 1, RB_ST_WORK_CAP_ = 2;
+constexpr long long kRbDefaultWorkCap = 65536;
+// pair (i, j), i < j, of a body's markers: the lexicographic order the score is summed in
+__host__ __device__ constexpr int rb_pair(int i, int j) { return i * (2 * kRbMaxMarkers - i - 1) / 2 + (j - i - 1); }
+struct RigidBodyModel {       // one registered body, as the host tabulates it (device memory, read-only to the kernel)
+  int32_t n, pad;             // markers
+  double q[kRbMaxMarkers][3]; // body coordinates
+  double d[kRbPairs];         // d_ij = sqrt(dx dx + dy dy + dz dz) at rb_pair(i, j)
+  unsigned long long posable[4];  // bit s: the marker subset s (bit m = marker m) is posable
+};
+struct RigidBodyArgs {
+  int64_t n_frames;
+  int K_max, B, B_max;        // point slots per frame (<= 64); registered bodies; body slots per frame of the outputs (>= B)
+  double tol, max_rms;
+  long long work_cap;
+  const RigidBodyModel* models;  // [B]
+  const double* xyz;          // [F][K_max][3]
+  const int32_t* n_pts;       // [F]
+  int32_t* found;             // [F][B_max]
+  int32_t* n_used;            // [F][B_max]
+  int8_t* assign;             // [F][B_max][8]
+  double* R;                  // [F][B_max][9]
+  double* t;                  // [F][B_max][3]
+  double* rms;                // [F][B_max]
+  double* score;              // [F][B_max]
+  int32_t* status;            // [F][B_max]
+};
+hipError_t launch_rigid_bodies(const RigidBodyArgs& a, hipStream_t stream);
+
 // object filter over the locator's output (reference KalmanFilter.py + LowPassFilter.py: the `filtered_objects` of
 // helpers.py:109), csrc/object_filter.hip.  The state of the recurrence lives in one device record per context.
 constexpr int kObjFilterMaxObjects = 8, kObjFilterMaxTaps = 16, kObjFilterMaxBuffer = 1024, kObjFilterMaxSlots = 64;

@@ -36,6 +36,10 @@ OVERLAY_CENTRES = 2       # ... a filled radius-1 circle on every stored centroi
 OVERLAY_EPILINES = 4      # ... one epipolar line per point and later camera (drawlines, helpers.py:365)
 CENTROID_REFERENCE = 0    # mocap_set_centroid_mode: the reference's int(m10 / m00) (helpers.py:152-155), the default
 CENTROID_WEIGHTED = 1     # ... grey-weighted sub-pixel centroid over the contour's bounding box (include/mocap_core.h)
+RB_MAX_BODIES, RB_MAX_MARKERS, RB_MAX_POINTS = 8, 8, 64   # mocap_set_rigid_bodies: bodies, markers per body, points per frame
+RB_DEFAULT_WORK_CAP = 65536   # ... extensions one (frame, body) search may make when work_cap = 0
+RB_ST_RMS = 1             # per (frame, body): the best assignment's fit has rms > max_rms (not found)
+RB_ST_WORK_CAP = 2        # ... the search needed more than work_cap extensions (not found)
 OPT_F32_ROUNDING = 1
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
@@ -69,6 +73,13 @@ SIGNATURES = {
     "mocap_track_frame_images": (_i32, [_vp, _i64, _vp, _i32, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                         _vp, _vp, _vp]),
     "mocap_track_frame_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_set_rigid_bodies": (_i32, [_vp, _i32, _vp, _vp, _dbl, _dbl, _i64]),
+    "mocap_locate_rigid_bodies": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_locate_rigid_bodies_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_bodies": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                        _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_bodies_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                            _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_object_filter": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _dbl, _dbl]),
     "mocap_reset_object_filter": (_i32, [_vp, _dbl]),
     "mocap_filter_objects": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -190,6 +201,7 @@ class MocapCore:
         self.filter_objects_n = 0    # drone indices of the object filter (set_object_filter), 0 = off
         self.preview_overlay = 0     # OVERLAY_* bits (set_preview_overlay), the library's default
         self.centroid_mode = CENTROID_REFERENCE   # CENTROID_* (set_centroid_mode), the library's default
+        self.rigid_bodies_n = 0      # bodies registered by set_rigid_bodies, 0 = none
 
     def close(self):
         if getattr(self, "_h", None):
@@ -635,6 +647,76 @@ class MocapCore:
 
     def world_set_origin(self, to_world, point):
         return world_set_origin(to_world, point, ctx=self._h, lib=self.lib)
+
+    # ------------------------------------------------------------------ rigid bodies (6-DoF poses of registered marker sets)
+    def set_rigid_bodies(self, markers, tol=0.01, max_rms=0.005, work_cap=0):
+        """mocap_set_rigid_bodies: `markers` = one [N][3] array of body coordinates per body (3 <= N <= 8, at most 8 bodies;
+        an empty list clears the registration).  tol, max_rms in metres; work_cap 0 = RB_DEFAULT_WORK_CAP.  A registration the
+        core refuses (MOCAP_E_ARG) raises and leaves the previous one in force."""
+        B = len(markers)
+        n = np.zeros(max(B, 1), dtype=np.int32)
+        q = np.zeros((max(B, 1), RB_MAX_MARKERS, 3))
+        for b, m in enumerate(markers[:RB_MAX_BODIES]):
+            m = np.asarray(m, dtype=np.float64).reshape(-1, 3)
+            n[b] = m.shape[0]
+            q[b, :min(m.shape[0], RB_MAX_MARKERS)] = m[:RB_MAX_MARKERS]
+        self._check(self.lib.mocap_set_rigid_bodies(self._h, B, _p(n), _p(q), float(tol), float(max_rms), int(work_cap)))
+        self.rigid_bodies_n = B
+
+    @staticmethod
+    def _body_outputs(F, B_max):
+        return {"found": np.zeros((F, B_max), dtype=np.int32), "n_used": np.zeros((F, B_max), dtype=np.int32),
+                "assign": np.zeros((F, B_max, RB_MAX_MARKERS), dtype=np.int8), "R": np.zeros((F, B_max, 3, 3)),
+                "t": np.zeros((F, B_max, 3)), "rms": np.zeros((F, B_max)), "score": np.zeros((F, B_max)),
+                "rb_status": np.zeros((F, B_max), dtype=np.int32)}
+
+    @staticmethod
+    def _body_ptrs(o):
+        return [_p(o[k]) for k in ("found", "n_used", "assign", "R", "t", "rms", "score", "rb_status")]
+
+    def locate_rigid_bodies(self, xyz, n_pts, B_max=None):
+        """mocap_locate_rigid_bodies over host arrays xyz [F][K_max][3] (K_max <= 64), n_pts [F] -> {"found", "n_used" [F][B],
+        "assign" int8 [F][B][8], "R" [F][B][3][3], "t" [F][B][3], "rms", "score" [F][B], "rb_status" [F][B]}; the entries of a
+        body that was not found are zero.  B_max: body slots per frame, default = the registered bodies."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        F, K_max, _ = xyz.shape
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        B_max = self.rigid_bodies_n if B_max is None else int(B_max)
+        o = self._body_outputs(F, B_max)
+        self._check(self.lib.mocap_locate_rigid_bodies(self._h, F, K_max, _p(xyz), _p(n_pts), B_max, *self._body_ptrs(o)))
+        return o
+
+    def locate_rigid_bodies_dev(self, n_frames, K_max, d_xyz, d_n_pts, B_max, d_found, d_n_used, d_assign, d_R, d_t, d_rms,
+                                d_score, d_status):
+        self._check(self.lib.mocap_locate_rigid_bodies_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_n_pts), int(B_max),
+                                                           _vp(d_found), _vp(d_n_used), _vp(d_assign), _vp(d_R), _vp(d_t),
+                                                           _vp(d_rms), _vp(d_score), _vp(d_status)))
+
+    def track_frame_bodies(self, blobs, counts, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8, B_max=None):
+        """mocap_track_frame_bodies: track_frame with the rigid-body stage behind the object search; the same dict plus the
+        keys of locate_rigid_bodies.  With bodies registered a frame holds at most 64 points (K_max <= 64)."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        F, C, M, _ = blobs.shape
+        assert C == self.C and counts.shape == (F, C)
+        K_max = min(C * M, 64) if K_max is None else int(K_max)
+        B_max = self.rigid_bodies_n if B_max is None else int(B_max)
+        o = self._track_outputs(F, K_max, O_max)
+        o.update(self._body_outputs(F, B_max))
+        self._check(self.lib.mocap_track_frame_bodies(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
+                                                      _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
+                                                      int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
+                                                      _p(o["droneIndex"]), _p(o["n_obj"]), B_max, *self._body_ptrs(o)))
+        return o
+
+    def track_frame_bodies_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
+                               d_status, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj, B_max, d_found, d_n_used, d_assign,
+                               d_R, d_t, d_rms, d_score, d_rb_status):
+        self._check(self.lib.mocap_track_frame_bodies_dev(
+            self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), float(gate_px), int(K_max), int(G_cap), _vp(d_xyz),
+            _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
+            _vp(d_drone or 0), _vp(d_n_obj or 0), int(B_max), _vp(d_found), _vp(d_n_used), _vp(d_assign), _vp(d_R), _vp(d_t),
+            _vp(d_rms), _vp(d_score), _vp(d_rb_status)))
 
     # ------------------------------------------------------------------ object filter (`filtered_objects`)
     def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):

@@ -48,6 +48,7 @@ _state = {
     "to_world": None,        # last Cameras.to_world_coords_matrix handed to set_to_world_coords_matrix
     "overlay": 0,            # capi.OVERLAY_* bits of set_preview_overlay: the drawings on the preview, off by default
     "centroid": capi.CENTROID_REFERENCE,   # capi.CENTROID_* of set_centroid_mode: integer centroids by default
+    "bodies": None,          # set_rigid_bodies: (names, marker arrays, tol, max_rms, work_cap), None = no body registered
 }
 
 
@@ -448,6 +449,71 @@ def track_frame(image_points, camera_poses, is_locating_objects=True, O_max=8):
     return res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else [])
 
 
+def set_rigid_bodies(bodies, tol=0.01, max_rms=0.005, work_cap=0):
+    """Registers the rigid bodies the core looks for (mocap_set_rigid_bodies, include/mocap_core.h): `bodies` = a list of
+    {"name": str, "markers": [[x, y, z], ...]} in body coordinates, 3 .. 8 markers each, at most 8 bodies; an empty list
+    switches the stage off.  tol (gate on every marker-to-marker distance) and max_rms (largest accepted residual of the fit)
+    are in the unit of the object points.  A registration the core refuses raises capi.MocapError and changes nothing."""
+    names = [str(b["name"]) for b in bodies]
+    markers = [np.asarray(b["markers"], dtype=np.float64).reshape(-1, 3) for b in bodies]
+    with _state["lock"]:
+        get_core().set_rigid_bodies(markers, tol=tol, max_rms=max_rms, work_cap=work_cap)
+        _state["bodies"] = (names, markers, float(tol), float(max_rms), int(work_cap)) if bodies else None
+
+
+def _bodies_core():
+    """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
+    core = get_core()
+    reg = _state["bodies"]
+    if reg is not None and getattr(core, "rigid_bodies_n", 0) != len(reg[0]):
+        core.set_rigid_bodies(reg[1], tol=reg[2], max_rms=reg[3], work_cap=reg[4])
+    return core
+
+
+def _bodies_list(res, f=0):
+    """One frame's found bodies: {"name", "R" 3x3, "t" [3], "rms", "markers": point index per marker, -1 = not seen}."""
+    reg = _state["bodies"]
+    if reg is None:
+        return []
+    return [{"name": reg[0][b], "R": res["R"][f, b].copy(), "t": res["t"][f, b].copy(), "rms": float(res["rms"][f, b]),
+             "markers": res["assign"][f, b, :reg[1][b].shape[0]].astype(int).tolist()}
+            for b in range(len(reg[0])) if res["found"][f, b]]
+
+
+def locate_rigid_bodies(object_points):
+    """The registered bodies among one frame's object points (at most 64): list of {"name", "R", "t", "rms", "markers"},
+    world = R body + t, bodies that are not found left out."""
+    P = np.asarray(object_points, dtype=np.float64).reshape(-1, 3)
+    if P.shape[0] == 0 or _state["bodies"] is None:
+        return []
+    with _state["lock"]:
+        res = _bodies_core().locate_rigid_bodies(P[None], [P.shape[0]])
+    return _bodies_list(res)
+
+
+def track_frame_bodies(image_points, camera_poses, is_locating_objects=True, O_max=8):
+    """track_frame with the rigid-body stage in the same core call.  Returns (errors, object_points, objects, bodies):
+    track_frame's three values and the list locate_rigid_bodies returns for the frame's object points; hand `bodies` to
+    object_points_payload(..., bodies=bodies)."""
+    for image_points_i in image_points:
+        try:
+            image_points_i.remove([None, None])
+        except Exception:
+            pass
+    with _state["lock"]:
+        core = _upload_cameras(camera_poses)
+        _bodies_core()
+        blobs, counts, _ = pack_frame(image_points)
+        res = core.track_frame_bodies(blobs, counts, gate_px=5.0, O_max=O_max if is_locating_objects else 0)
+    if int(res["status"][0]) != 0:
+        raise capi.MocapError(_status_message(int(res["status"][0])))
+    k = int(res["n_pts"][0])
+    if k == 0:
+        return np.array([]), np.array([]), [], []
+    return (res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else []),
+            _bodies_list(res))
+
+
 def _filtered_list(res, f=0):
     """One frame's `filtered_objects` as the reference builds it (KalmanFilter.py:93-98): drones in ascending index, absent ones left out."""
     return [{"pos": res["fpos"][f, d].copy(), "vel": res["fvel"][f, d].copy(), "heading": float(res["fheading"][f, d]),
@@ -553,18 +619,22 @@ def camera_read_track(raw_frames, camera_poses, M_max=16, is_locating_objects=Tr
             _objects_list(res) if is_locating_objects else []) + tail
 
 
-def object_points_payload(errors, object_points, objects, filtered_objects=()):
+def object_points_payload(errors, object_points, objects, filtered_objects=(), bodies=None):
     """The dict the reference emits as the `object-points` socket event (helpers.py:128-133), built from what
     track_frame() / camera_read_track() / track_frame_filtered() return.  `filtered_objects` is KalmanFilter.predict_location's
     list (or track_frame_filtered's fourth value); its "pos" and "vel" arrays are .tolist()-ed like helpers.py:124-126 does,
-    entries a caller has already converted pass through."""
+    entries a caller has already converted pass through.  `bodies` (track_frame_bodies' fourth value; the reference has no such
+    field) adds a "bodies" list of {"name", "R", "t", "rms", "markers"}; without it the dict is the reference's."""
     as_json = lambda d: {k: (v.tolist() if isinstance(v, np.ndarray) else v) for (k, v) in d.items()}   # noqa: E731
-    return {
+    payload = {
         "object_points": np.asarray(object_points).tolist(),
         "errors": np.asarray(errors).tolist(),
         "objects": [as_json(obj) for obj in objects],
         "filtered_objects": [as_json(obj) for obj in filtered_objects],
     }
+    if bodies is not None:
+        payload["bodies"] = [as_json(body) for body in bodies]
+    return payload
 
 
 def _status_message(st):
