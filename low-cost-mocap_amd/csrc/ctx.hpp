@@ -121,6 +121,8 @@ struct mocap_ctx {
   DevBuf img_grey, img_bbox;  // weighted mode only: grey plane [images][S][S], slot windows [images][M_max][4] int16
   DevBuf compact_ws;        // block totals of the track-compaction scan
   DevBuf frame_ws;          // wide-frame workspace: [workgroup][hit lists | group columns | ...]
+  DevBuf bb_ws;             // search kernels (csrc/frame_bb.hip): the winners' records, [num_cus * kBBMaxWgPerCu][frame_bb_ws_bytes] -- one size for the
+                            // context's life, a buffer of its own: no other launch's reserve() ever frees it behind a queued search pass
   DevBuf live_stage;        // mocap_track_frame: device copy of a wide frame's blobs (narrow frames are read from pinned host memory in place)
   DevBuf resub;             // device-side re-submit: counters | frame list | gathered inputs | second-pass outputs
   DevBuf resub_ctr;         // ... its two alternating counters (never re-allocated while a call is in flight)

@@ -1,7 +1,7 @@
 // frame_bb.hip -- the frame path for the realistic rigs (plain intrinsics -- one matrix for all cameras, or one per camera
 // as a calibration gives them: frame_bb_calib_kernel, BBState's PERK --, <= 16 cameras, <= 64 blobs per
 // camera, <= 255 roots): epipolar correspondence search + EXACT branch-and-bound selection, one 256-lane workgroup per
-// frame, persistent, everything between the blob arrays in and the kept points out in LDS.  Replaces
+// frame, persistent, everything between the blob arrays in and the kept points out in LDS (but the winners' points: phase E).  Replaces
 //   find_point_correspondance_and_object_points   (reference computer_code/api/helpers.py:339-421)
 // like frame_kernel.hip does (which keeps the general case: intrinsics that are not plain, wide frames, tiny frames, and
 // the exhaustive walk every result of this file is tested against, MOCAP_EVAL_BB=0).
@@ -35,7 +35,8 @@
 //   D   branch and bound over blocks of the Cartesian product: seeds, block tests, evaluation of the
 //       survivors' candidates spread over all lanes; per (wave, root) slot = lexicographic minimum of (error bits,
 //       candidate index) = np.argmin's first minimum (helpers.py:418) whatever the evaluation order
-//   E   one lane per kept root: merge the four waves' slots, decode the winning group, write xyz / err / corr
+//   E   one lane per kept root: merge the four waves' slots, fetch the winning slot's point (left in the workgroup's L2-resident
+//       workspace by the lane that evaluated it), decode the winning group, write xyz / err / corr
 #include "mocap_device.hpp"
 #include "kernels.hpp"
 #include <cstdlib>
@@ -1136,6 +1137,17 @@ struct BBState {
             wave_lds_sync();
             if (holder) atomicMin(&slot_g[ss], gword);
             wave_lds_sync();
+            // the lane that holds the slot after this round -- its error AND its index stood -- leaves the candidate's point in
+            // the slot's record of the workspace (phase E reads the winning slot's); every change of a slot's (key, index) pair
+            // comes with the store of the lane that made it, a cut-short or NaN candidate's included (it can be all a root has)
+            // (a slot can be re-won by another lane of this wave in a later pass of this loop, with no barrier in between: the two
+            // stores go to one address from one wave, and a wave's stores to an address reach L2 in the order it issued them)
+            if (holder && slot_g[ss] == gword) {
+              double* rec = winner_rec(ss);
+              rec[0] = X[0];
+              rec[1] = X[1];
+              rec[2] = X[2];
+            }
           }
         }
         __syncthreads();  // every lane is done with the records: new ones may be queued (through the other counter)
@@ -1210,14 +1222,16 @@ struct BBState {
       if (do_push) push_block(r, gh, pk);
       __syncthreads();
     }
+    wait_own_stores();  // the winners' records have reached L2 (stores are acknowledged from there) before any lane reads one
     __syncthreads();
   }
 
-  // winner of root r: the (wave, root) slots merged
-  __device__ bool root_winner(int r, double& eb, uint32_t& gb) const {
-    if (!gcnt[r]) return false;
-    unsigned long long kb = ~0ull;
-    uint32_t gw = 0xFFFFFFFFu;
+  // winner of root r (one with candidates): the (wave, root) slots merged -- its key (error bits), index word and the wave
+  // whose slot it is (that slot's record holds the point); false: no candidate of the root was delivered
+  __device__ __forceinline__ bool root_winner(int r, unsigned long long& kb, uint32_t& gw, int& wb) const {
+    kb = ~0ull;
+    gw = 0xFFFFFFFFu;
+    wb = 0;
     for (int w = 0; w < W; w++) {
       const int s = w * RS + r;
       const unsigned long long k = slot_key[s];
@@ -1225,31 +1239,45 @@ struct BBState {
       if (k < kb || (k == kb && g < gw)) {
         kb = k;
         gw = g;
+        wb = w;
       }
     }
-    if (kb == ~0ull) return false;
-    gb = gw >> 1;
-    eb = kb != kInfBits ? __longlong_as_double((long long)kb)
-                        : ((gw & 1u) ? __longlong_as_double(0x7ff8000000000000ll) : __builtin_huge_val());
-    return true;
+    return kb != ~0ull;
   }
 
   // ---------------------------------------------------------------- phase E
-  // The winner's point is not kept while the search runs (12 doubles per root and wave: 4.5 of the frame's 33.8 KB of LDS,
-  // the difference between four and five frames per CU): the group is decoded here anyway, its DLT matrix is the canonical
-  // sum again (cameras ascending, fetch_candidate's bits) and the point is solve_and_score's own arithmetic on it -- nothing
-  // of which depends on the bound the evaluation was cut against.
-  __device__ void write_point(int64_t frame, int r, double e, uint32_t gl) const {
+  // The winners' points do not live in LDS (12 doubles per root and wave: 4.5 of the frame's 33.8 KB, the difference between four
+  // and five frames per CU) and are not solved for a second time either: the lane that ends an evaluation round as the holder of
+  // a (wave, root) slot leaves its candidate's point -- solve_and_score's own bits -- in the slot's record of the workgroup's
+  // workspace (search(), the delivery), 24 bytes per slot in memory the workgroup rewrites frame after frame, i.e. in L2.
+  // Slots are per wave, so no two waves ever write the same record and the merge of the four slots picks the record with them.
+  __device__ __forceinline__ double* winner_rec(int s) const {  // (a uniform base + a 32-bit lane offset: the address stays out of the vector registers)
+    return (double*)(p.ws + (size_t)blockIdx.x * p.ws_stride + (size_t)(24u * (uint32_t)s));
+  }
+  __device__ void write_point(int64_t frame, int r) const {
     const int C = cn();
+    unsigned long long kb;
+    uint32_t gw;
+    int wv;
+    if (!root_winner(r, kb, gw, wv)) return;
+    const uint32_t gl = gw >> 1;
+    const double e = kb != kInfBits ? __longlong_as_double((long long)kb)
+                                    : ((gw & 1u) ? __longlong_as_double(0x7ff8000000000000ll) : __builtin_huge_val());
     const size_t o = (size_t)frame * R + outslot[r];
+    // The record was written by a lane of wave wv of this workgroup during this frame's search and is complete in L2: every
+    // wave waits for its stores' acknowledgements (which come from L2) before the barrier that ends search().  The workgroup
+    // uses the same addresses for every frame, so the vector L1 may still hold the line as an EARLIER frame left it: the loads
+    // are agent-scope atomics (sc1), which the hardware never serves from the vector L1 -- the guarantee the AMDGPU memory
+    // model builds agent-scope coherence on -- and which therefore see what the XCD's L2 holds.  (The next frame's stores cannot
+    // overtake these loads either: the frame's last barrier is behind a wait for them.)
     p.err[o] = e;
-    double B[10];
-#pragma unroll
-    for (int ee = 0; ee < 10; ee++) B[ee] = 0.0;
+    const double* rec = winner_rec(wv * RS + r);
+    const double X[3] = {q_ld(rec + 0), q_ld(rec + 1), q_ld(rec + 2)};
     uint32_t rem = gl;  // decode the winning group
     const int rc = root_cam[r];
     int16_t* co = p.corr + o * C;
-    int j = 0;
+    uint32_t cw[4] = {0u, 0u, 0u, 0u};  // CT == 8: the row as four words
+#pragma unroll CT > 0 ? CT : 1
     for (int c = 0; c < C; c++) {
       int16_t s = -1;
       if (c == rc) {
@@ -1266,11 +1294,18 @@ struct BBState {
           rem = qd;
         }
       }
-      co[c] = s;
-      if (s >= 0) add_view(B, c, (uint32_t)s, j++);
+      if constexpr (CT == 8)
+        cw[c >> 1] |= (uint32_t)(uint16_t)s << (16 * (c & 1));
+      else
+        co[c] = s;
     }
-    double X[3];
-    solve_point(B, X);
+    if constexpr (CT == 8) {
+      // eight cameras: the row is 16 bytes at a multiple of 16 bytes from the array's start -- one store instead of eight
+      // (the type says 2-byte alignment: the caller's array is int16_t, and global memory takes the access at any alignment)
+      typedef uint32_t row_t __attribute__((ext_vector_type(4), aligned(2)));
+      row_t v = {cw[0], cw[1], cw[2], cw[3]};
+      *(row_t*)co = v;
+    }
     store_point(p, o, X);  // incl. the fused world-coordinate epilogue (helpers.py:96-103)
   }
 };
@@ -1294,10 +1329,16 @@ __global__ __launch_bounds__(kBBThreads, bb_wg_per_cu(RL)) void frame_bb_calib_k
 }
 
 int frame_bb_wg_per_cu_cap(int C, int M, int R) { return bb_wg_per_cu(bb_fixed_slots(C, M, R)); }
-size_t frame_bb_ws_bytes(int) { return 0; }  // (no per-workgroup HBM workspace: everything between input and output lives in LDS)
+// The winners' records (BBState::winner_rec): one point per (wave, root slot), sized for the largest layout whatever the call's
+// is -- one size per context, so that no launch ever makes the workspace grow behind another that is still queued on it
+// (the re-submit's second pass follows the first at once, with another layout).  24 KB per workgroup; the part a layout touches
+// (4.5 KB at 48 slots) is rewritten frame after frame and stays in L2.
+size_t frame_bb_ws_bytes(int) { return BBLayout::al(sizeof(double) * 3 * (size_t)kBBWaves * 255, 256); }
+static_assert(bb_wg_per_cu(48) <= kBBMaxWgPerCu && bb_wg_per_cu(64) <= kBBMaxWgPerCu && bb_wg_per_cu(0) <= kBBMaxWgPerCu, "frame_capi.hip sizes the workspace for kBBMaxWgPerCu workgroups per CU");
 
 hipError_t launch_frame_bb(const FrameArgs& a, int grid, hipStream_t stream) {
   const size_t lds = frame_bb_lds_bytes(a.cv.C, a.M, a.K_max);
+  if (!a.ws || a.ws_stride < sizeof(double) * 3 * (size_t)kBBWaves * (size_t)frame_bb_root_slots(a.cv.C, a.M, a.K_max)) return hipErrorInvalidValue;  // the winners' records
   // the kernel addresses the tables from one base (BBCamTables): the block layout of mocap_set_cameras, whose Pq is 12 C
   // doubles for identical intrinsics and 12 C C otherwise
   const size_t nPq = a.cv.uniformK ? (size_t)12 * a.cv.C : (size_t)12 * a.cv.C * a.cv.C;

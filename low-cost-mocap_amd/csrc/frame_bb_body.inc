@@ -1,6 +1,10 @@
 // frame_bb_body.inc -- the body of the search kernels (csrc/frame_bb.hip includes it once per __global__: the identical-K
 // kernel and the per-camera-K one are the same text on two BBState types; a shared __device__ function in its place moved
 // the identical-K kernels' register allocation).  In scope: FrameArgs p, smem, BB_STATE = the BBState type.
+  // The re-submit's second pass behind a batch that flagged nothing (FrameArgs::n_frames_dev): the count was final before this
+  // launch began, so the test is uniform over the grid -- every workgroup leaves before it touches a queue counter, and counters
+  // nobody touched are still the zeros the next launch relies on.
+  if (p.n_frames_dev && q_load(p.n_frames_dev) <= 0) return;
   BB_STATE st(p, smem);
   const int tid = threadIdx.x;
   const FrameQueues& q = p.q;
@@ -40,10 +44,7 @@
       const int nroots = st.misc[MI_NROOTS];
       st.fresh_tid();
       for (int r = st.tid; r < nroots; r += kBBThreads) {
-        if (st.outslot[r] < 0) continue;
-        double e;
-        uint32_t gl;
-        if (st.root_winner(r, e, gl)) st.write_point(frame, r, e, gl);
+        if (st.outslot[r] >= 0) st.write_point(frame, r);  // (a root with candidates: only those have an output slot)
       }
     }
     wait_own_stores();  // ... and loads: the next frame's blobs are in LDS

@@ -274,11 +274,15 @@ int match_dev_locked(mocap_ctx* ctx, const FrameBatch& b, int K_max, int64_t G_c
   if (per_cu > wave_cap) per_cu = wave_cap;
   if (per_cu < 1) per_cu = 1;
   const int64_t full_grid = (int64_t)ctx->num_cus * per_cu;
-  if (pl.use_bb && frame_bb_ws_bytes(ctx->C)) {
+  if (pl.use_bb) {
+    // the winners' records, in a buffer of their own (not the wide variant's frame_ws: a wide second pass behind a search first
+    // pass would grow that one, and DevBuf::reserve frees what it replaces): one size whatever the layout and the grid of this
+    // call (num_cus * kBBMaxWgPerCu >= full_grid), allocated by the context's first search pass and never again -- nothing is
+    // ever freed behind a launch that is still queued on it (the re-submit's second pass follows the first at once)
     a.ws_stride = frame_bb_ws_bytes(ctx->C);
-    if (ctx->frame_ws.reserve((size_t)full_grid * a.ws_stride))
-      return ctx->fail(MOCAP_E_HIP, "hipMalloc(search workspace, %zu B) failed", (size_t)full_grid * a.ws_stride);
-    a.ws = (unsigned char*)ctx->frame_ws.ptr;
+    const size_t ws_bytes = (size_t)ctx->num_cus * kBBMaxWgPerCu * a.ws_stride;
+    if (ctx->bb_ws.reserve(ws_bytes)) return ctx->fail(MOCAP_E_HIP, "hipMalloc(search workspace, %zu B) failed", ws_bytes);
+    a.ws = (unsigned char*)ctx->bb_ws.ptr;
   }
   if (pl.wide) {
     a.ws_stride = frame_ws_bytes(ctx->C, M_max, K_max, pl.T, pl.hit_cap, true, false);

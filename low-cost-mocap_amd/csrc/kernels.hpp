@@ -50,7 +50,8 @@ struct FrameArgs {
   int32_t* status;        // [F]
   int32_t* n_cand;        // [F] or null
   const double* world;    // null, or the 4x4 to-world matrix: xyz leaves the kernel in world coordinates
-  // wide frames (state does not fit LDS): per-workgroup workspace in HBM, hit-list cap per (root, camera)
+  // per-workgroup workspace in HBM -- wide frames (state does not fit LDS): the frame state; frame_bb.hip: the winners' records --
+  // and the wide variant's hit-list cap per (root, camera)
   unsigned char* ws;
   size_t ws_stride;
   int H;
@@ -134,7 +135,11 @@ bool frame_bb_fits(int C, int M, int R);
 size_t frame_bb_lds_bytes(int C, int M, int R);
 hipError_t launch_frame_bb(const FrameArgs& a, int grid, hipStream_t stream);
 int frame_bb_wg_per_cu_cap(int C, int M, int R);  // workgroups per CU the kernel's register budget allows (its waves per SIMD)
-size_t frame_bb_ws_bytes(int C);  // bytes of global workspace per workgroup (the probe scheme's parked candidates), 0 = none
+// bytes of global workspace per workgroup: the winners' records, one point (3 doubles) per (wave, root slot), written by the lane
+// that evaluated the candidate and read back by phase E -- the same for every layout (sized for 255 root slots), so the buffer
+// is allocated once per context, for num_cus * kBBMaxWgPerCu workgroups
+size_t frame_bb_ws_bytes(int C);
+constexpr int kBBMaxWgPerCu = 5;  // most workgroups per CU any instantiation runs with (frame_bb_wg_per_cu_cap)
 
 // object (drone) locator over the frame path's output (reference helpers.py:424-480), csrc/post_kernels.hip
 struct LocateArgs {
