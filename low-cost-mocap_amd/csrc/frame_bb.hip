@@ -35,8 +35,9 @@
 //   D   branch and bound over blocks of the Cartesian product: seeds, block tests, evaluation of the
 //       survivors' candidates spread over all lanes; per (wave, root) slot = lexicographic minimum of (error bits,
 //       candidate index) = np.argmin's first minimum (helpers.py:418) whatever the evaluation order
-//   E   one lane per kept root: merge the four waves' slots, fetch the winning slot's point (left in the workgroup's L2-resident
-//       workspace by the lane that evaluated it), decode the winning group, write xyz / err / corr
+//   E   one lane per kept root: merge the four waves' slots, fetch the winning slot's record -- the point and the group's packed
+//       blob bytes, left in the workgroup's L2-resident workspace by the lane that evaluated the candidate --, write xyz / err
+//       and the corr row built from the bytes.  Reads slot_key / slot_g / outslot and nothing of the matching's state
 #include "mocap_device.hpp"
 #include "kernels.hpp"
 #include <cstdlib>
@@ -50,6 +51,11 @@ namespace mocap {
 constexpr int kBBThreads = 256;
 constexpr int kBBWaves = kBBThreads / 64;
 constexpr int kBBRecs = kBBThreads + 64;  // surviving blocks queued between two evaluation rounds (flush above 64)
+// a winner's record in the workgroup's workspace: the point (three doubles) + the group's packed blob bytes (CW words)
+// words of packed blob bytes per group (Packed<CW>): one up to eight cameras, two up to sixteen -- the kernels' CW (BB_PICK), the
+// LDS layout's and the records' all come from here
+constexpr int bb_cw(int C) { return C <= 8 ? 1 : 2; }
+constexpr uint32_t bb_rec_bytes(int CW) { return 24u + 8u * (uint32_t)CW; }
 
 // LDS carving, identical on host (size) and device (pointers): the frame's persistent state (blobs, per-blob DLT table,
 // roots, hit lists), the search's arrays (block records, result slots -- dead while matching, which keeps its speculative
@@ -139,10 +145,10 @@ static int frame_bb_root_slots(int C, int M, int R) {
   const int f = bb_fixed_slots(C, M, R);
   return f ? f : R;
 }
-size_t frame_bb_lds_bytes(int C, int M, int R) { return BBLayout(C, M, frame_bb_root_slots(C, M, R), C <= 8 ? 1 : 2, bb_wg_per_cu(bb_fixed_slots(C, M, R))).total; }
+size_t frame_bb_lds_bytes(int C, int M, int R) { return BBLayout(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R))).total; }
 static size_t frame_bb_lds_bytes_min(int C, int M, int R) {
-  const BBLayout L(C, M, frame_bb_root_slots(C, M, R), C <= 8 ? 1 : 2, bb_wg_per_cu(bb_fixed_slots(C, M, R)));
-  return L.total - (8 + 8 * (size_t)(C <= 8 ? 1 : 2)) * (size_t)L.ncache;
+  const BBLayout L(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R)));
+  return L.total - (8 + 8 * (size_t)bb_cw(C)) * (size_t)L.ncache;
 }
 bool frame_bb_fits(int C, int M, int R) {
   // blob indices and root numbers are bytes (0xFF = none); a (root, blob) group is at most one wave; the expanded
@@ -1089,8 +1095,9 @@ struct BBState {
           uint32_t lo = 0;
           if (i0 + (uint32_t)(wave * 64) < ne)  // wave-uniform
             lo = (uint32_t)coop_last_le(rec_start, (int)ns, i0 + (uint32_t)(wave * 64), have ? i : ne - 1, lane);
+          Packed<CW> pk;  // the candidate's blob bytes: they go into the winner's record with the point
+          pk.clear();
           if (have) {
-            Packed<CW> pk;
             double B[10];
             const int v = fetch_candidate(lo, i, r, gl, pk, B);
             auto obs_p = [&](int c, double& x, double& y) -> bool {
@@ -1137,17 +1144,15 @@ struct BBState {
             wave_lds_sync();
             if (holder) atomicMin(&slot_g[ss], gword);
             wave_lds_sync();
-            // the lane that holds the slot after this round -- its error AND its index stood -- leaves the candidate's point in
-            // the slot's record of the workspace (phase E reads the winning slot's); every change of a slot's (key, index) pair
-            // comes with the store of the lane that made it, a cut-short or NaN candidate's included (it can be all a root has)
-            // (a slot can be re-won by another lane of this wave in a later pass of this loop, with no barrier in between: the two
-            // stores go to one address from one wave, and a wave's stores to an address reach L2 in the order it issued them)
-            if (holder && slot_g[ss] == gword) {
-              double* rec = winner_rec(ss);
-              rec[0] = X[0];
-              rec[1] = X[1];
-              rec[2] = X[2];
-            }
+            // the lane that holds the slot after this round -- its error AND its index stood -- leaves the candidate's point and
+            // its group's blob bytes in the slot's record of the workspace (phase E reads the winning slot's and nothing else of
+            // the group); every change of a slot's (key, index) pair comes with the store of the lane that made it, a cut-short
+            // or NaN candidate's included (it can be all a root has)
+            // (a slot can be re-won by another lane of this wave in a later pass of this loop, with no barrier in between: the
+            // record's words are stored by ONE lane per pass, every word goes to its own address from one wave, and a wave's
+            // stores to an address reach L2 in the order it issued them -- so each word, the bytes' included, ends up as the
+            // last holder left it)
+            if (holder && slot_g[ss] == gword) store_winner(ss, X, pk);
           }
         }
         __syncthreads();  // every lane is done with the records: new ones may be queued (through the other counter)
@@ -1246,21 +1251,48 @@ struct BBState {
   }
 
   // ---------------------------------------------------------------- phase E
-  // The winners' points do not live in LDS (12 doubles per root and wave: 4.5 of the frame's 33.8 KB, the difference between four
+  // The winners do not live in LDS (12 doubles per root and wave: 4.5 of the frame's 33.8 KB, the difference between four
   // and five frames per CU) and are not solved for a second time either: the lane that ends an evaluation round as the holder of
-  // a (wave, root) slot leaves its candidate's point -- solve_and_score's own bits -- in the slot's record of the workgroup's
-  // workspace (search(), the delivery), 24 bytes per slot in memory the workgroup rewrites frame after frame, i.e. in L2.
+  // a (wave, root) slot leaves its candidate's point -- solve_and_score's own bits -- and the group's packed blob bytes (the
+  // Packed<CW> it evaluated: one byte per camera, 0xFF = not in the group) in the slot's record of the workgroup's workspace
+  // (search(), the delivery): 24 + 8 CW bytes per slot in memory the workgroup rewrites frame after frame, i.e. in L2.
   // Slots are per wave, so no two waves ever write the same record and the merge of the four slots picks the record with them.
-  __device__ __forceinline__ double* winner_rec(int s) const {  // (a uniform base + a 32-bit lane offset: the address stays out of the vector registers)
-    return (double*)(p.ws + (size_t)blockIdx.x * p.ws_stride + (size_t)(24u * (uint32_t)s));
+  static constexpr uint32_t kRecBytes = bb_rec_bytes(CW);
+  __device__ __forceinline__ unsigned char* winner_rec(int s) const {  // (a uniform base + a 32-bit lane offset: the address stays out of the vector registers)
+    return p.ws + (size_t)blockIdx.x * p.ws_stride + (size_t)(kRecBytes * (uint32_t)s);
   }
+  __device__ __forceinline__ void store_winner(int s, const double (&X)[3], const Packed<CW>& pk) const {
+    unsigned long long* rec = (unsigned long long*)winner_rec(s);
+    if constexpr (CW == 1) {
+      // 32 bytes at a multiple of 32 (the workspace is 256-byte aligned, so is the stride): two 16-byte stores
+      typedef unsigned long long rec2_t __attribute__((ext_vector_type(2)));
+      const rec2_t lo = {(unsigned long long)__double_as_longlong(X[0]), (unsigned long long)__double_as_longlong(X[1])};
+      const rec2_t hi = {(unsigned long long)__double_as_longlong(X[2]), pk.w[0]};
+      ((rec2_t*)rec)[0] = lo;
+      ((rec2_t*)rec)[1] = hi;
+    } else {
+      // 40 bytes at a multiple of 8: five 8-byte stores
+#pragma unroll
+      for (int k = 0; k < 3; k++) rec[k] = (unsigned long long)__double_as_longlong(X[k]);
+#pragma unroll
+      for (int k = 0; k < CW; k++) rec[3 + k] = pk.w[k];
+    }
+  }
+  // two bytes of a group (low 16 bits of `two`) as two entries of a correspondence row: 0xFF -> -1, any other byte (a blob
+  // index, <= 63) -> itself
+  __device__ static __forceinline__ uint32_t row_word(uint32_t two) {
+    const uint32_t x = (two & 0xFFu) | ((two & 0xFF00u) << 8);
+    const uint32_t none = ((x + 0x00010001u) >> 8) & 0x00010001u;  // 1 where the byte was 0xFF
+    return x | none * 0xFF00u;
+  }
+  // Phase E reads slot_key, slot_g and outslot of the frame's LDS state and nothing else: none of the matching's arrays
+  // (nh, hits, root_cam, root_blob) and no divmod -- the row comes from the record's bytes.
   __device__ void write_point(int64_t frame, int r) const {
     const int C = cn();
     unsigned long long kb;
     uint32_t gw;
     int wv;
     if (!root_winner(r, kb, gw, wv)) return;
-    const uint32_t gl = gw >> 1;
     const double e = kb != kInfBits ? __longlong_as_double((long long)kb)
                                     : ((gw & 1u) ? __longlong_as_double(0x7ff8000000000000ll) : __builtin_huge_val());
     const size_t o = (size_t)frame * R + outslot[r];
@@ -1270,41 +1302,25 @@ struct BBState {
     // are agent-scope atomics (sc1), which the hardware never serves from the vector L1 -- the guarantee the AMDGPU memory
     // model builds agent-scope coherence on -- and which therefore see what the XCD's L2 holds.  (The next frame's stores cannot
     // overtake these loads either: the frame's last barrier is behind a wait for them.)
+    const unsigned long long* rec = (const unsigned long long*)winner_rec(wv * RS + r);
+    unsigned long long w[3 + CW];
+#pragma unroll
+    for (int k = 0; k < 3 + CW; k++) w[k] = q_ld(rec + k);
     p.err[o] = e;
-    const double* rec = winner_rec(wv * RS + r);
-    const double X[3] = {q_ld(rec + 0), q_ld(rec + 1), q_ld(rec + 2)};
-    uint32_t rem = gl;  // decode the winning group
-    const int rc = root_cam[r];
+    const double X[3] = {__longlong_as_double((long long)w[0]), __longlong_as_double((long long)w[1]), __longlong_as_double((long long)w[2])};
     int16_t* co = p.corr + o * C;
-    uint32_t cw[4] = {0u, 0u, 0u, 0u};  // CT == 8: the row as four words
-#pragma unroll CT > 0 ? CT : 1
-    for (int c = 0; c < C; c++) {
-      int16_t s = -1;
-      if (c == rc) {
-        s = (int16_t)root_blob[r];
-      } else if (c > rc) {
-        const uint32_t n = nh[(size_t)r * C + c];
-        if (n) {
-          uint32_t qd = rem, dgt = 0;
-          if (n > 1) {  // (a single hit is digit 0 of radix 1: nothing to divide)
-            if (rem < 8192u) divmod_tiny(rem, n, qd, dgt); else
-            divmod_small(rem, n, qd, dgt);
-          }
-          s = (int16_t)hits[((size_t)r * C + c) * M + dgt];
-          rem = qd;
-        }
-      }
-      if constexpr (CT == 8)
-        cw[c >> 1] |= (uint32_t)(uint16_t)s << (16 * (c & 1));
-      else
-        co[c] = s;
-    }
     if constexpr (CT == 8) {
       // eight cameras: the row is 16 bytes at a multiple of 16 bytes from the array's start -- one store instead of eight
       // (the type says 2-byte alignment: the caller's array is int16_t, and global memory takes the access at any alignment)
       typedef uint32_t row_t __attribute__((ext_vector_type(4), aligned(2)));
-      row_t v = {cw[0], cw[1], cw[2], cw[3]};
+      const uint32_t lo = (uint32_t)w[3], hi = (uint32_t)(w[3] >> 32);
+      row_t v = {row_word(lo), row_word(lo >> 16), row_word(hi), row_word(hi >> 16)};
       *(row_t*)co = v;
+    } else {
+      for (int c = 0; c < C; c++) {
+        const uint32_t k = (uint32_t)(w[3 + (CW == 1 ? 0 : c >> 3)] >> (8 * (c & 7))) & 0xFFu;
+        co[c] = k == 0xFFu ? (int16_t)-1 : (int16_t)k;
+      }
     }
     store_point(p, o, X);  // incl. the fused world-coordinate epilogue (helpers.py:96-103)
   }
@@ -1331,14 +1347,14 @@ __global__ __launch_bounds__(kBBThreads, bb_wg_per_cu(RL)) void frame_bb_calib_k
 int frame_bb_wg_per_cu_cap(int C, int M, int R) { return bb_wg_per_cu(bb_fixed_slots(C, M, R)); }
 // The winners' records (BBState::winner_rec): one point per (wave, root slot), sized for the largest layout whatever the call's
 // is -- one size per context, so that no launch ever makes the workspace grow behind another that is still queued on it
-// (the re-submit's second pass follows the first at once, with another layout).  24 KB per workgroup; the part a layout touches
-// (4.5 KB at 48 slots) is rewritten frame after frame and stays in L2.
-size_t frame_bb_ws_bytes(int) { return BBLayout::al(sizeof(double) * 3 * (size_t)kBBWaves * 255, 256); }
+// (the re-submit's second pass follows the first at once, with another layout).  40 KB per workgroup (255 slots of the two-word
+// record); the part a layout touches (6 KB at 48 slots and one word) is rewritten frame after frame and stays in L2.
+size_t frame_bb_ws_bytes(int) { return BBLayout::al(bb_rec_bytes(2) * (size_t)kBBWaves * 255, 256); }
 static_assert(bb_wg_per_cu(48) <= kBBMaxWgPerCu && bb_wg_per_cu(64) <= kBBMaxWgPerCu && bb_wg_per_cu(0) <= kBBMaxWgPerCu, "frame_capi.hip sizes the workspace for kBBMaxWgPerCu workgroups per CU");
 
 hipError_t launch_frame_bb(const FrameArgs& a, int grid, hipStream_t stream) {
   const size_t lds = frame_bb_lds_bytes(a.cv.C, a.M, a.K_max);
-  if (!a.ws || a.ws_stride < sizeof(double) * 3 * (size_t)kBBWaves * (size_t)frame_bb_root_slots(a.cv.C, a.M, a.K_max)) return hipErrorInvalidValue;  // the winners' records
+  if (!a.ws || a.ws_stride < bb_rec_bytes(bb_cw(a.cv.C)) * (size_t)kBBWaves * (size_t)frame_bb_root_slots(a.cv.C, a.M, a.K_max)) return hipErrorInvalidValue;  // the winners' records
   // the kernel addresses the tables from one base (BBCamTables): the block layout of mocap_set_cameras, whose Pq is 12 C
   // doubles for identical intrinsics and 12 C C otherwise
   const size_t nPq = a.cv.uniformK ? (size_t)12 * a.cv.C : (size_t)12 * a.cv.C * a.cv.C;
@@ -1347,6 +1363,7 @@ hipError_t launch_frame_bb(const FrameArgs& a, int grid, hipStream_t stream) {
   const bool f32 = a.cv.f32_rounding != 0;
   const int fixed = bb_fixed_slots(a.cv.C, a.M, a.K_max);
   if (fixed && fixed != 48 && fixed != 64) return hipErrorInvalidValue;
+  static_assert(bb_cw(8) == 1 && bb_cw(9) == 2 && bb_cw(16) == 2, "BB_PICK takes CW = 1 up to eight cameras, CW = 2 above");
 #define BB_PICK(KERNEL)                                                                             \
   (fixed == 48       ? (f32 ? KERNEL<true, 1, 8, 16, 48> : KERNEL<false, 1, 8, 16, 48>)             \
    : fixed == 64     ? (f32 ? KERNEL<true, 1, 8, 16, 64> : KERNEL<false, 1, 8, 16, 64>)             \

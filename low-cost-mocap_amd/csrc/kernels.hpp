@@ -135,8 +135,9 @@ bool frame_bb_fits(int C, int M, int R);
 size_t frame_bb_lds_bytes(int C, int M, int R);
 hipError_t launch_frame_bb(const FrameArgs& a, int grid, hipStream_t stream);
 int frame_bb_wg_per_cu_cap(int C, int M, int R);  // workgroups per CU the kernel's register budget allows (its waves per SIMD)
-// bytes of global workspace per workgroup: the winners' records, one point (3 doubles) per (wave, root slot), written by the lane
-// that evaluated the candidate and read back by phase E -- the same for every layout (sized for 255 root slots), so the buffer
+// bytes of global workspace per workgroup: the winners' records, one point (3 doubles) + the group's packed blob bytes (one or two words) per
+// (wave, root slot), written by the lane that evaluated the candidate and read back by phase E -- the same for every layout (sized
+// for 255 root slots of the two-word record), so the buffer
 // is allocated once per context, for num_cus * kBBMaxWgPerCu workgroups
 size_t frame_bb_ws_bytes(int C);
 constexpr int kBBMaxWgPerCu = 5;  // most workgroups per CU any instantiation runs with (frame_bb_wg_per_cu_cap)
