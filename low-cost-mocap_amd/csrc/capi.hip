@@ -113,7 +113,10 @@ extern "C" int mocap_create(int device_id, mocap_ctx** out) {
   if ((t = getenv("MOCAP_PRUNE"))) c->prune = atoi(t) ? 1 : 0;
   if ((t = getenv("MOCAP_EIGCUT"))) c->eigcut = atoi(t) ? 1 : 0;
   if ((t = getenv("MOCAP_EVAL_BB"))) c->eval_bb = atoi(t) ? 1 : 0;
-  if ((t = getenv("MOCAP_BB_PL")) && atoi(t) >= 1 && atoi(t) <= 64) c->bb_pl = atoi(t);
+  if ((t = getenv("MOCAP_BB_PL_MIN")) && atoi(t) >= 1 && atoi(t) <= 64) c->bb_pl_min = atoi(t);
+  if ((t = getenv("MOCAP_BB_NB_MAX")) && atoi(t) >= 1) c->bb_nb_max = atoi(t);
+  if (c->bb_pl_min > c->bb_pl) c->bb_pl_min = c->bb_pl;
+  if ((t = getenv("MOCAP_BB_PL")) && atoi(t) >= 1 && atoi(t) <= 64) c->bb_pl = c->bb_pl_min = atoi(t);  // one size for every root: at least this many candidates per block
   if ((t = getenv("MOCAP_BB_FLUSH")) && atoi(t) >= 1) c->bb_flush = atoi(t);
   if ((t = getenv("MOCAP_BB_MIN_G")) && atoi(t) >= 0) c->bb_min_g = atoi(t);
   if ((t = getenv("MOCAP_FRAME_LAUNCHES"))) c->frame_launches = atoi(t) == 3 ? 3 : 1;  // 3: main / slice / merge launches (A/B)  // 0: every group is reprojected in full (A/B)

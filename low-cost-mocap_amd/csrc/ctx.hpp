@@ -76,7 +76,10 @@ struct mocap_ctx {
   int prune = 1;            // stop a candidate group's reprojection once it cannot beat its root's best (exact)
   int exhaustive = 0;       // MOCAP_OPT_EXHAUSTIVE_WALK: no branch and bound, no cut-offs (verification mode)
   int eval_bb = 1;          // branch-and-bound selection (csrc/frame_bb.hip) wherever it applies; 0: always the exhaustive walk
-  int bb_pl = 16;           // ... candidates per block (at least)
+  int bb_pl = 16;           // ... candidates per block: a root stops opening digits here at the latest (MOCAP_BB_PL: at least this many, as before round 10)
+  int bb_pl_min = 16;       // ... a root opens digits while its blocks hold fewer candidates than this,
+  int bb_nb_max = 1;        // ... or fewer than bb_pl while it still has more blocks than this (frame_bb.hip, phase C).  16 / 1 = one size for
+                            // every root: every finer setting of the round-10 sweep was slower (profiles/r10_block_size_ab.txt)
   int bb_min_g = 0;         // ... frames with fewer candidates queue every block untested (swept: 0-512 equal, 2048 +13 %)
   int bb_flush = 0;         // ... queued candidates that trigger their evaluation (0 = one per lane)
   int eigcut = 1;           // ... and drop it before the null vector / the reprojection on an eigenvalue bound (EigCut)

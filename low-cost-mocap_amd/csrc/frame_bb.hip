@@ -15,7 +15,8 @@
 //    the same pass for the provisional roots, then a chain over the cameras that is bookkeeping only.
 //  * written for instruction issue, which is what binds it: one lane per (root, camera) pair with the camera's blobs walked
 //    serially; the camera count (8) and, for 8 x 16 with K_max <= 48 / <= 64, the whole LDS layout at compile time; the
-//    blocks' bounds and blob indices cached between seed and test pass; the camera tables behind one base pointer.
+//    blocks' bounds cached between seed and test pass (one float each), their blob bytes and matrices built from what the
+//    root's blocks share (pkbase); the camera tables behind one base pointer.
 //  * a software pipeline over the frames: frame k + 1 is pulled from the queue and fetched straight into a spare LDS
 //    buffer (global_load_lds, no registers) while frame k is searched.
 //  * one evaluation path: a frame below the search threshold (MOCAP_BB_MIN_G, default 0 = never) queues all its blocks
@@ -42,6 +43,7 @@
 #include "kernels.hpp"
 #include <cstdlib>
 #include "frame_common.hpp"
+#include "bb_fold.hpp"
 // (Round 6: the timing-only switches -- phases compiled out, parts run twice -- and the probe scheme, measured slower in
 // round 5, left this file; they are in the history at 7c94a55 and in docs/HISTORY.md.  What remains switchable is what a
 // test uses: -DMOCAP_DEBUG_EIGCHECK, the self-check build of tests/test_gpu_bb_adversarial.py.)
@@ -65,10 +67,11 @@ constexpr uint32_t bb_rec_bytes(int CW) { return 24u + 8u * (uint32_t)CW; }
 // 48-slot layout -- the bench's -- whose 29.2 KB leave room for FIVE frames per CU: 96 VGPRs (52 spilled instead of 22, +6 % per
 // frame) and a block cache of 161 entries instead of 385, and still 4.50 -> 4.31 ms per 100 k frames (profiles/r06_wide_experiments.txt, (15)).
 constexpr int bb_wg_per_cu(int RL) { return RL == 48 ? 5 : 4; }
+constexpr size_t kBBCacheEntry = 4;  // bytes per cached block bound
 constexpr int kBBLdsSlack = 1024;  // (measured: 512 keeps the occupancy step as well, 0 does not)
 struct BBLayout {
   size_t bxy, bxy_nx, cnt_nx, bt, rbound, seedkey, slot_key, claimw, recs, rpk, scr, scr_bytes, goff, gcnt, outslot, boff, bnb, seedgh, slot_g, cnt,
-      misc, bpl, nh, hits, act, root_blob, root_cam, nact, bnl, bv, bcache, bpk, total;
+      misc, bpl, nh, hits, act, root_blob, root_cam, nact, bnl, bv, pkbase, seen, bcache, total;
   int ncache;
   __host__ __device__ static size_t al(size_t x, size_t a) { return (x + a - 1) / a * a; }
   __host__ __device__ BBLayout(int C, int M, int R, int CW, int wg_per_cu) {
@@ -86,6 +89,7 @@ struct BBLayout {
     bt = take(sizeof(double) * 10 * ((size_t)C * M + 1), 16);  // DLT contribution per (camera, blob): five b128 reads; + one record of zeros ("camera not in the group")
     rbound = take(8 * (size_t)R, 8);
     claimw = take(8 * (size_t)C, 8);
+    pkbase = take(8 * (size_t)CW * R, 8);  // per root: its own blob and its single-hit cameras' blobs (phase C -> block_pk)
     // the search's block records and result slots: dead while matching -> phase B keeps the speculative epipolar
     // lines here (match(): lines of every blob that MIGHT become a root, computed off the critical path)
     scr = seedkey = take(8 * (size_t)R, 8);
@@ -103,6 +107,7 @@ struct BBLayout {
     cnt = take(4 * (size_t)C, 4);
     misc = take(4 * 16, 4);
     bpl = take(2 * (size_t)R, 2);
+    seen = take(2 * (size_t)R, 2);  // per root: the cameras it sees, one bit each (per-camera K: a view's position)
     nh = take((size_t)R * C, 1);
     hits = take((size_t)R * C * M, 1);
     act = take((size_t)R * C, 1);
@@ -111,12 +116,13 @@ struct BBLayout {
     nact = take((size_t)R, 1);
     bnl = take((size_t)R, 1);
     bv = take((size_t)R, 1);
-    // cache of the blocks' bounds (seed pass -> test pass: {s1, trace} rounded UP to float, 8 bytes per block): as many
-    // entries as fit below the next occupancy step of the 160 KB LDS (5, 4, 3, ... workgroups per CU), at most 1024
-    // (round 5: + the block's blob indices, 8 CW bytes: a surviving block is queued from the cache alone -- no second decode)
-    bcache = take(0, 8);
+    // cache of the blocks' bounds (seed pass -> test pass: ONE float per block, bb_fold.hpp): as many entries as fit below
+    // the next occupancy step of the 160 KB LDS (5, 4, 3, ... workgroups per CU), at most 1024
+    // (rounds 5-9: {s1, trace} + the block's blob indices, 8 + 8 CW bytes -- 161 entries at five workgroups per CU, fewer than
+    // the blocks of every third bench frame; the few blocks that survive rebuild their indices from pkbase, block_pk)
+    bcache = take(0, 4);
     ncache = 0;
-    const size_t per_entry = 8 + 8 * (size_t)CW;
+    const size_t per_entry = kBBCacheEntry;
     for (int per_cu = wg_per_cu; per_cu >= 1; per_cu--) {
       const size_t lim = ((size_t)160 * 1024 / per_cu - kBBLdsSlack) / 256 * 256;  // (slack: allocation granule, other LDS users)
       if (lim >= o + per_entry * 64) {
@@ -125,9 +131,7 @@ struct BBLayout {
         break;
       }
     }
-    o += 8 * (size_t)ncache;
-    bpk = o;
-    o += 8 * (size_t)CW * ncache;
+    o += per_entry * (size_t)ncache;
     total = al(o, 16);
   }
 };
@@ -148,7 +152,7 @@ static int frame_bb_root_slots(int C, int M, int R) {
 size_t frame_bb_lds_bytes(int C, int M, int R) { return BBLayout(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R))).total; }
 static size_t frame_bb_lds_bytes_min(int C, int M, int R) {
   const BBLayout L(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R)));
-  return L.total - (8 + 8 * (size_t)bb_cw(C)) * (size_t)L.ncache;
+  return L.total - kBBCacheEntry * (size_t)L.ncache;
 }
 bool frame_bb_fits(int C, int M, int R) {
   // blob indices and root numbers are bytes (0xFF = none); a (root, blob) group is at most one wave; the expanded
@@ -257,8 +261,9 @@ struct BBState {
   int32_t *outslot, *cnt, *misc;
   uint16_t* bpl;
   uint8_t *nh, *hits, *act, *root_blob, *root_cam, *nact, *bnl, *bv;
-  float2* bcache;      // [ncache] {s1, trace} of the first blocks, rounded up (BBLayout::bcache)
-  unsigned long long* bpk;  // [ncache][CW] ... and their partial groups' blob indices
+  float* bcache;       // [ncache] the first blocks' bounds, folded (BBLayout::bcache, bb_fold.hpp)
+  unsigned long long* pkbase;  // [RS][CW] blob indices every block of the root shares
+  uint16_t* seen;      // [RS] cameras the root sees
   int ncache;
   unsigned char* scr;  // phase B scratch = the search's records and slots (BBLayout::scr)
   size_t scr_bytes;
@@ -306,8 +311,9 @@ struct BBState {
     bv = (uint8_t*)(smem + L.bv);
     scr = smem + L.scr;
     scr_bytes = L.scr_bytes;
-    bcache = (float2*)(smem + L.bcache);
-    bpk = (unsigned long long*)(smem + L.bpk);
+    bcache = (float*)(smem + L.bcache);
+    pkbase = (unsigned long long*)(smem + L.pkbase);
+    seen = (uint16_t*)(smem + L.seen);
     ncache = L.ncache;
   }
 
@@ -793,10 +799,17 @@ struct BBState {
       unsigned long long total = 1;
       int views = 1, na = 0;
       bool over = false;
+      // what every block of the root has in common (block_pk): the root's own blob and the single-hit cameras' blobs
+      Packed<CW> pkb;
+      pkb.clear();
+      pkb.set(rc, root_blob[r]);
+      uint32_t sm = 1u << rc;
       for (int c = rc + 1; c < C; c++) {
         const unsigned n = nh[(size_t)r * C + c];
         if (n > 1) act[(size_t)r * C + na++] = (uint8_t)c;  // multi-hit cameras = the digits of the candidate index
+        if (n == 1) pkb.set(c, hits[((size_t)r * C + c) * M]);
         if (n) {
+          sm |= 1u << c;
           views++;
           total *= n;
           if (total > (unsigned long long)p.G_cap) {
@@ -808,17 +821,29 @@ struct BBState {
       if (over) atomicOr(&misc[MI_STATUS], MOCAP_ST_CAND_OVERFLOW_);
       nact[r] = (uint8_t)na;
       bv[r] = (uint8_t)views;
+#pragma unroll
+      for (int k = 0; k < CW; k++) pkbase[(size_t)r * CW + k] = pkb.w[k];
+      if (PERK) seen[r] = (uint16_t)sm;
       rbound[r] = kInfBits;
       const uint32_t g = (views > 1 && !over) ? (uint32_t)total : 0u;  // helpers.py:413-414 drops 1-view roots
       gcnt[r] = g;
-      // the search's blocks of this root (phase D): the nl fastest digits stay open (pl >= bb_pl candidates per block), one
-      // block per value of the others.  Here rather than at the start of the search: the same lanes, no extra barrier pair.
+      // the search's blocks of this root (phase D): the nl fastest digits stay open (pl candidates per block), one block per
+      // value of the others.  The size is the root's own: digits open until a block holds bb_pl_min candidates, and further -- up
+      // to bb_pl -- while more than bb_nb_max blocks would be left.  A root with few candidates gets small blocks (its seed block,
+      // evaluated against no bound at all, is most of what it costs), one with many keeps the number of bounds in check.
+      // Here rather than at the start of the search: the same lanes, no extra barrier pair.
       {
         const uint8_t* a = act + (size_t)r * C;
         uint32_t pl = 1, nb = 1;
         int nl = 0;
-        while (nl < na && pl < (uint32_t)p.bb_pl) pl *= nh[(size_t)r * C + a[nl++]];
-        for (int k = nl; k < na; k++) nb *= nh[(size_t)r * C + a[k]];
+        for (int k = 0; k < na; k++) nb *= nh[(size_t)r * C + a[k]];  // (= total; 1 for a root over G_cap, which has no blocks)
+        if (over) nb = 1;
+        while (nl < na && (pl < (uint32_t)p.bb_pl_min || (pl < (uint32_t)p.bb_pl && nb > (uint32_t)p.bb_nb_max))) {
+          const uint32_t n = nh[(size_t)r * C + a[nl++]];
+          uint32_t dummy;
+          pl *= n;
+          divmod_small(nb, n, nb, dummy);  // (exact: nb < 2^24 is a multiple of n)
+        }
         bpl[r] = (uint16_t)pl;
         bnl[r] = (uint8_t)nl;
         bnb[r] = g ? nb : 0u;
@@ -926,6 +951,54 @@ struct BBState {
     return v;
   }
 
+  // Blob indices of block gh of root r: what the root's blocks share (pkbase: the root's blob, the single-hit cameras) plus the
+  // block's own fixed digits -- the multi-hit cameras act[bnl[r] .. nact[r]-1], typically one to three; the open digits' and the
+  // absent cameras' bytes stay 0xFF.  (group_matrix walks all cameras for the same bytes; it remains the self-check build's decoder.)
+  __device__ __forceinline__ void block_pk(int r, uint32_t gh, Packed<CW>& pk) const {
+    const int C = cn();
+#pragma unroll
+    for (int k = 0; k < CW; k++) pk.w[k] = pkbase[(size_t)r * CW + k];
+    const uint8_t* a = act + (size_t)r * C;
+    const int na = nact[r];
+    uint32_t rem = gh;
+    for (int k = bnl[r]; k < na; k++) {
+      const int c = a[k];
+      const uint32_t n = nh[(size_t)r * C + c];
+      uint32_t qd, dgt;
+      if (rem < 8192u) divmod_tiny(rem, n, qd, dgt); else  // (the usual case for every lane of the wave: one path runs)
+      divmod_small(rem, n, qd, dgt);
+      rem = qd;
+      pk.set(c, hits[((size_t)r * C + c) * M + dgt]);
+    }
+  }
+  // ... and the DLT matrix of the block's partial group: the table rows of its cameras in ascending order, branch-free -- a camera
+  // that is open or absent adds the record of zeros, as in fetch_candidate (same bits as skipping it).  Per-camera K: a view's
+  // position is the number of SEEN cameras before it, the open ones included (the root's `seen` mask), add_view's rule.
+  // Returns the views of the partial group.
+  __device__ __forceinline__ int block_matrix(int r, uint32_t gh, Packed<CW>& pk, double (&B)[10]) const {
+    const int C = cn();
+    block_pk(r, gh, pk);
+#pragma unroll
+    for (int ee = 0; ee < 10; ee++) B[ee] = 0.0;
+    if constexpr (PERK) {
+      const uint32_t sm = seen[r];
+#pragma unroll CT > 0 ? CT : 1
+      for (int c = 0; c < C; c++) {
+        const uint32_t k = pk.get(c);
+        if (k != 0xFFu) add_view(B, c, k, __popc(sm & ((1u << c) - 1u)));
+      }
+    } else {
+#pragma unroll CT > 0 ? CT : 1
+      for (int c = 0; c < C; c++) {
+        const uint32_t k = pk.get(c);
+        const double* t = bt + (size_t)(k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
+#pragma unroll
+        for (int ee = 0; ee < 10; ee++) B[ee] = B[ee] + t[ee];
+      }
+    }
+    return (int)bv[r] - (int)bnl[r];
+  }
+
   // Record r of the queue and candidate i of the expanded list -> the candidate's root, index, blob indices and DLT matrix
   // (cameras in ascending order: the one canonical rounding of B; a camera that is not in the group adds the table's record
   // of zeros: x + (+0.0) = x for every x the sum can hold -- it starts at +0.0, so it is never -0.0 -- the same bits
@@ -1009,13 +1082,15 @@ struct BBState {
     };
     auto rec_start = [&](int k) { return (recs[k].rs & 0x7FFFFFFFu) >> 8; };
     // EigCut's first test of a (partial) group of root r against the best error of the root so far
-    auto dropped = [&](int r, double s1, double tr) {
+    // (root_y: the root's side of the test -- p3max2c times the limit its best error so far sets, with the allowances)
+    auto root_y = [&](int r) {
       const int vf = bv[r];
       const double bound = __longlong_as_double((long long)rbound[r]);
       const double limit = bound * (double)(2 * vf) * (1.0 + 0x1p-40);
       const double limit_adj = fma(1.002, limit, (double)(2 * vf) * ec.o2slack);
-      return s1 * fma(2e-12, tr, p.p3max2c * limit_adj) < 1.0;
+      return p.p3max2c * limit_adj;
     };
+    auto dropped = [&](int r, double s1, double tr) { return s1 * fma(2e-12, tr, root_y(r)) < 1.0; };
     if (bound_tests) {
       bb_prio<kPrioSeed>();
       // ---- 1. seeds: s1 of every block (cached for the tests); per root the block with the largest s1 (smallest
@@ -1035,18 +1110,14 @@ struct BBState {
           const uint32_t gh = b - boff[r];
           double B[10], tr = 0.0;
           Packed<CW> pk;
-          const int v = group_matrix<true>(r, gh, bnl[r], B, pk);
+          const int v = block_matrix(r, gh, pk, B);
           double s1d = __builtin_huge_val();  // a one-view partial group carries no information: never dropped, any seed
           float s1 = 0.0f;
           if (v >= 2) {
             s1d = eigcut_s1_shifted(B, c0, tr);
             s1 = (float)fmin(s1d, 3e38);
           }
-          if (b < (uint32_t)ncache) {
-            bcache[b] = make_float2(__double2float_ru(s1d), __double2float_ru(tr));
-#pragma unroll
-            for (int k = 0; k < CW; k++) bpk[(size_t)b * CW + k] = pk.w[k];
-          }
+          if (b < (uint32_t)ncache) bcache[b] = v >= 2 ? bb_fold_bound(s1d, tr) : bb_fold_inf();
           my_key = ((unsigned long long)__float_as_uint(s1) << 32) | (unsigned long long)(0xFFFFFFFFu - gh);
           my_r = r;
           my_gh = gh;
@@ -1066,9 +1137,8 @@ struct BBState {
           const uint32_t gh = 0xFFFFFFFFu - (uint32_t)seedkey[r];
           seedgh[r] = gh;
           seedkey[r] = 0ull;
-          double B[10];
           Packed<CW> pk;
-          group_matrix<false>(r, gh, bnl[r], B, pk);
+          block_pk(r, gh, pk);
           push_block(r, gh, pk);
         }
       }
@@ -1184,19 +1254,18 @@ struct BBState {
           double B[10], tr;
           bool survive = true;
           if (bound_tests && b < (uint32_t)ncache) {
-            // {s1, trace} from the seed pass, rounded up: a larger s1 or trace only ever keeps a block (safe side)
-            const float2 sc = bcache[b];
-            survive = !dropped(r, (double)sc.x, (double)sc.y);
-#pragma unroll
-            for (int k = 0; k < CW; k++) pk.w[k] = bpk[(size_t)b * CW + k];
+            // the bound from the seed pass, folded into one float on the safe side (bb_fold.hpp); a block that survives -- a
+            // handful per frame -- rebuilds its blob indices
+            survive = !bb_fold_dropped(bcache[b], root_y(r));
+            if (survive) block_pk(r, gh, pk);
           } else if (bound_tests) {
-            const int v = group_matrix<true>(r, gh, bnl[r], B, pk);
+            const int v = block_matrix(r, gh, pk, B);
             if (v >= 2) {
               const double s1 = eigcut_s1_shifted(B, c0, tr);
               survive = !dropped(r, s1, tr);
             }
           } else {
-            group_matrix<false>(r, gh, bnl[r], B, pk);
+            block_pk(r, gh, pk);
           }
           do_push = survive;
 #ifdef MOCAP_DEBUG_EIGCHECK  // self-check build: EVERY candidate of a dropped block is evaluated in full against the bound it was dropped on

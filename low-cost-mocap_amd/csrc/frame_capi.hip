@@ -142,11 +142,13 @@ FrameArgs frame_args(const mocap_ctx* ctx, const FrameBatch& b, int K_max, int64
   if (!pl.wide && ctx->frame_threads == 0 && pl.T == 64) a.p3max2 = 0.0;  // tiny frames (a handful of candidates): the cut-offs cost more than they save
   a.eval_bb = pl.use_bb ? 1 : 0;
   a.bb_pl = ctx->bb_pl;
+  a.bb_nb_max = ctx->bb_nb_max;
   for (int i = 0; i < 3; i++) a.bb_c0[i] = ctx->eig_c0[i];
   a.p3max2c = ctx->p3max2c;
   a.bb_flush = ctx->bb_flush > 0 ? ctx->bb_flush : 256;
   a.bb_min_g = ctx->bb_min_g;
   while (a.bb_pl > 1 && (size_t)a.bb_pl * M_max * 2 * 256 >= ((size_t)1 << 22)) a.bb_pl /= 2;  // expanded-list counter: 22 bits
+  a.bb_pl_min = ctx->bb_pl_min < a.bb_pl ? ctx->bb_pl_min : a.bb_pl;
   a.ws = nullptr;
   a.ws_stride = 0;
   const bool hv = heavy && pl.wide;

@@ -58,7 +58,8 @@ struct FrameArgs {
   int wide;   // 1: wide variant; 2: ... with the chain over the cameras strictly sequential (A/B, tests: MOCAP_WIDE_SPEC=0)
   int prune;  // cut the reprojection of a group short once it cannot beat the best of its root (exact, see evaluate())
   int eval_bb;  // (host only) the batch goes to frame_bb.hip
-  int bb_pl;    // ... candidates per block (at least)
+  int bb_pl;    // ... candidates per block: no root opens another digit from here on
+  int bb_pl_min, bb_nb_max;  // ... a root opens digits while pl < bb_pl_min, or while pl < bb_pl and it has more than bb_nb_max blocks left
   int bb_flush; // ... queued candidates that trigger their evaluation
   int bb_min_g; // ... frames with fewer candidates are walked exhaustively
   double bb_c0[3]; // branch and bound: origin of the frame its bounds are taken in (a point inside the working volume)
