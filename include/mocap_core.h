@@ -529,6 +529,87 @@ int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, co
                                  int32_t* d_rb_n_used, int8_t* d_rb_assign, double* d_rb_R, double* d_rb_t, double* d_rb_rms,
                                  double* d_rb_score, int32_t* d_rb_status);
 
+/* ---------------------------------------------------------------- marker tracker (the core's own contract)
+ * Identity over time: which point of this frame is the marker that was which point of the last one.  Every stage above treats a
+ * frame on its own; this one gives each marker a number that it keeps while it moves, through a few frames of occlusion and
+ * past another marker.  Opt-in and the core's own: with the tracker off nothing that existed before changes.
+ *
+ * State (on the device, in the context): T_max track slots, 1 <= T_max <= MOCAP_MT_MAX_TRACKS (64), each with
+ *   live, id (i32), p[3], v[3] (f64), t_seen (f64), missed, hits (i32)
+ * and next_id (i32), which starts at 0.  A session of more than 2^31 - 1 births is out of scope.
+ *
+ * mocap_set_marker_tracker: allocates and clears the state (and clears it when called again).
+ *   T_max       track slots; 0 switches the tracker off and frees the state; < 0 or > 64 is MOCAP_E_ARG
+ *   gate        metres, finite and > 0; g2 = gate * gate is formed once on the host in double
+ *   max_missed  >= 0: frames a track may go unseen before it is retired
+ *   vel_alpha   in [0, 1]: weight of the newest finite-difference velocity
+ * A bad value returns MOCAP_E_ARG and NOTHING changes (the previous settings and the state stay in force).
+ *
+ * One frame at time t has the points x_j, j < n: the first n_pts[f] of its K_max slots as the frame path writes them (world
+ * coordinates when a world transform is set).  K_max <= MOCAP_MT_MAX_POINTS (64), more is MOCAP_E_ARG; n_pts[f] outside
+ * 0 .. K_max counts as 0 (the "no valid slot" rule of mocap_locate_objects).  A non-finite t: status MOCAP_MT_ST_BAD_TIME,
+ * the frame's id are -1, its hits and n_tracks 0, and the state is untouched -- the "_dev" forms report it this way; the host
+ * forms reject a non-finite t with MOCAP_E_ARG before anything runs.
+ *
+ * All arithmetic is IEEE double, no fused operation, in the order written here.
+ *   1. Prediction.  For every live slot i: dt_i = t - t_seen_i.  dt_i > 0: pred_i = p_i + v_i * dt_i per component (product,
+ *      then sum); otherwise pred_i = p_i.
+ *   2. Admissible pairs.  (i, j) is admissible iff slot i is live, point j < n has three finite coordinates, and
+ *      d2_ij = dx dx + dy dy + dz dz < g2 (strict), d = x_j - pred_i, the sum taken in x, y, z order.
+ *   3. Association.  The admissible pairs are taken in ascending lexicographic order of (d2, slot i, point j); a pair is
+ *      committed when neither its slot nor its point has been taken: the greedy global nearest neighbour, a function of the
+ *      state and the frame alone, independent of the order of evaluation.
+ *   4. Matched slot i with point j.  dt_i > 0: u = (x_j - p_i) / dt_i per component (difference, then IEEE division) and
+ *      v_i = v_i + vel_alpha * (u - v_i); otherwise v_i is unchanged.  Then p_i = x_j, t_seen_i = t, missed_i = 0, hits_i += 1.
+ *   5. Unmatched live slot.  missed_i += 1; missed_i > max_missed: the track is retired and its slot is free from this moment,
+ *      this frame's births included.  A coasting track keeps p, v and t_seen: its prediction goes on extrapolating from its
+ *      last sighting.
+ *   6. Births.  The unmatched finite points, in ascending j, each take the LOWEST free slot: id = next_id++, p = x_j, v = 0,
+ *      t_seen = t, missed = 0, hits = 1.  With no free slot the point gets no track, the frame's status carries
+ *      MOCAP_MT_ST_FULL and next_id does not advance.  (The slot rule is part of the contract: slots break ties in step 3.)
+ *
+ * Outputs per frame:
+ *   id [K_max] i32     the track of point j; -1 for slots >= n, non-finite points and points that found no slot
+ *   hits [K_max] i32   that track's hits after this frame, 0 where id is -1 (hits >= 2 hides one-frame ghosts)
+ *   n_tracks i32       live slots after the frame
+ *   status i32         0 | MOCAP_MT_ST_FULL | MOCAP_MT_ST_BAD_TIME
+ * Cutting a session into calls of any lengths gives bit-identical outputs and state.  Every entry point of this section
+ * returns MOCAP_E_ARG before mocap_set_marker_tracker, with the tracker off, or with K_max > 64.
+ * Out of scope: a minimum-cost (Hungarian) assignment, filtering of the positions, identities for rigid bodies, merging or
+ * splitting of tracks, more than 64 points or tracks. */
+#define MOCAP_MT_MAX_TRACKS 64
+#define MOCAP_MT_MAX_POINTS 64
+enum {
+  MOCAP_MT_ST_FULL = 1,     /* a finite point of the frame found no free slot: it has no track */
+  MOCAP_MT_ST_BAD_TIME = 2  /* the frame's time stamp is not finite: no output, the state untouched */
+};
+int mocap_set_marker_tracker(mocap_ctx* ctx, int T_max, double gate, int max_missed, double vel_alpha);
+/* clears all tracks and sets next_id = 0; enqueued on the context's stream */
+int mocap_reset_marker_tracker(mocap_ctx* ctx);
+/* n_frames consecutive frames, in order: t [F], xyz [F][K_max][3], n_pts [F] (mocap_match_triangulate's xyz and n_out) ->
+ * id [F][K_max], hits [F][K_max], n_tracks [F], status [F].  One wave walks the frames, lane = track slot and point.  The
+ * "_dev" form enqueues on the context's stream (for batches); the host form uploads, runs and downloads. */
+int mocap_track_markers(mocap_ctx* ctx, int64_t n_frames, const double* t, int K_max, const double* xyz, const int32_t* n_pts,
+                        int32_t* id, int32_t* hits, int32_t* n_tracks, int32_t* status);
+int mocap_track_markers_dev(mocap_ctx* ctx, int64_t n_frames, const double* d_t, int K_max, const double* d_xyz,
+                            const int32_t* d_n_pts, int32_t* d_id, int32_t* d_hits, int32_t* d_n_tracks, int32_t* d_status);
+/* the live slots in slot order (synchronises): *n of them; id, t_seen, missed, hits [64], pos, vel [64][3] (host) */
+int mocap_get_marker_tracks(mocap_ctx* ctx, int32_t* n, int32_t* id, double* pos, double* vel, double* t_seen, int32_t* missed,
+                            int32_t* hits);
+/* mocap_track_frame / mocap_track_frame_dev with the tracker's outputs appended: t [F] in, mk_id, mk_hits [F][K_max],
+ * mk_n_tracks, mk_status [F] out; every other argument and every shared output as there, bit for bit.  The host form queues
+ * the tracker behind the export; it reads the frame's points where the frame path left them and writes into the same pinned
+ * block as the rest of the payload: still one enqueue and one event wait. */
+int mocap_track_frame_ids(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts, double gate_px,
+                          int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr, int32_t* n_pts, int32_t* status,
+                          int O_max, double* pos, double* heading, double* oerr, int32_t* drone, int32_t* n_obj, const double* t,
+                          int32_t* mk_id, int32_t* mk_hits, int32_t* mk_n_tracks, int32_t* mk_status);
+int mocap_track_frame_ids_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs, const int32_t* d_counts,
+                              double gate_px, int K_max, int64_t G_cap, double* d_xyz, double* d_err, int16_t* d_corr,
+                              int32_t* d_n_pts, int32_t* d_status, int O_max, double* d_pos, double* d_heading, double* d_oerr,
+                              int32_t* d_drone, int32_t* d_n_obj, const double* d_t, int32_t* d_mk_id, int32_t* d_mk_hits,
+                              int32_t* d_mk_n_tracks, int32_t* d_mk_status);
+
 /* ---------------------------------------------------------------- object filter
  * `filtered_objects` of the live loop (helpers.py:109, self.kalman_filter.predict_location(objects)): per drone index a
  * cv.KalmanFilter(9, 6) in float32 (constant acceleration, measurement = position and finite-difference velocity, nearest

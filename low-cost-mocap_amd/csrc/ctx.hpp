@@ -141,6 +141,10 @@ struct mocap_ctx {
   DevBuf objf_state;        // ObjFilterState | h [B] | low-pass history [2][D][4][B] (a call reads one half and writes the other)
   DevBuf objf_ws;           // per call: samples [D][4][F] | slots [F][D][2] | samples appended [D]
   uint32_t objf_calls = 0;  // ... parity selects the half that holds the history
+  // marker tracker (mocap_set_marker_tracker, csrc/marker_track_capi.hip): mt_T == 0 = off
+  int mt_T = 0, mt_max_missed = 0;
+  double mt_g2 = 0.0, mt_alpha = 0.0;
+  DevBuf mt_state;          // MarkerTrackState: the track slots and next_id
   DevBuf calib_ws;          // calibration tail: one partial per workgroup (pair sums | floor factors), csrc/calib_tail.hip
   // preview-stream JPEG encoder (csrc/jpeg_capi.hip): header and divisors of the last (H, T * W, quality), workspace of a chunk
   int jpeg_key[3] = {0, 0, 0};
@@ -211,3 +215,14 @@ struct BodiesIO {
 };
 int bodies_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const BodiesIO& io);
 int bodies_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const BodiesIO& io);
+// marker tracker over the frame path's points (marker_track_capi.hip); every pointer device-accessible; `who` names the entry point
+struct MarkersIO {
+  const double* t;    // [F]
+  int32_t* id;        // [F][K_max]
+  int32_t* hits;      // [F][K_max]
+  int32_t* n_tracks;  // [F]
+  int32_t* status;    // [F]
+};
+int markers_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const MarkersIO& io);
+int markers_times_check(mocap_ctx* ctx, const char* who, int64_t n_frames, const double* t);  // host time stamps: all finite
+int markers_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const MarkersIO& io);

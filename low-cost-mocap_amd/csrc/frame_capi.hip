@@ -742,8 +742,9 @@ struct TrackOut {
 // fo != null (mocap_track_frame_filtered): host time stamps in, the object filter's outputs out -- its two kernels are queued
 // behind the export and write into the same pinned block, the call still waits for one event
 // bo != null (mocap_track_frame_bodies): the rigid-body kernel is queued behind the export in the same way
+// mo != null (mocap_track_frame_ids): host time stamps in, the marker tracker's outputs out, queued in the same way
 int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o,
-                 const FilterIO* fo = nullptr, const JpegOut* jo = nullptr, const BodiesIO* bo = nullptr) {
+                 const FilterIO* fo = nullptr, const JpegOut* jo = nullptr, const BodiesIO* bo = nullptr, const MarkersIO* mo = nullptr) {
   const int64_t n_frames = b.n_frames;
   const int M_max = b.M_max;
   if (!ctx->C) return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_cameras has not been called");
@@ -766,6 +767,11 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     const int rc = bodies_check(ctx, "mocap_track_frame_bodies", n_frames, K_max, *bo);
     if (rc) return rc;
   }
+  if (mo) {
+    int rc = markers_check(ctx, "mocap_track_frame_ids", n_frames, K_max, *mo);
+    if (!rc) rc = markers_times_check(ctx, "mocap_track_frame_ids", n_frames, mo->t);
+    if (rc) return rc;
+  }
   if (jo) {  // the preview stream: the processed frames of the blob stage as one JPEG per frame set
     const char* bad = jpeg::check_args(n_frames, ctx->img_C, ctx->img_S, ctx->img_S, jo->quality, jo->capacity);
     if (bad) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images_jpeg: %s", bad);
@@ -786,6 +792,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   FilterIO hf{};
   const size_t FB = bo ? F * (size_t)bo->B_max : 0;
   BodiesIO hb{bo ? bo->B_max : 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  MarkersIO hm{};
   auto lay_host = [&](void* base) {
     Carver c(base);
     h_blobs = c.take<float>(F * C * M_max * 2);
@@ -822,6 +829,13 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
       hb.rms = c.take<double>(FB);
       hb.score = c.take<double>(FB);
       hb.status = c.take<int32_t>(FB);
+    }
+    if (mo) {
+      hm.t = c.take<double>(F);
+      hm.id = c.take<int32_t>(F * K_max);
+      hm.hits = c.take<int32_t>(F * K_max);
+      hm.n_tracks = c.take<int32_t>(F);
+      hm.status = c.take<int32_t>(F);
     }
     return c.off;
   };
@@ -938,6 +952,11 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
       rc = bodies_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hb);
       if (rc) return rc;
     }
+    if (mo) {  // likewise: the points from device memory, time stamps from and identities into the pinned block
+      memcpy(const_cast<double*>(hm.t), mo->t, sizeof(double) * F);
+      rc = markers_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hm);
+      if (rc) return rc;
+    }
     if (fo) {
       memcpy(const_cast<double*>(hf.t), fo->t, sizeof(double) * F);
       rc = filter_dev_locked(ctx, n_frames, O, h_pos, h_head, h_drone, h_nobj, hf);
@@ -981,6 +1000,12 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     memcpy(bo->rms, hb.rms, sizeof(double) * FB);
     memcpy(bo->score, hb.score, sizeof(double) * FB);
     memcpy(bo->status, hb.status, sizeof(int32_t) * FB);
+  }
+  if (mo) {
+    memcpy(mo->id, hm.id, sizeof(int32_t) * F * K_max);
+    memcpy(mo->hits, hm.hits, sizeof(int32_t) * F * K_max);
+    memcpy(mo->n_tracks, hm.n_tracks, sizeof(int32_t) * F);
+    memcpy(mo->status, hm.status, sizeof(int32_t) * F);
   }
   for (size_t f = 0; f < F && jo; f++) {
     jo->size[f] = h_jsize[f];
@@ -1092,6 +1117,46 @@ extern "C" int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, in
     if (rc) return rc;
   }
   rc = bodies_dev_locked(ctx, n_frames, K_max, d_xyz, d_n_pts, bo);
+  if (rc) return rc;
+  return ctx->mark_enqueued();
+}
+
+// mocap_track_frame / mocap_track_frame_dev with the marker tracker (csrc/marker_track.hip) behind the object search
+extern "C" int mocap_track_frame_ids(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                                     double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr,
+                                     int32_t* n_pts, int32_t* status, int O_max, double* pos, double* heading, double* oerr,
+                                     int32_t* drone, int32_t* n_obj, const double* t, int32_t* mk_id, int32_t* mk_hits,
+                                     int32_t* mk_n_tracks, int32_t* mk_status) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
+  const MarkersIO mo{t, mk_id, mk_hits, mk_n_tracks, mk_status};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, nullptr, nullptr, nullptr, &mo);
+}
+
+extern "C" int mocap_track_frame_ids_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
+                                         const int32_t* d_counts, double gate_px, int K_max, int64_t G_cap, double* d_xyz,
+                                         double* d_err, int16_t* d_corr, int32_t* d_n_pts, int32_t* d_status, int O_max,
+                                         double* d_pos, double* d_heading, double* d_oerr, int32_t* d_drone, int32_t* d_n_obj,
+                                         const double* d_t, int32_t* d_mk_id, int32_t* d_mk_hits, int32_t* d_mk_n_tracks,
+                                         int32_t* d_mk_status) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const MarkersIO mo{d_t, d_mk_id, d_mk_hits, d_mk_n_tracks, d_mk_status};
+  int rc = markers_check(ctx, "mocap_track_frame_ids_dev", n_frames, K_max, mo);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
+  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
+  rc = match_dev_locked(ctx, b, K_max, G_cap, o);
+  if (rc) return rc;
+  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
+  if (rc) return rc;
+  if (O_max > 0) {
+    rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
+    if (rc) return rc;
+  }
+  rc = markers_dev_locked(ctx, n_frames, K_max, d_xyz, d_n_pts, mo);
   if (rc) return rc;
   return ctx->mark_enqueued();
 }

@@ -252,6 +252,33 @@ struct ObjFilterArgs {
 hipError_t launch_object_filter(const ObjFilterArgs& a, hipStream_t stream);  // scan kernel, then low-pass kernel
 hipError_t launch_object_filter_reset(ObjFilterState* state, int D, double now, hipStream_t stream);
 
+// marker tracker (the core's own contract, include/mocap_core.h "marker tracker"), csrc/marker_track.hip: identities of a
+// session's points from frame to frame.  The state of the recurrence lives in one device record per context.
+constexpr int kMtMaxTracks = 64, kMtMaxPoints = 64;  // mirrored from include/mocap_core.h (MOCAP_MT_*)
+constexpr int MT_ST_FULL_ = 1, MT_ST_BAD_TIME_ = 2;
+struct MarkerTrackState {     // all zero = no track, next_id 0
+  int32_t live[kMtMaxTracks], id[kMtMaxTracks];
+  double p[kMtMaxTracks][3], v[kMtMaxTracks][3];
+  double t_seen[kMtMaxTracks];
+  int32_t missed[kMtMaxTracks], hits[kMtMaxTracks];
+  int32_t next_id, pad;
+};
+struct MarkerTrackArgs {
+  int64_t n_frames;
+  int K_max, T_max;           // point slots per frame (<= 64); track slots (1 .. 64)
+  int max_missed;
+  double g2, vel_alpha;       // gate * gate (formed on the host)
+  const double* t;            // [F] time stamps
+  const double* xyz;          // [F][K_max][3]
+  const int32_t* n_pts;       // [F]
+  MarkerTrackState* state;
+  int32_t* id;                // [F][K_max]
+  int32_t* hits;              // [F][K_max]
+  int32_t* n_tracks;          // [F]
+  int32_t* status;            // [F]
+};
+hipError_t launch_marker_tracker(const MarkerTrackArgs& a, hipStream_t stream);
+
 // calibration tail over a capture's frame-path outputs (reference index.py:158-194, :290-309), csrc/calib_tail.hip
 constexpr int kCalibThreads = 256;      // frames per workgroup: the grid is ceil(F / 256), a function of F alone
 constexpr int kPairSlabDoubles = 3;     // per workgroup: sum of pair distances, pairs, frames skipped

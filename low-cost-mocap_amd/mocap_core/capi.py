@@ -41,6 +41,9 @@ RB_DEFAULT_WORK_CAP = 65536   # ... extensions one (frame, body) search may make
 RB_ST_RMS = 1             # per (frame, body): the best assignment's fit has rms > max_rms (not found)
 RB_ST_WORK_CAP = 2        # ... the search needed more than work_cap extensions (not found)
 OPT_F32_ROUNDING = 1
+MT_MAX_TRACKS, MT_MAX_POINTS = 64, 64   # mocap_set_marker_tracker: track slots, points per frame
+MT_ST_FULL = 1            # per frame: a finite point found no free track slot (its id is -1)
+MT_ST_BAD_TIME = 2        # ... the frame's time stamp is not finite: no output, the state untouched
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
@@ -80,6 +83,15 @@ SIGNATURES = {
                                         _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_track_frame_bodies_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                             _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_set_marker_tracker": (_i32, [_vp, _i32, _dbl, _i32, _dbl]),
+    "mocap_reset_marker_tracker": (_i32, [_vp]),
+    "mocap_track_markers": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_markers_dev": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_get_marker_tracks": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_ids": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_ids_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_object_filter": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _dbl, _dbl]),
     "mocap_reset_object_filter": (_i32, [_vp, _dbl]),
     "mocap_filter_objects": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -202,6 +214,7 @@ class MocapCore:
         self.preview_overlay = 0     # OVERLAY_* bits (set_preview_overlay), the library's default
         self.centroid_mode = CENTROID_REFERENCE   # CENTROID_* (set_centroid_mode), the library's default
         self.rigid_bodies_n = 0      # bodies registered by set_rigid_bodies, 0 = none
+        self.marker_tracker = None   # (gate, max_missed, vel_alpha, T_max) of set_marker_tracker, None = off
 
     def close(self):
         if getattr(self, "_h", None):
@@ -717,6 +730,77 @@ class MocapCore:
             _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
             _vp(d_drone or 0), _vp(d_n_obj or 0), int(B_max), _vp(d_found), _vp(d_n_used), _vp(d_assign), _vp(d_R), _vp(d_t),
             _vp(d_rms), _vp(d_score), _vp(d_rb_status)))
+
+    # ------------------------------------------------------------------ marker tracker (identities over time)
+    def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):
+        """mocap_set_marker_tracker: allocates and clears the tracker's state.  gate in metres; max_missed = frames a track may go
+        unseen; vel_alpha in [0, 1]; T_max = track slots (1 .. 64), 0 switches the tracker off.  Settings the core refuses
+        (MOCAP_E_ARG) raise and leave the previous ones, and the state, in force."""
+        self._check(self.lib.mocap_set_marker_tracker(self._h, int(T_max), float(gate), int(max_missed), float(vel_alpha)))
+        self.marker_tracker = (float(gate), int(max_missed), float(vel_alpha), int(T_max)) if int(T_max) else None
+
+    def reset_marker_tracker(self):
+        self._check(self.lib.mocap_reset_marker_tracker(self._h))
+
+    @staticmethod
+    def _marker_outputs(F, K_max):
+        return {"id": np.full((F, K_max), -1, dtype=np.int32), "hits": np.zeros((F, K_max), dtype=np.int32),
+                "n_tracks": np.zeros(F, dtype=np.int32), "mk_status": np.zeros(F, dtype=np.int32)}
+
+    @staticmethod
+    def _marker_ptrs(o):
+        return [_p(o[k]) for k in ("id", "hits", "n_tracks", "mk_status")]
+
+    def track_markers(self, t, xyz, n_pts):
+        """mocap_track_markers over host arrays t [F], xyz [F][K_max][3] (K_max <= 64), n_pts [F], consecutive frames in order ->
+        {"id", "hits" [F][K_max], "n_tracks", "mk_status" [F]}; id -1 = the slot holds no tracked point."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        F, K_max, _ = xyz.shape
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        o = self._marker_outputs(F, K_max)
+        self._check(self.lib.mocap_track_markers(self._h, F, _p(t), K_max, _p(xyz), _p(n_pts), *self._marker_ptrs(o)))
+        return o
+
+    def track_markers_dev(self, n_frames, d_t, K_max, d_xyz, d_n_pts, d_id, d_hits, d_n_tracks, d_status):
+        self._check(self.lib.mocap_track_markers_dev(self._h, int(n_frames), _vp(d_t), int(K_max), _vp(d_xyz), _vp(d_n_pts),
+                                                     _vp(d_id), _vp(d_hits), _vp(d_n_tracks), _vp(d_status)))
+
+    def marker_tracks(self):
+        """mocap_get_marker_tracks (synchronises): the live tracks in slot order, {"id", "missed", "hits" [n], "pos", "vel" [n][3],
+        "t_seen" [n]}."""
+        n = np.zeros(1, dtype=np.int32)
+        o = {"id": np.zeros(MT_MAX_TRACKS, dtype=np.int32), "pos": np.zeros((MT_MAX_TRACKS, 3)), "vel": np.zeros((MT_MAX_TRACKS, 3)),
+             "t_seen": np.zeros(MT_MAX_TRACKS), "missed": np.zeros(MT_MAX_TRACKS, dtype=np.int32),
+             "hits": np.zeros(MT_MAX_TRACKS, dtype=np.int32)}
+        self._check(self.lib.mocap_get_marker_tracks(self._h, _p(n), *[_p(o[k]) for k in ("id", "pos", "vel", "t_seen", "missed", "hits")]))
+        return {k: v[:int(n[0])].copy() for k, v in o.items()}
+
+    def track_frame_ids(self, blobs, counts, t, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8):
+        """mocap_track_frame_ids: track_frame with the marker tracker behind the object search, t [F] = the frames' time stamps;
+        the same dict plus the keys of track_markers.  A frame holds at most 64 points (K_max <= 64); one that needs more is
+        reported like track_frame reports it (status, n_pts) and NOT re-run here: the tracker has consumed the call's frames."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        F, C, M, _ = blobs.shape
+        assert C == self.C and counts.shape == (F, C)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        K_max = min(C * M, 64) if K_max is None else int(K_max)
+        o = self._track_outputs(F, K_max, O_max)
+        o.update(self._marker_outputs(F, K_max))
+        self._check(self.lib.mocap_track_frame_ids(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
+                                                   _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
+                                                   int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
+                                                   _p(o["droneIndex"]), _p(o["n_obj"]), _p(t), *self._marker_ptrs(o)))
+        return o
+
+    def track_frame_ids_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
+                            d_status, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj, d_t, d_id, d_hits, d_n_tracks,
+                            d_mk_status):
+        self._check(self.lib.mocap_track_frame_ids_dev(
+            self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), float(gate_px), int(K_max), int(G_cap), _vp(d_xyz),
+            _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
+            _vp(d_drone or 0), _vp(d_n_obj or 0), _vp(d_t), _vp(d_id), _vp(d_hits), _vp(d_n_tracks), _vp(d_mk_status)))
 
     # ------------------------------------------------------------------ object filter (`filtered_objects`)
     def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):

@@ -49,6 +49,7 @@ _state = {
     "overlay": 0,            # capi.OVERLAY_* bits of set_preview_overlay: the drawings on the preview, off by default
     "centroid": capi.CENTROID_REFERENCE,   # capi.CENTROID_* of set_centroid_mode: integer centroids by default
     "bodies": None,          # set_rigid_bodies: (names, marker arrays, tol, max_rms, work_cap), None = no body registered
+    "markers": None,         # set_marker_tracker: (gate, max_missed, vel_alpha, T_max), None = tracker off
 }
 
 
@@ -512,6 +513,61 @@ def track_frame_bodies(image_points, camera_poses, is_locating_objects=True, O_m
         return np.array([]), np.array([]), [], []
     return (res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else []),
             _bodies_list(res))
+
+
+def set_marker_tracker(gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):
+    """Switches the marker tracker on (mocap_set_marker_tracker, include/mocap_core.h) and clears its tracks: from now on
+    track_markers() / track_frame_ids() give every object point an id that it keeps from frame to frame.  gate = how far (in the
+    unit of the object points) a marker may be from its constant-velocity prediction; max_missed = frames it may go unseen;
+    vel_alpha in [0, 1] = weight of the newest velocity; T_max = track slots (1 .. 64), 0 switches the tracker off.  Settings
+    the core refuses raise capi.MocapError and change nothing."""
+    with _state["lock"]:
+        get_core().set_marker_tracker(gate=gate, max_missed=max_missed, vel_alpha=vel_alpha, T_max=T_max)
+        _state["markers"] = (float(gate), int(max_missed), float(vel_alpha), int(T_max)) if int(T_max) else None
+
+
+def _markers_core():
+    """The tracker lives in the context: a core handed over by set_core gets the settings on first use (callers hold the lock)."""
+    core = get_core()
+    reg = _state["markers"]
+    if reg is not None and getattr(core, "marker_tracker", None) != reg:
+        core.set_marker_tracker(gate=reg[0], max_missed=reg[1], vel_alpha=reg[2], T_max=reg[3])
+    return core
+
+
+def track_markers(object_points, now=None):
+    """The ids of one frame's object points (at most 64), in their order: list of int, -1 = the point has no track (not finite,
+    or every track slot taken).  Frames are handed over in time order; `now` defaults to time.time().  Needs
+    set_marker_tracker()."""
+    now = time.time() if now is None else float(now)
+    P = np.asarray(object_points, dtype=np.float64).reshape(-1, 3)
+    n = P.shape[0]
+    with _state["lock"]:
+        res = _markers_core().track_markers([now], P[None] if n else np.zeros((1, 1, 3)), [n])
+    return res["id"][0, :n].astype(int).tolist()
+
+
+def track_frame_ids(image_points, camera_poses, now=None, is_locating_objects=True, O_max=8):
+    """track_frame with the marker tracker in the same core call.  Returns (errors, object_points, objects, ids): track_frame's
+    three values and the list track_markers returns for the frame's object points.  `now` defaults to time.time()."""
+    now = time.time() if now is None else float(now)
+    for image_points_i in image_points:
+        try:
+            image_points_i.remove([None, None])
+        except Exception:
+            pass
+    with _state["lock"]:
+        core = _upload_cameras(camera_poses)
+        _markers_core()
+        blobs, counts, _ = pack_frame(image_points)
+        res = core.track_frame_ids(blobs, counts, [now], gate_px=5.0, O_max=O_max if is_locating_objects else 0)
+    if int(res["status"][0]) != 0:
+        raise capi.MocapError(_status_message(int(res["status"][0])))
+    k = int(res["n_pts"][0])
+    if k == 0:
+        return np.array([]), np.array([]), [], []
+    return (res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else []),
+            res["id"][0, :k].astype(int).tolist())
 
 
 def _filtered_list(res, f=0):
