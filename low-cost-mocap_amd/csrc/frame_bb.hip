@@ -425,7 +425,10 @@ struct BBState {
   // The next frame's blobs and counts travel from HBM straight into the spare LDS buffer while the current frame is
   // searched (global_load_lds: no VGPR is held -- a register prefetch was spilled to scratch by the compiler, i.e. went
   // to HBM and back): neither the queue atomic nor the first touch of a frame sits on the per-frame critical path.
-  // The loads complete before the frame's last barrier (wait_own_stores: vmcnt(0) counts them).
+  // They are issued behind the matching and waited for at the search's entry (search(): the compiler waits for them before the
+  // first LDS access that follows anyway -- it cannot tell their LDS target from any other address), so what they overlap is the
+  // frame's bookkeeping stores and the other workgroups of the CU; a frame without candidates waits at its last barrier
+  // (wait_own_stores: vmcnt(0) counts them).
   __device__ __forceinline__ void prefetch_lds(int64_t frame) const {
     const int C = cn();
     const float* src = p.blobs + (size_t)frame * C * M * 2;
@@ -1050,6 +1053,14 @@ struct BBState {
     fresh_tid();
     const int C = cn();
     (void)C;
+    // Barriers: the rounds of the search exchange LDS state only, so its inner barriers are block_sync_lds_only() -- a round
+    // does not wait for the L2 acknowledgement of its winner-record stores (phase E reads them behind wait_own_stores() and the
+    // search's LAST barrier, which stays a full one).
+    // The wait below: the compiler cannot tell the prefetch's LDS target from any other LDS address and waits for vmcnt(0)
+    // before the first LDS access behind a global_load_lds on every path that has not waited yet -- with the frame's prefetch
+    // pending that was before each view's blob read and each delivery atomic of the evaluation (11 waits per pass, each also
+    // a wait for the pass's record stores).  One wait it can see, here, where the first LDS read would have waited anyway.
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) alone (gfx9 encoding: expcnt 7, lgkmcnt 15)
     const int nroots = misc[MI_NROOTS];
     // queued records | their candidates << 10.  Two words that take turns: a flush moves on to the other one (zero since the
     // flush before), and lane 0 zeroes the one just used behind the round's barrier -- nobody touches it until the next
@@ -1125,7 +1136,7 @@ struct BBState {
           atomicMax(&seedkey[r], my_key);
         }
       }
-      __syncthreads();
+      block_sync_lds_only();
       if (nblocks <= (uint32_t)T) {
         if (my_r >= 0 && seedkey[my_r] == my_key) {  // (keys are unique inside a root: exactly one lane per root with blocks)
           seedgh[my_r] = my_gh;
@@ -1143,7 +1154,7 @@ struct BBState {
         }
       }
       bb_prio<kPrioEval>();
-      __syncthreads();
+      block_sync_lds_only();
     }
     // ---- 2. the queued records' candidates (spread over all lanes, whatever root they belong to), then the next
     // blocks' tests, until nothing is left
@@ -1179,7 +1190,7 @@ struct BBState {
               return true;
             };
             const double bound = __longlong_as_double((long long)rbound[r]);
-            solve_and_score<!PERK, true, F32R, false>(cv, B, v, obs_p, X, e, bound * (double)(2 * v) * (1.0 + 0x1p-40), ec);
+            solve_and_score<!PERK, true, F32R, false, 1, true>(cv, B, v, obs_p, X, e, bound * (double)(2 * v) * (1.0 + 0x1p-40), ec);
 #ifdef MOCAP_DEBUG_EIGCHECK  // self-check build: a candidate whose evaluation was cut short must not beat the bound it was cut against
             if (!(e < inf)) {
               double B2[10], X2[3], e2;
@@ -1225,7 +1236,7 @@ struct BBState {
             if (holder && slot_g[ss] == gword) store_winner(ss, X, pk);
           }
         }
-        __syncthreads();  // every lane is done with the records: new ones may be queued (through the other counter)
+        block_sync_lds_only();  // every lane is done with the records: new ones may be queued (through the other counter)
         if (tid == 0) *ctr = 0;
         {
           int32_t* t = ctr;
@@ -1292,9 +1303,9 @@ struct BBState {
 #endif
         }
       }
-      __syncthreads();
+      block_sync_lds_only();
       if (do_push) push_block(r, gh, pk);
-      __syncthreads();
+      block_sync_lds_only();
     }
     wait_own_stores();  // the winners' records have reached L2 (stores are acknowledged from there) before any lane reads one
     __syncthreads();

@@ -28,7 +28,7 @@
     st.match();
     bb_prio<kPrioEval>();
     const int next = st.misc[MI_NEXT];
-    if (next >= 0) st.prefetch_lds(next);  // in flight during the search
+    if (next >= 0) st.prefetch_lds(next);  // in flight until the search's entry (BBState::search) or the frame's last barrier
     if (tid == 0) {
       const int status = st.misc[MI_STATUS];
       p.n_out[frame] = status ? 0 : st.misc[MI_NOUT];

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace mocap {
 
@@ -102,6 +103,14 @@ __device__ __forceinline__ void block_sync_lds() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
 }
+
+// A workgroup barrier for state that lives in LDS ALONE: the wave's LDS accesses retired, then the bare barrier.  __syncthreads()
+// carries a workgroup-scope fence over global memory as well, which on gfx9 -- one counter for loads and stores -- is
+// s_waitcnt vmcnt(0): every global store of the wave acknowledged by L2 and every global_load_lds landed, at EVERY barrier.
+// For barriers between which the waves exchange nothing through global memory (the search's rounds: the winners' records are
+// read behind wait_own_stores() + __syncthreads() at its end, the prefetched frame behind the frame's last barrier).  The asm is
+// a compiler barrier too ("memory"): no LDS or global access moves across it.
+__device__ __forceinline__ void block_sync_lds_only() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ double rsqrt_pos(double d) {
   const double y = __builtin_amdgcn_rsq(d);
@@ -357,7 +366,7 @@ __device__ __forceinline__ void reproject_sq(Tab RT, ctab_t K4, const double (&X
 //   F32R: reproduce OpenCV's float32 roundings (MOCAP_OPT_F32_ROUNDING).
 // Returns the number of views; X / err are valid when it is >= 2.
 // Second half of triangulate_and_score: null vector of B (v views accumulated), point, reprojection error.
-template <bool UNIFORM_K, bool PAIRWISE, bool F32R, int BATCH = 1, class View, class Obs2>
+template <bool UNIFORM_K, bool PAIRWISE, bool F32R, int BATCH = 1, bool BORN = false, class View, class Obs2>
 __device__ __forceinline__ void score_point(const View& cv, int v, Obs2&& obs2, const double (&X)[3], double& err,
                                             double limit);
 
@@ -370,7 +379,7 @@ __device__ __forceinline__ void score_point(const View& cv, int v, Obs2&& obs2, 
 // of frame_bb.hip, whose survivors are mostly near-winners, it costs more than it cuts (5.77 vs 6.00 ms per 100 k
 // frames, round 3) and is compiled out there.
 // BATCH > 1: obs2 is a functor with raw(c) / decode(raw, x, y) next to operator() -- see triangulate_and_score.
-template <bool UNIFORM_K, bool PAIRWISE, bool F32R, bool DEPTH_CUT = true, int BATCH = 1, class View, class Obs2>
+template <bool UNIFORM_K, bool PAIRWISE, bool F32R, bool DEPTH_CUT = true, int BATCH = 1, bool BORN = false, class View, class Obs2>
 __device__ __forceinline__ void solve_and_score(const View& cv, double (&B)[10], int v, Obs2&& obs2,
                                                 double (&X)[3], double& err,
                                                 double limit = __builtin_huge_val(), const EigCut& ec = EigCut{}) {
@@ -428,7 +437,7 @@ __device__ __forceinline__ void solve_and_score(const View& cv, double (&B)[10],
       return;
     }
   }
-  score_point<UNIFORM_K, PAIRWISE, F32R, BATCH>(cv, v, obs2, X, err, limit);
+  score_point<UNIFORM_K, PAIRWISE, F32R, BATCH, BORN>(cv, v, obs2, X, err, limit);
 }
 
 // The point alone (helpers.py:318-321) of a group whose DLT matrix is B: solve_and_score's arithmetic up to the point,
@@ -443,7 +452,7 @@ __device__ __forceinline__ void solve_point(double (&B)[10], double (&X)[3]) {
 }
 
 // calculate_reprojection_error (helpers.py:214-241) of a GIVEN point X seen by v cameras.
-template <bool UNIFORM_K, bool PAIRWISE, bool F32R, int BATCH, class View, class Obs2>
+template <bool UNIFORM_K, bool PAIRWISE, bool F32R, int BATCH, bool BORN, class View, class Obs2>
 __device__ __forceinline__ void score_point(const View& cv, int v, Obs2&& obs2, const double (&X)[3], double& err,
                                             double limit) {
   const int C = cv.C;
@@ -460,31 +469,80 @@ __device__ __forceinline__ void score_point(const View& cv, int v, Obs2&& obs2, 
   const int C4 = C & ~3;
   double seq = 0.0, r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int j = 0;
-  for (int c0 = 0; c0 < C4; c0 += 4) {
-    if (!(seq <= limit)) continue;  // cut short: whole waves skip the block once every lane is out
-    unsigned long long rw[4] = {0, 0, 0, 0};
-    if constexpr (BATCH > 1) {  // the four observations are fetched before any of them is used
+  // One group of four cameras.  FIRST (BORN: cameras 0-3): the partial sums are born here -- a view's pair is its two squares, or
+  // zeros when the camera is not seen -- instead of being zeroed up front and added to under the view's exec mask: with eight
+  // zeros live across every view's region the compiler re-materialised them before each region (52 moves per evaluation of
+  // the headline search kernel; 44 of them are gone).  0.0 + s = s bit for bit for a square s (never -0.0), NaN included.  The first group
+  // is not guarded by the limit either: seq is 0 there, and a limit that 0 does not pass (negative, NaN) fails the final test
+  // whatever the sum of non-negative terms comes to -- the same +inf, without an exec region around four views.
+  // BORN is the search kernels' (csrc/frame_bb.hip); without it the loop below is the one every other kernel has always had: in
+  // the wide, heavy and general kernels, at their register ceilings, the new form cost registers (heavy_bb_kernel 55 -> 61
+  // spilled, heavy_enum_kernel 168 -> 172 VGPRs).
+  if constexpr (BORN) {
+    auto group = [&](int c0, auto first) {
+      constexpr bool FIRST = decltype(first)::value;
+      unsigned long long rw[4] = {0, 0, 0, 0};
+      if constexpr (BATCH > 1) {
 #pragma unroll
-      for (int u = 0; u < 4; u++) rw[u] = obs2.raw(c0 + u);
-    }
+        for (int u = 0; u < 4; u++) rw[u] = obs2.raw(c0 + u);
+      }
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
-      double x, y;
-      bool seen;
-      if constexpr (BATCH > 1)
-        seen = obs2.decode(rw[u], x, y);
-      else
-        seen = obs2(c0 + u, x, y);
-      if (seen) {
-        double du2, dv2;
-        reproject_sq<F32R>(cv.rt(12 * (c0 + u)), cv.k4(4 * (UNIFORM_K ? 0 : j)), Xp, x, y, du2, dv2);
-        seq = seq + du2;
-        seq = seq + dv2;
-        if (PAIRWISE) {
-          r[2 * u] = r[2 * u] + du2;
-          r[2 * u + 1] = r[2 * u + 1] + dv2;
+      for (int u = 0; u < 4; u++) {
+        double x, y;
+        bool seen;
+        if constexpr (BATCH > 1)
+          seen = obs2.decode(rw[u], x, y);
+        else
+          seen = obs2(c0 + u, x, y);
+        double du2 = 0.0, dv2 = 0.0;
+        if (seen) {
+          reproject_sq<F32R>(cv.rt(12 * (c0 + u)), cv.k4(4 * (UNIFORM_K ? 0 : j)), Xp, x, y, du2, dv2);
+          seq = seq + du2;
+          seq = seq + dv2;
+          if (PAIRWISE && !FIRST) {
+            r[2 * u] = r[2 * u] + du2;
+            r[2 * u + 1] = r[2 * u + 1] + dv2;
+          }
+          j++;
         }
-        j++;
+        if (PAIRWISE && FIRST) {
+          r[2 * u] = du2;
+          r[2 * u + 1] = dv2;
+        }
+      }
+    };
+    if (C4 > 0) group(0, std::true_type{});
+    for (int c0 = 4; c0 < C4; c0 += 4) {
+      if (!(seq <= limit)) continue;  // cut short: whole waves skip the block once every lane is out
+      group(c0, std::false_type{});
+    }
+  } else {
+    for (int c0 = 0; c0 < C4; c0 += 4) {
+      if (!(seq <= limit)) continue;  // cut short: whole waves skip the block once every lane is out
+      unsigned long long rw[4] = {0, 0, 0, 0};
+      if constexpr (BATCH > 1) {  // the four observations are fetched before any of them is used
+#pragma unroll
+        for (int u = 0; u < 4; u++) rw[u] = obs2.raw(c0 + u);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        double x, y;
+        bool seen;
+        if constexpr (BATCH > 1)
+          seen = obs2.decode(rw[u], x, y);
+        else
+          seen = obs2(c0 + u, x, y);
+        if (seen) {
+          double du2, dv2;
+          reproject_sq<F32R>(cv.rt(12 * (c0 + u)), cv.k4(4 * (UNIFORM_K ? 0 : j)), Xp, x, y, du2, dv2);
+          seq = seq + du2;
+          seq = seq + dv2;
+          if (PAIRWISE) {
+            r[2 * u] = r[2 * u] + du2;
+            r[2 * u + 1] = r[2 * u + 1] + dv2;
+          }
+          j++;
+        }
       }
     }
   }
