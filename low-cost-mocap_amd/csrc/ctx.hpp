@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "io_fields.hpp"
 #include "kernels.hpp"
 
 #define HIP_TRY(ctx, expr)                                     \
@@ -39,23 +40,6 @@ struct Event : Owned {
   hipEvent_t ev = nullptr;
   hipError_t ready() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }  // created by its first user
   ~Event() { if (ev) (void)hipEventDestroy(ev); }
-};
-
-// Sub-buffers of one allocation, each padded to `align` bytes.  A layout is ONE function that takes its fields from a
-// Carver and returns `off`: run on a null base it gives the size to reserve, run on the buffer it gives the pointers.
-struct Carver {
-  uintptr_t base;
-  size_t align, off = 0;
-  explicit Carver(void* b, size_t align_ = 256) : base((uintptr_t)b), align(align_) {}
-  template <class T>
-  static size_t padded(size_t count, size_t align = 256) { return (sizeof(T) * count + align - 1) / align * align; }
-  template <class T>
-  T* take(size_t count) {
-    T* p = (T*)(base + off);
-    off += padded<T>(count, align);
-    return p;
-  }
-  void align_to(size_t a) { off = (off + a - 1) / a * a; }
 };
 
 struct mocap_ctx {
@@ -190,39 +174,22 @@ struct JpegOut {
 int locate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const double* d_err,
                       const int32_t* d_n_pts, int O_max, double* d_pos, double* d_heading, double* d_oerr,
                       int32_t* d_drone, int32_t* d_lead, int32_t* d_n_obj);
-// object filter over the locator's outputs (object_filter_capi.hip); every pointer device-accessible; `who` names the entry point
-struct FilterIO {
-  const double* t;  // [F]
-  float* fpos;      // [F][D][3]
-  float* fvel;      // [F][D][3]
-  double* fheading; // [F][D]
-  int32_t* chosen;  // [F][D]
-};
+// the optional stages of the live loop (io_fields.hpp); `who` names the entry point in a check's message
 int filter_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int O_max, const FilterIO& io);
 int filter_dev_locked(mocap_ctx* ctx, int64_t n_frames, int O_max, const double* d_pos, const double* d_heading,
                       const int32_t* d_drone, const int32_t* d_n_obj, const FilterIO& io);
-// rigid bodies over the frame path's points (rigid_body_capi.hip); every pointer device-accessible, arrays [F][B_max]; `who` names the entry point
-struct BodiesIO {
-  int B_max;        // body slots per frame (>= the registered bodies; the slots beyond them are zero-filled)
-  int32_t* found;
-  int32_t* n_used;
-  int8_t* assign;   // [F][B_max][8]
-  double* R;        // [F][B_max][9]
-  double* t;        // [F][B_max][3]
-  double* rms;
-  double* score;
-  int32_t* status;
-};
 int bodies_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const BodiesIO& io);
 int bodies_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const BodiesIO& io);
-// marker tracker over the frame path's points (marker_track_capi.hip); every pointer device-accessible; `who` names the entry point
-struct MarkersIO {
-  const double* t;    // [F]
-  int32_t* id;        // [F][K_max]
-  int32_t* hits;      // [F][K_max]
-  int32_t* n_tracks;  // [F]
-  int32_t* status;    // [F]
-};
 int markers_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const MarkersIO& io);
 int markers_times_check(mocap_ctx* ctx, const char* who, int64_t n_frames, const double* t);  // host time stamps: all finite
 int markers_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const MarkersIO& io);
+
+// copier for copy_fields (io_fields.hpp) on the context's stream
+struct StreamCopy {
+  mocap_ctx* ctx;
+  hipMemcpyKind kind;
+  int operator()(void* dst, const void* src, size_t bytes) const {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
+    return 0;
+  }
+};

@@ -1,6 +1,8 @@
 // frame_capi.hip -- C ABI of the frame path (include/mocap_core.h): which kernel a batch takes (plan_frame), the
 // launch (match_dev_locked), the device-side re-submit of frames that hit a cap (resubmit_dev_locked), the host and
-// "_dev" entry points built from them, and the live loop in one call (mocap_track_*).  Host runtime only.
+// "_dev" entry points built from them, and the live loop in one call (mocap_track_*): track_locked behind the host forms,
+// track_dev_locked behind the device forms, the optional stages handed to both as one TrackStages and laid out, staged and
+// copied back through their field lists (io_fields.hpp).  Host runtime only.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -735,16 +737,30 @@ namespace {
 struct TrackOut {
   FrameOut pts;  // (corr optional, n_cand unused)
   int O_max; double* pos; double* heading; double* oerr; int32_t* drone; int32_t* n_obj;
-  float* blobs; int32_t* counts; int32_t* blob_status;
+  float* blobs = nullptr; int32_t* counts = nullptr; int32_t* blob_status = nullptr;  // (the forms that take raw frames)
 };
 
-// images != null: raw frames [F][C][rows][cols][3] (host); else b.blobs / b.counts (host) are the input
-// fo != null (mocap_track_frame_filtered): host time stamps in, the object filter's outputs out -- its two kernels are queued
-// behind the export and write into the same pinned block, the call still waits for one event
-// bo != null (mocap_track_frame_bodies): the rigid-body kernel is queued behind the export in the same way
-// mo != null (mocap_track_frame_ids): host time stamps in, the marker tracker's outputs out, queued in the same way
+// the optional stages behind the object search, null = off; an entry point hands over the one it carries
+struct TrackStages {
+  const FilterIO* filter = nullptr;    // mocap_track_frame_filtered: time stamps in, the object filter's outputs out
+  const JpegOut* jpeg = nullptr;       // mocap_track_frame_images_jpeg: the preview stream
+  const BodiesIO* bodies = nullptr;    // mocap_track_frame_bodies: the rigid-body locator
+  const MarkersIO* markers = nullptr;  // mocap_track_frame_ids: time stamps in, the marker tracker's outputs out
+  TrackStages() = default;
+  TrackStages(const FilterIO& io) : filter(&io) {}
+  TrackStages(const JpegOut& io) : jpeg(&io) {}
+  TrackStages(const BodiesIO& io) : bodies(&io) {}
+  TrackStages(const MarkersIO& io) : markers(&io) {}
+};
+
+// images != null: raw frames [F][C][rows][cols][3] (host); else b.blobs / b.counts (host) are the input.  The filter, the
+// bodies and the markers are described once (io_fields.hpp): their arrays are carved from the same pinned block as the frame's
+// outputs, their kernels are queued behind the export and write into that block, their outputs are copied to the caller -- the
+// call still waits for one event.  The JPEG stream stays written out here: its slots have a 16-byte stride in the block and only
+// the bytes that exist are copied back, which no field list says.
 int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o,
-                 const FilterIO* fo = nullptr, const JpegOut* jo = nullptr, const BodiesIO* bo = nullptr, const MarkersIO* mo = nullptr) {
+                 const TrackStages& stages = {}) {
+  const JpegOut* jo = stages.jpeg;
   const int64_t n_frames = b.n_frames;
   const int M_max = b.M_max;
   if (!ctx->C) return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_cameras has not been called");
@@ -759,19 +775,12 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (images && (!ctx->img_C || ctx->img_C != ctx->C))
     return ctx->fail(MOCAP_E_NOCAMS, "mocap_set_image_params has not been called for this camera set");
   if (images && (!o.blobs || !o.counts || !o.blob_status)) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images: null blob buffer");
-  if (fo) {
-    const int rc = filter_check(ctx, "mocap_track_frame_filtered", n_frames, o.O_max, *fo);
-    if (rc) return rc;
-  }
-  if (bo) {
-    const int rc = bodies_check(ctx, "mocap_track_frame_bodies", n_frames, K_max, *bo);
-    if (rc) return rc;
-  }
-  if (mo) {
-    int rc = markers_check(ctx, "mocap_track_frame_ids", n_frames, K_max, *mo);
-    if (!rc) rc = markers_times_check(ctx, "mocap_track_frame_ids", n_frames, mo->t);
-    if (rc) return rc;
-  }
+  int rc = MOCAP_OK;
+  if (stages.filter) rc = filter_check(ctx, "mocap_track_frame_filtered", n_frames, o.O_max, *stages.filter);
+  if (!rc && stages.bodies) rc = bodies_check(ctx, "mocap_track_frame_bodies", n_frames, K_max, *stages.bodies);
+  if (!rc && stages.markers) rc = markers_check(ctx, "mocap_track_frame_ids", n_frames, K_max, *stages.markers);
+  if (!rc && stages.markers) rc = markers_times_check(ctx, "mocap_track_frame_ids", n_frames, stages.markers->t);
+  if (rc) return rc;
   if (jo) {  // the preview stream: the processed frames of the blob stage as one JPEG per frame set
     const char* bad = jpeg::check_args(n_frames, ctx->img_C, ctx->img_S, ctx->img_S, jo->quality, jo->capacity);
     if (bad) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images_jpeg: %s", bad);
@@ -779,19 +788,19 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int C = ctx->C, O = o.O_max > 0 ? o.O_max : 1;
-  const size_t F = (size_t)n_frames, FD = fo ? F * ctx->objf_D : 0;
+  const size_t F = (size_t)n_frames;
+  const IoDims n{F, (size_t)K_max, stages.bodies ? (size_t)stages.bodies->B_max : 0, (size_t)ctx->objf_D};
   const size_t n_raw = images ? F * C * (size_t)ctx->img_rows * ctx->img_cols * 3 : 0;
   const size_t j_stride = jo ? ((size_t)jo->capacity + 15) / 16 * 16 : 0;  // slots the export kernel copies 16 bytes at a time
   uint8_t* h_jpeg = nullptr;
   int64_t* h_jsize = nullptr;
-  // caller-visible side (pinned host memory): inputs | frame outputs | objects
+  // caller-visible side (pinned host memory): inputs | frame outputs | objects | the stages' arrays
   float* h_blobs;
   int32_t *h_counts, *h_bstat, *h_drone, *h_nobj;
   FrameOut h;
   double *h_pos, *h_head, *h_oerr;
   FilterIO hf{};
-  const size_t FB = bo ? F * (size_t)bo->B_max : 0;
-  BodiesIO hb{bo ? bo->B_max : 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  BodiesIO hb{(int)n.B};
   MarkersIO hm{};
   auto lay_host = [&](void* base) {
     Carver c(base);
@@ -809,34 +818,13 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     h_oerr = c.take<double>(F * O);
     h_drone = c.take<int32_t>(F * O);
     h_nobj = c.take<int32_t>(F);
-    if (fo) {
-      hf.t = c.take<double>(F);
-      hf.fpos = c.take<float>(FD * 3);
-      hf.fvel = c.take<float>(FD * 3);
-      hf.fheading = c.take<double>(FD);
-      hf.chosen = c.take<int32_t>(FD);
-    }
+    if (stages.filter) carve(c, hf, n);
     if (jo) {
       h_jpeg = c.take<uint8_t>(F * j_stride);
       h_jsize = c.take<int64_t>(F);
     }
-    if (bo) {
-      hb.found = c.take<int32_t>(FB);
-      hb.n_used = c.take<int32_t>(FB);
-      hb.assign = c.take<int8_t>(FB * kRbMaxMarkers);
-      hb.R = c.take<double>(FB * 9);
-      hb.t = c.take<double>(FB * 3);
-      hb.rms = c.take<double>(FB);
-      hb.score = c.take<double>(FB);
-      hb.status = c.take<int32_t>(FB);
-    }
-    if (mo) {
-      hm.t = c.take<double>(F);
-      hm.id = c.take<int32_t>(F * K_max);
-      hm.hits = c.take<int32_t>(F * K_max);
-      hm.n_tracks = c.take<int32_t>(F);
-      hm.status = c.take<int32_t>(F);
-    }
+    if (stages.bodies) carve(c, hb, n);
+    if (stages.markers) carve(c, hm, n);
     return c.off;
   };
   const size_t host_total = lay_host(nullptr);
@@ -941,27 +929,21 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     in.counts = st_counts;
   }
   {
-    int rc = match_dev_locked(ctx, in, K_max, G_cap, d);
+    rc = match_dev_locked(ctx, in, K_max, G_cap, d);
     if (rc) return rc;
     // frames that hit a cap (candidates, hit lists, roots): re-run, those frames only, with the largest caps the core has --
     // the reference has none (helpers.py:394-400) -- before the export; queued behind the first pass, no host round trip
     rc = resubmit_dev_locked(ctx, in, K_max, d, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, launch_track_export(la, ea, ctx->stream));
-    if (bo) {  // the frame's points where the frame path left them (device memory), the bodies into the pinned block
-      rc = bodies_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hb);
-      if (rc) return rc;
-    }
-    if (mo) {  // likewise: the points from device memory, time stamps from and identities into the pinned block
-      memcpy(const_cast<double*>(hm.t), mo->t, sizeof(double) * F);
-      rc = markers_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hm);
-      if (rc) return rc;
-    }
-    if (fo) {
-      memcpy(const_cast<double*>(hf.t), fo->t, sizeof(double) * F);
-      rc = filter_dev_locked(ctx, n_frames, O, h_pos, h_head, h_drone, h_nobj, hf);
-      if (rc) return rc;
-    }
+    // the stages read the frame's points where the frame path left them (device memory), the filter the export's objects in
+    // the pinned block; time stamps travel through that block, every output lands in it
+    if (stages.bodies) rc = bodies_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hb);
+    if (!rc && stages.markers) rc = copy_fields<true>(hm, *stages.markers, n, HostCopy{});
+    if (!rc && stages.markers) rc = markers_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hm);
+    if (!rc && stages.filter) rc = copy_fields<true>(hf, *stages.filter, n, HostCopy{});
+    if (!rc && stages.filter) rc = filter_dev_locked(ctx, n_frames, O, h_pos, h_head, h_drone, h_nobj, hf);
+    if (rc) return rc;
     if (jo) {  // encoded in device memory, then the bytes that exist travel into the pinned block 16 at a time
       if (ctx->preview_overlay & kOverlayEpilines) {  // the points' epipolar lines, over the blob stage's own drawings
         rc = epilines_dev_locked(ctx, "mocap_track_frame_images_jpeg", n_frames, ctx->img_S, d_proc, M_max, d_blobs, d_counts, K_max,
@@ -985,28 +967,9 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     memcpy(o.oerr + f * O, h_oerr + f * O, sizeof(double) * no);
     memcpy(o.drone + f * O, h_drone + f * O, sizeof(int32_t) * no);
   }
-  if (fo) {
-    memcpy(fo->fpos, hf.fpos, sizeof(float) * FD * 3);
-    memcpy(fo->fvel, hf.fvel, sizeof(float) * FD * 3);
-    memcpy(fo->fheading, hf.fheading, sizeof(double) * FD);
-    memcpy(fo->chosen, hf.chosen, sizeof(int32_t) * FD);
-  }
-  if (bo && FB) {
-    memcpy(bo->found, hb.found, sizeof(int32_t) * FB);
-    memcpy(bo->n_used, hb.n_used, sizeof(int32_t) * FB);
-    memcpy(bo->assign, hb.assign, FB * kRbMaxMarkers);
-    memcpy(bo->R, hb.R, sizeof(double) * FB * 9);
-    memcpy(bo->t, hb.t, sizeof(double) * FB * 3);
-    memcpy(bo->rms, hb.rms, sizeof(double) * FB);
-    memcpy(bo->score, hb.score, sizeof(double) * FB);
-    memcpy(bo->status, hb.status, sizeof(int32_t) * FB);
-  }
-  if (mo) {
-    memcpy(mo->id, hm.id, sizeof(int32_t) * F * K_max);
-    memcpy(mo->hits, hm.hits, sizeof(int32_t) * F * K_max);
-    memcpy(mo->n_tracks, hm.n_tracks, sizeof(int32_t) * F);
-    memcpy(mo->status, hm.status, sizeof(int32_t) * F);
-  }
+  if (stages.filter) copy_fields<false>(*stages.filter, hf, n, HostCopy{});
+  if (stages.bodies) copy_fields<false>(*stages.bodies, hb, n, HostCopy{});
+  if (stages.markers) copy_fields<false>(*stages.markers, hm, n, HostCopy{});
   for (size_t f = 0; f < F && jo; f++) {
     jo->size[f] = h_jsize[f];
     memcpy(jo->jpeg + f * (size_t)jo->capacity, h_jpeg + f * j_stride, (size_t)(h_jsize[f] < jo->capacity ? h_jsize[f] : jo->capacity));
@@ -1022,6 +985,27 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   return MOCAP_OK;
 }
 
+// The device forms (mocap_track_frame*_dev; `who` names the entry point): the stage's own check first, then frame pass ->
+// device-side re-submit of the frames that hit a cap -> object search -> the stage, all queued, nothing waited for.  The
+// object search is skipped at O_max = 0 -- except in front of the filter, whose check demands O_max >= 1.
+int track_dev_locked(mocap_ctx* ctx, const char* who, const FrameBatch& b, int K_max, int64_t G_cap, const TrackOut& o,
+                     const TrackStages& stages) {
+  int rc = MOCAP_OK;
+  if (stages.filter) rc = filter_check(ctx, who, b.n_frames, o.O_max, *stages.filter);
+  if (!rc && stages.bodies) rc = bodies_check(ctx, who, b.n_frames, K_max, *stages.bodies);
+  if (!rc && stages.markers) rc = markers_check(ctx, who, b.n_frames, K_max, *stages.markers);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = match_dev_locked(ctx, b, K_max, G_cap, o.pts);
+  if (!rc) rc = resubmit_dev_locked(ctx, b, K_max, o.pts, nullptr);
+  if (!rc && (stages.filter || o.O_max > 0))
+    rc = locate_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.err, o.pts.n_out, o.O_max, o.pos, o.heading, o.oerr, o.drone, nullptr, o.n_obj);
+  if (!rc && stages.bodies) rc = bodies_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, *stages.bodies);
+  if (!rc && stages.markers) rc = markers_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, *stages.markers);
+  if (!rc && stages.filter) rc = filter_dev_locked(ctx, b.n_frames, o.O_max, o.pos, o.heading, o.drone, o.n_obj, *stages.filter);
+  return rc ? rc : ctx->mark_enqueued();
+}
+
 }  // namespace
 
 extern "C" int mocap_track_frame(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
@@ -1030,7 +1014,7 @@ extern "C" int mocap_track_frame(mocap_ctx* ctx, int64_t n_frames, int M_max, co
                                  int32_t* drone, int32_t* n_obj) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj};
   return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o);
 }
 
@@ -1054,8 +1038,8 @@ extern "C" int mocap_track_frame_images_jpeg(mocap_ctx* ctx, int64_t n_frames, c
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!images) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images_jpeg: null image buffer");
   const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, blobs, counts, blob_status};
-  const JpegOut jo{quality, jpeg, capacity, jpeg_size};
-  return track_locked(ctx, images, FrameBatch{n_frames, M_max, nullptr, nullptr, gate_px}, K_max, G_cap, o, nullptr, &jo);
+  const JpegOut io{quality, jpeg, capacity, jpeg_size};
+  return track_locked(ctx, images, FrameBatch{n_frames, M_max, nullptr, nullptr, gate_px}, K_max, G_cap, o, io);
 }
 
 extern "C" int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
@@ -1064,19 +1048,8 @@ extern "C" int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max
                                      double* d_pos, double* d_heading, double* d_oerr, int32_t* d_drone, int32_t* d_n_obj) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
-  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
-  int rc = match_dev_locked(ctx, b, K_max, G_cap, o);
-  if (rc) return rc;
-  // frames that hit a cap are re-run on the device with the largest caps before the object search reads the points
-  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
-  if (rc) return rc;
-  if (O_max > 0) {
-    rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
-    if (rc) return rc;
-  }
-  return ctx->mark_enqueued();
+  const TrackOut o{{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr}, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj};
+  return track_dev_locked(ctx, "mocap_track_frame_dev", FrameBatch{n_frames, M_max, d_blobs, d_counts, gate_px}, K_max, G_cap, o, TrackStages{});
 }
 
 // mocap_track_frame / mocap_track_frame_dev with the rigid-body stage (csrc/rigid_body.hip) behind the object search
@@ -1088,9 +1061,9 @@ extern "C" int mocap_track_frame_bodies(mocap_ctx* ctx, int64_t n_frames, int M_
                                         int32_t* rb_status) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
-  const BodiesIO bo{B_max, rb_found, rb_n_used, rb_assign, rb_R, rb_t, rb_rms, rb_score, rb_status};
-  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, nullptr, nullptr, &bo);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj};
+  const BodiesIO io{B_max, rb_found, rb_n_used, rb_assign, rb_R, rb_t, rb_rms, rb_score, rb_status};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, io);
 }
 
 extern "C" int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
@@ -1102,23 +1075,9 @@ extern "C" int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, in
                                             int32_t* d_rb_status) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const BodiesIO bo{B_max, d_rb_found, d_rb_n_used, d_rb_assign, d_rb_R, d_rb_t, d_rb_rms, d_rb_score, d_rb_status};
-  int rc = bodies_check(ctx, "mocap_track_frame_bodies_dev", n_frames, K_max, bo);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
-  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
-  rc = match_dev_locked(ctx, b, K_max, G_cap, o);
-  if (rc) return rc;
-  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
-  if (rc) return rc;
-  if (O_max > 0) {
-    rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
-    if (rc) return rc;
-  }
-  rc = bodies_dev_locked(ctx, n_frames, K_max, d_xyz, d_n_pts, bo);
-  if (rc) return rc;
-  return ctx->mark_enqueued();
+  const TrackOut o{{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr}, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj};
+  const BodiesIO io{B_max, d_rb_found, d_rb_n_used, d_rb_assign, d_rb_R, d_rb_t, d_rb_rms, d_rb_score, d_rb_status};
+  return track_dev_locked(ctx, "mocap_track_frame_bodies_dev", FrameBatch{n_frames, M_max, d_blobs, d_counts, gate_px}, K_max, G_cap, o, io);
 }
 
 // mocap_track_frame / mocap_track_frame_dev with the marker tracker (csrc/marker_track.hip) behind the object search
@@ -1129,9 +1088,9 @@ extern "C" int mocap_track_frame_ids(mocap_ctx* ctx, int64_t n_frames, int M_max
                                      int32_t* mk_n_tracks, int32_t* mk_status) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
-  const MarkersIO mo{t, mk_id, mk_hits, mk_n_tracks, mk_status};
-  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, nullptr, nullptr, nullptr, &mo);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj};
+  const MarkersIO io{t, mk_id, mk_hits, mk_n_tracks, mk_status};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, io);
 }
 
 extern "C" int mocap_track_frame_ids_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
@@ -1142,23 +1101,9 @@ extern "C" int mocap_track_frame_ids_dev(mocap_ctx* ctx, int64_t n_frames, int M
                                          int32_t* d_mk_status) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const MarkersIO mo{d_t, d_mk_id, d_mk_hits, d_mk_n_tracks, d_mk_status};
-  int rc = markers_check(ctx, "mocap_track_frame_ids_dev", n_frames, K_max, mo);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
-  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
-  rc = match_dev_locked(ctx, b, K_max, G_cap, o);
-  if (rc) return rc;
-  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
-  if (rc) return rc;
-  if (O_max > 0) {
-    rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
-    if (rc) return rc;
-  }
-  rc = markers_dev_locked(ctx, n_frames, K_max, d_xyz, d_n_pts, mo);
-  if (rc) return rc;
-  return ctx->mark_enqueued();
+  const TrackOut o{{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr}, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj};
+  const MarkersIO io{d_t, d_mk_id, d_mk_hits, d_mk_n_tracks, d_mk_status};
+  return track_dev_locked(ctx, "mocap_track_frame_ids_dev", FrameBatch{n_frames, M_max, d_blobs, d_counts, gate_px}, K_max, G_cap, o, io);
 }
 
 extern "C" int mocap_track_frame_filtered(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
@@ -1168,9 +1113,9 @@ extern "C" int mocap_track_frame_filtered(mocap_ctx* ctx, int64_t n_frames, int 
                                           double* fheading, int32_t* chosen) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj, nullptr, nullptr, nullptr};
-  const FilterIO fo{t, fpos, fvel, fheading, chosen};
-  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, &fo);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj};
+  const FilterIO io{t, fpos, fvel, fheading, chosen};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, io);
 }
 
 extern "C" int mocap_track_frame_filtered_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
@@ -1181,18 +1126,7 @@ extern "C" int mocap_track_frame_filtered_dev(mocap_ctx* ctx, int64_t n_frames, 
                                               double* d_fheading, int32_t* d_chosen) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const FilterIO fo{d_t, d_fpos, d_fvel, d_fheading, d_chosen};
-  int rc = filter_check(ctx, "mocap_track_frame_filtered_dev", n_frames, O_max, fo);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const FrameBatch b{n_frames, M_max, d_blobs, d_counts, gate_px};
-  const FrameOut o{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr};
-  rc = match_dev_locked(ctx, b, K_max, G_cap, o);
-  if (rc) return rc;
-  rc = resubmit_dev_locked(ctx, b, K_max, o, nullptr);
-  if (rc) return rc;
-  rc = locate_dev_locked(ctx, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_oerr, d_drone, nullptr, d_n_obj);
-  if (rc) return rc;
-  rc = filter_dev_locked(ctx, n_frames, O_max, d_pos, d_heading, d_drone, d_n_obj, fo);
-  return rc ? rc : ctx->mark_enqueued();
+  const TrackOut o{{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr}, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj};
+  const FilterIO io{d_t, d_fpos, d_fvel, d_fheading, d_chosen};
+  return track_dev_locked(ctx, "mocap_track_frame_filtered_dev", FrameBatch{n_frames, M_max, d_blobs, d_counts, gate_px}, K_max, G_cap, o, io);
 }

@@ -105,41 +105,34 @@ extern "C" int mocap_track_markers(mocap_ctx* ctx, int64_t n_frames, const doubl
                                    const int32_t* n_pts, int32_t* id, int32_t* hits, int32_t* n_tracks, int32_t* status) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = markers_check(ctx, "mocap_track_markers", n_frames, K_max, MarkersIO{t, id, hits, n_tracks, status});
+  const MarkersIO io{t, id, hits, n_tracks, status};
+  int rc = markers_check(ctx, "mocap_track_markers", n_frames, K_max, io);
   if (rc) return rc;
   if (n_frames == 0) return MOCAP_OK;
   if (!xyz || !n_pts) return ctx->fail(MOCAP_E_ARG, "mocap_track_markers: null buffer");
   rc = markers_times_check(ctx, "mocap_track_markers", n_frames, t);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t F = (size_t)n_frames, FK = F * (size_t)K_max;
-  double *d_t, *d_xyz;
+  const IoDims n{(size_t)n_frames, (size_t)K_max};
+  double* d_xyz;
   int32_t* d_n;
   MarkersIO d{};
   auto lay = [&](void* base) {
     Carver c(base);
-    d_t = c.take<double>(F);
-    d_xyz = c.take<double>(FK * 3);
-    d_n = c.take<int32_t>(F);
-    d.id = c.take<int32_t>(FK);
-    d.hits = c.take<int32_t>(FK);
-    d.n_tracks = c.take<int32_t>(F);
-    d.status = c.take<int32_t>(F);
+    d_xyz = c.take<double>(n.F * n.K * 3);
+    d_n = c.take<int32_t>(n.F);
+    carve(c, d, n);
     return c.off;
   };
   DevBuf& s = ctx->scratch[0];
   if (s.reserve(lay(nullptr))) return ctx->fail(MOCAP_E_HIP, "hipMalloc failed");
   lay(s.ptr);
-  d.t = d_t;
-  HIP_TRY(ctx, hipMemcpyAsync(d_t, t, sizeof(double) * F, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * FK * 3, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_n, n_pts, sizeof(int32_t) * F, hipMemcpyHostToDevice, ctx->stream));
-  rc = markers_dev_locked(ctx, n_frames, K_max, d_xyz, d_n, d);
+  HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * n.F * n.K * 3, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_n, n_pts, sizeof(int32_t) * n.F, hipMemcpyHostToDevice, ctx->stream));
+  rc = copy_fields<true>(d, io, n, StreamCopy{ctx, hipMemcpyHostToDevice});
+  if (!rc) rc = markers_dev_locked(ctx, n_frames, K_max, d_xyz, d_n, d);
+  if (!rc) rc = copy_fields<false>(io, d, n, StreamCopy{ctx, hipMemcpyDeviceToHost});
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(id, d.id, sizeof(int32_t) * FK, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(hits, d.hits, sizeof(int32_t) * FK, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(n_tracks, d.n_tracks, sizeof(int32_t) * F, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(status, d.status, sizeof(int32_t) * F, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MOCAP_OK;
 }

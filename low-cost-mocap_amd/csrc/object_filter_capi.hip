@@ -153,42 +153,37 @@ extern "C" int mocap_filter_objects(mocap_ctx* ctx, int64_t n_frames, const doub
                                     double* fheading, int32_t* chosen) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = filter_check(ctx, "mocap_filter_objects", n_frames, O_max, FilterIO{t, fpos, fvel, fheading, chosen});
+  const FilterIO io{t, fpos, fvel, fheading, chosen};
+  int rc = filter_check(ctx, "mocap_filter_objects", n_frames, O_max, io);
   if (rc) return rc;
   if (n_frames == 0) return MOCAP_OK;
   if (!pos || !heading || !drone || !n_obj) return ctx->fail(MOCAP_E_ARG, "mocap_filter_objects: null buffer");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t F = (size_t)n_frames, O = (size_t)O_max, D = (size_t)ctx->objf_D;
-  double *d_t, *d_pos, *d_head, *d_fhead;
-  int32_t *d_drone, *d_nobj, *d_chosen;
-  float *d_fpos, *d_fvel;
+  const size_t F = (size_t)n_frames, O = (size_t)O_max;
+  const IoDims n{F, 0, 0, (size_t)ctx->objf_D};
+  double *d_pos, *d_head;
+  int32_t *d_drone, *d_nobj;
+  FilterIO d{};
   auto lay = [&](void* base) {
     Carver c(base);
-    d_t = c.take<double>(F);
     d_pos = c.take<double>(F * O * 3);
     d_head = c.take<double>(F * O);
     d_drone = c.take<int32_t>(F * O);
     d_nobj = c.take<int32_t>(F);
-    d_fpos = c.take<float>(F * D * 3);
-    d_fvel = c.take<float>(F * D * 3);
-    d_fhead = c.take<double>(F * D);
-    d_chosen = c.take<int32_t>(F * D);
+    carve(c, d, n);
     return c.off;
   };
   DevBuf& s = ctx->scratch[0];
   if (s.reserve(lay(nullptr))) return ctx->fail(MOCAP_E_HIP, "hipMalloc failed");
   lay(s.ptr);
-  HIP_TRY(ctx, hipMemcpyAsync(d_t, t, sizeof(double) * F, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos, sizeof(double) * F * O * 3, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_head, heading, sizeof(double) * F * O, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_drone, drone, sizeof(int32_t) * F * O, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_nobj, n_obj, sizeof(int32_t) * F, hipMemcpyHostToDevice, ctx->stream));
-  rc = filter_dev_locked(ctx, n_frames, O_max, d_pos, d_head, d_drone, d_nobj, FilterIO{d_t, d_fpos, d_fvel, d_fhead, d_chosen});
+  rc = copy_fields<true>(d, io, n, StreamCopy{ctx, hipMemcpyHostToDevice});
+  if (!rc) rc = filter_dev_locked(ctx, n_frames, O_max, d_pos, d_head, d_drone, d_nobj, d);
+  if (!rc) rc = copy_fields<false>(io, d, n, StreamCopy{ctx, hipMemcpyDeviceToHost});
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(fpos, d_fpos, sizeof(float) * F * D * 3, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(fvel, d_fvel, sizeof(float) * F * D * 3, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(fheading, d_fhead, sizeof(double) * F * D, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(chosen, d_chosen, sizeof(int32_t) * F * D, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MOCAP_OK;
 }

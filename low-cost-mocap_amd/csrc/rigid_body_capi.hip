@@ -17,6 +17,7 @@ static_assert(kRbMaxBodies == MOCAP_RB_MAX_BODIES && kRbMaxMarkers == MOCAP_RB_M
               "kernels.hpp mirrors include/mocap_core.h");
 static_assert(RB_ST_RMS_ == MOCAP_RB_ST_RMS && RB_ST_WORK_CAP_ == MOCAP_RB_ST_WORK_CAP && kRbDefaultWorkCap == MOCAP_RB_DEFAULT_WORK_CAP,
               "kernels.hpp mirrors include/mocap_core.h");
+static_assert(BodiesIO::kAssign == MOCAP_RB_MAX_MARKERS, "io_fields.hpp mirrors include/mocap_core.h");
 
 namespace {
 
@@ -161,44 +162,31 @@ extern "C" int mocap_locate_rigid_bodies(mocap_ctx* ctx, int64_t n_frames, int K
                                          double* score, int32_t* status) {
   if (!ctx) return MOCAP_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = bodies_check(ctx, "mocap_locate_rigid_bodies", n_frames, K_max, BodiesIO{B_max, found, n_used, assign, R, t, rms, score, status});
+  const BodiesIO io{B_max, found, n_used, assign, R, t, rms, score, status};
+  int rc = bodies_check(ctx, "mocap_locate_rigid_bodies", n_frames, K_max, io);
   if (rc) return rc;
   if (n_frames == 0 || B_max == 0) return MOCAP_OK;
   if (!xyz || !n_pts) return ctx->fail(MOCAP_E_ARG, "mocap_locate_rigid_bodies: null buffer");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t F = (size_t)n_frames, FB = F * (size_t)B_max;
+  const IoDims n{(size_t)n_frames, (size_t)K_max, (size_t)B_max};
   double* d_xyz;
   int32_t* d_n;
-  BodiesIO d{B_max, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  BodiesIO d{B_max};
   auto lay = [&](void* base) {
     Carver c(base);
-    d_xyz = c.take<double>(F * K_max * 3);
-    d_n = c.take<int32_t>(F);
-    d.found = c.take<int32_t>(FB);
-    d.n_used = c.take<int32_t>(FB);
-    d.assign = c.take<int8_t>(FB * kRbMaxMarkers);
-    d.R = c.take<double>(FB * 9);
-    d.t = c.take<double>(FB * 3);
-    d.rms = c.take<double>(FB);
-    d.score = c.take<double>(FB);
-    d.status = c.take<int32_t>(FB);
+    d_xyz = c.take<double>(n.F * n.K * 3);
+    d_n = c.take<int32_t>(n.F);
+    carve(c, d, n);
     return c.off;
   };
   DevBuf& s = ctx->scratch[0];
   if (s.reserve(lay(nullptr))) return ctx->fail(MOCAP_E_HIP, "hipMalloc failed");
   lay(s.ptr);
-  HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * F * K_max * 3, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_n, n_pts, sizeof(int32_t) * F, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * n.F * n.K * 3, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_n, n_pts, sizeof(int32_t) * n.F, hipMemcpyHostToDevice, ctx->stream));
   rc = bodies_dev_locked(ctx, n_frames, K_max, d_xyz, d_n, d);
+  if (!rc) rc = copy_fields<false>(io, d, n, StreamCopy{ctx, hipMemcpyDeviceToHost});
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(found, d.found, sizeof(int32_t) * FB, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(n_used, d.n_used, sizeof(int32_t) * FB, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(assign, d.assign, FB * kRbMaxMarkers, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(R, d.R, sizeof(double) * FB * 9, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(t, d.t, sizeof(double) * FB * 3, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(rms, d.rms, sizeof(double) * FB, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(score, d.score, sizeof(double) * FB, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(status, d.status, sizeof(int32_t) * FB, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MOCAP_OK;
 }

@@ -382,71 +382,76 @@ class MocapCore:
                 "error": np.full((F, O), np.nan), "droneIndex": np.full((F, O), -1, dtype=np.int32),
                 "n_obj": np.zeros(F, dtype=np.int32)}
 
-    def track_frame(self, blobs, counts, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8):
-        """mocap_track_frame: match -> world coordinates -> locate_objects for one or a few frames in one call
-        (helpers.py:94-133).  O_max = 0 switches the object search off (Cameras.is_locating_objects)."""
+    @staticmethod
+    def _track_ptrs(o, O_max):
+        """The argument run every host mocap_track_frame* shares behind G_cap: frame outputs, O_max, object outputs."""
+        return [_p(o[k]) for k in ("xyz", "err", "corr", "n_pts", "status")] + [int(O_max)] + \
+               [_p(o[k]) for k in ("pos", "heading", "error", "droneIndex", "n_obj")]
+
+    def _track_blobs(self, blobs, counts, K_max):
+        """The blob inputs of a host mocap_track_frame* -> (blobs, counts, F, M, K_max), K_max defaulted."""
         blobs = np.ascontiguousarray(blobs, dtype=np.float32)
         counts = np.ascontiguousarray(counts, dtype=np.int32)
         F, C, M, _ = blobs.shape
         assert C == self.C and counts.shape == (F, C)
-        K_max = min(C * M, 64) if K_max is None else int(K_max)
+        return blobs, counts, F, M, min(C * M, 64) if K_max is None else int(K_max)
+
+    @staticmethod
+    def _track_retry(call, K_max, K_all, O_max):
+        """call(K_max) -> the outputs of one mocap_track_frame*; again with more slots while a frame has more roots than K_max:
+        the core re-ran those frames itself and says how many slots they need (n_pts).  K_all: a frame's blobs over all cameras."""
+        limit = 256 if O_max else 1024
         while True:
+            o = call(K_max)
+            need = (o["status"] & ST_ROOT_OVERFLOW).astype(bool) & (o["n_pts"] > K_max)
+            if not (need.any() and K_max < min(K_all, limit)):
+                return o
+            K_max = min(int(o["n_pts"][need].max()), limit)
+
+    def track_frame(self, blobs, counts, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8):
+        """mocap_track_frame: match -> world coordinates -> locate_objects for one or a few frames in one call
+        (helpers.py:94-133).  O_max = 0 switches the object search off (Cameras.is_locating_objects)."""
+        blobs, counts, F, M, K_max = self._track_blobs(blobs, counts, K_max)
+
+        def call(K_max):
             o = self._track_outputs(F, K_max, O_max)
             self._check(self.lib.mocap_track_frame(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
-                                                   _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
-                                                   int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
-                                                   _p(o["droneIndex"]), _p(o["n_obj"])))
-            need = (o["status"] & ST_ROOT_OVERFLOW).astype(bool) & (o["n_pts"] > K_max)
-            if need.any() and K_max < min(C * M, 256 if O_max else 1024):
-                # the core re-ran those frames itself and says how many slots they need (n_pts)
-                K_max = min(int(o["n_pts"][need].max()), 256 if O_max else 1024)
-                continue
+                                                   *self._track_ptrs(o, O_max)))
             return o
+        return self._track_retry(call, K_max, self.C * M, O_max)
 
-    def track_frame_images(self, images, M_max=16, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8):
-        """mocap_track_frame_images: raw camera frames [F][C][rows][cols][3] -> image points, object points, objects."""
+    def _track_images(self, entry, images, M_max, gate_px, K_max, G_cap, O_max, *stream):
+        """mocap_track_frame_images / _images_jpeg (`stream`: the latter's trailing arguments), with the root-overflow retry."""
         images = np.ascontiguousarray(images, dtype=np.uint8)
         F, C = images.shape[:2]
         assert images.shape == (F, C, self.img_rows, self.img_cols, 3) and C == self.img_C == self.C
         K_max = min(C * M_max, 64) if K_max is None else int(K_max)
-        while True:
+
+        def call(K_max):
             o = self._track_outputs(F, K_max, O_max)
             o.update(blobs=np.zeros((F, C, M_max, 2), dtype=np.float32), counts=np.zeros((F, C), dtype=np.int32),
                      blob_status=np.zeros((F, C), dtype=np.int32))
-            self._check(self.lib.mocap_track_frame_images(self._h, F, _p(images), int(M_max), float(gate_px), K_max, int(G_cap),
-                                                          _p(o["blobs"]), _p(o["counts"]), _p(o["blob_status"]), _p(o["xyz"]),
-                                                          _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]), int(O_max),
-                                                          _p(o["pos"]), _p(o["heading"]), _p(o["error"]), _p(o["droneIndex"]),
-                                                          _p(o["n_obj"])))
-            need = (o["status"] & ST_ROOT_OVERFLOW).astype(bool) & (o["n_pts"] > K_max)
-            if need.any() and K_max < min(C * M_max, 256 if O_max else 1024):
-                K_max = min(int(o["n_pts"][need].max()), 256 if O_max else 1024)
-                continue
+            self._check(entry(self._h, F, _p(images), int(M_max), float(gate_px), K_max, int(G_cap), _p(o["blobs"]), _p(o["counts"]),
+                              _p(o["blob_status"]), *self._track_ptrs(o, O_max), *stream))
             return o
+        return self._track_retry(call, K_max, C * M_max, O_max)
+
+    def track_frame_images(self, images, M_max=16, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8):
+        """mocap_track_frame_images: raw camera frames [F][C][rows][cols][3] -> image points, object points, objects."""
+        return self._track_images(self.lib.mocap_track_frame_images, images, M_max, gate_px, K_max, G_cap, O_max)
 
     def track_frame_images_jpeg(self, images, M_max=16, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8, quality=95, capacity=None):
         """mocap_track_frame_images_jpeg: track_frame_images plus the preview stream: "jpeg" = one bytes object per frame set
         (its C processed frames side by side, the file cv.imencode('.jpg') writes), "jpeg_size" the bytes each needed."""
         images = np.ascontiguousarray(images, dtype=np.uint8)
         F, C = images.shape[:2]
-        assert images.shape == (F, C, self.img_rows, self.img_cols, 3) and C == self.img_C == self.C
-        K_max = min(C * M_max, 64) if K_max is None else int(K_max)
         S = self.img_cols
         cap = self.jpeg_default_capacity(S, S * C) if capacity is None else int(capacity)
         while True:
-            o = self._track_outputs(F, K_max, O_max)
-            o.update(blobs=np.zeros((F, C, M_max, 2), dtype=np.float32), counts=np.zeros((F, C), dtype=np.int32),
-                     blob_status=np.zeros((F, C), dtype=np.int32))
             buf, size = np.zeros((F, cap), dtype=np.uint8), np.zeros(F, dtype=np.int64)
-            self._check(self.lib.mocap_track_frame_images_jpeg(
-                self._h, F, _p(images), int(M_max), float(gate_px), K_max, int(G_cap), _p(o["blobs"]), _p(o["counts"]),
-                _p(o["blob_status"]), _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]), int(O_max),
-                _p(o["pos"]), _p(o["heading"]), _p(o["error"]), _p(o["droneIndex"]), _p(o["n_obj"]), int(quality), _p(buf), cap,
-                _p(size)))
-            need = (o["status"] & ST_ROOT_OVERFLOW).astype(bool) & (o["n_pts"] > K_max)
-            if need.any() and K_max < min(C * M_max, 256 if O_max else 1024):
-                K_max = min(int(o["n_pts"][need].max()), 256 if O_max else 1024)
-                continue
+            o = self._track_images(self.lib.mocap_track_frame_images_jpeg, images, M_max, gate_px, K_max, G_cap, O_max,
+                                   int(quality), _p(buf), cap, _p(size))
+            K_max = o["xyz"].shape[1]                     # (the slots a root-overflow retry settled on)
             if capacity is None and (size > cap).any():   # a frame set that does not compress: once more with room for it
                 cap = int(size.max())
                 continue
@@ -708,18 +713,12 @@ class MocapCore:
     def track_frame_bodies(self, blobs, counts, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8, B_max=None):
         """mocap_track_frame_bodies: track_frame with the rigid-body stage behind the object search; the same dict plus the
         keys of locate_rigid_bodies.  With bodies registered a frame holds at most 64 points (K_max <= 64)."""
-        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        F, C, M, _ = blobs.shape
-        assert C == self.C and counts.shape == (F, C)
-        K_max = min(C * M, 64) if K_max is None else int(K_max)
+        blobs, counts, F, M, K_max = self._track_blobs(blobs, counts, K_max)
         B_max = self.rigid_bodies_n if B_max is None else int(B_max)
         o = self._track_outputs(F, K_max, O_max)
         o.update(self._body_outputs(F, B_max))
         self._check(self.lib.mocap_track_frame_bodies(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
-                                                      _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
-                                                      int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
-                                                      _p(o["droneIndex"]), _p(o["n_obj"]), B_max, *self._body_ptrs(o)))
+                                                      *self._track_ptrs(o, O_max), B_max, *self._body_ptrs(o)))
         return o
 
     def track_frame_bodies_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
@@ -780,18 +779,12 @@ class MocapCore:
         """mocap_track_frame_ids: track_frame with the marker tracker behind the object search, t [F] = the frames' time stamps;
         the same dict plus the keys of track_markers.  A frame holds at most 64 points (K_max <= 64); one that needs more is
         reported like track_frame reports it (status, n_pts) and NOT re-run here: the tracker has consumed the call's frames."""
-        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        F, C, M, _ = blobs.shape
-        assert C == self.C and counts.shape == (F, C)
+        blobs, counts, F, M, K_max = self._track_blobs(blobs, counts, K_max)
         t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
-        K_max = min(C * M, 64) if K_max is None else int(K_max)
         o = self._track_outputs(F, K_max, O_max)
         o.update(self._marker_outputs(F, K_max))
         self._check(self.lib.mocap_track_frame_ids(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
-                                                   _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
-                                                   int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
-                                                   _p(o["droneIndex"]), _p(o["n_obj"]), _p(t), *self._marker_ptrs(o)))
+                                                   *self._track_ptrs(o, O_max), _p(t), *self._marker_ptrs(o)))
         return o
 
     def track_frame_ids_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
@@ -849,19 +842,13 @@ class MocapCore:
         """mocap_track_frame_filtered: track_frame with the object filter behind the object search, t [F] = the frames' time
         stamps.  A frame that needs more than K_max slots is reported like track_frame reports it (status, n_pts) and NOT
         re-run here: the filter has consumed the call's time stamps."""
-        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        F, C, M, _ = blobs.shape
-        assert C == self.C and counts.shape == (F, C)
+        blobs, counts, F, M, K_max = self._track_blobs(blobs, counts, K_max)
         t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
-        K_max = min(C * M, 64) if K_max is None else int(K_max)
         o = self._track_outputs(F, K_max, O_max)
         o.update(self._filter_outputs(F))
         self._check(self.lib.mocap_track_frame_filtered(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
-                                                        _p(o["xyz"]), _p(o["err"]), _p(o["corr"]), _p(o["n_pts"]), _p(o["status"]),
-                                                        int(O_max), _p(o["pos"]), _p(o["heading"]), _p(o["error"]),
-                                                        _p(o["droneIndex"]), _p(o["n_obj"]), _p(t), _p(o["fpos"]), _p(o["fvel"]),
-                                                        _p(o["fheading"]), _p(o["chosen"])))
+                                                        *self._track_ptrs(o, O_max), _p(t),
+                                                        *[_p(o[k]) for k in ("fpos", "fvel", "fheading", "chosen")]))
         return o
 
     def track_frame_filtered_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
