@@ -58,6 +58,9 @@ constexpr int kBBRecs = kBBThreads + 64;  // surviving blocks queued between two
 // LDS layout's and the records' all come from here
 constexpr int bb_cw(int C) { return C <= 8 ? 1 : 2; }
 constexpr uint32_t bb_rec_bytes(int CW) { return 24u + 8u * (uint32_t)CW; }
+// a group's bytes are table rows (BBState::ROWS) where the whole layout is a compile-time constant and C ML + 1 rows fit a byte;
+// ML a power of two: phase E takes the blob index back as byte & (ML - 1)
+constexpr bool bb_group_rows(int CT, int ML, int RL) { return CT > 0 && ML > 0 && RL > 0 && CT * ML < 0xFF && (ML & (ML - 1)) == 0; }
 
 // LDS carving, identical on host (size) and device (pointers): the frame's persistent state (blobs, per-blob DLT table,
 // roots, hit lists), the search's arrays (block records, result slots -- dead while matching, which keeps its speculative
@@ -160,19 +163,22 @@ bool frame_bb_fits(int C, int M, int R) {
   return C >= 2 && C <= 16 && M >= 1 && M <= 64 && R >= 1 && R <= 255 && frame_bb_lds_bytes_min(C, M, R) <= (size_t)128 * 1024;
 }
 
-// blob indices of one (partial) group: one byte per camera, 0xFF = the camera is open or not in the group
-template <int CW>
+// blob indices of one (partial) group: one byte per camera, NONE = the camera is open or not in the group.  Runtime layouts:
+// the byte is the blob index, NONE = 0xFF.  Fixed layouts (bb_group_rows): the byte is the blob's ROW c ML + k of the per-blob
+// table -- what every consumer of a group needs (the DLT record at bt + 80 row, the observation at bxy[row]) --, NONE = C ML, the
+// table's record of zeros.
+template <int CW, uint32_t NONE = 0xFFu>
 struct Packed {
   unsigned long long w[CW];
   __device__ __forceinline__ void clear() {
 #pragma unroll
-    for (int k = 0; k < CW; k++) w[k] = ~0ull;
+    for (int k = 0; k < CW; k++) w[k] = NONE * 0x0101010101010101ull;
   }
-  __device__ __forceinline__ void set(int c, uint32_t idx) {  // the camera's byte must still be 0xFF
+  __device__ __forceinline__ void set(int c, uint32_t idx) {  // the camera's byte must still be NONE
     if (CW == 1)
-      w[0] ^= (unsigned long long)(idx ^ 0xFFu) << (8 * c);
+      w[0] ^= (unsigned long long)(idx ^ NONE) << (8 * c);
     else
-      w[c >> 3] ^= (unsigned long long)(idx ^ 0xFFu) << (8 * (c & 7));
+      w[c >> 3] ^= (unsigned long long)(idx ^ NONE) << (8 * (c & 7));
   }
   __device__ __forceinline__ uint32_t get(int c) const {
     return CW == 1 ? (uint32_t)(w[0] >> (8 * c)) & 0xFFu : (uint32_t)(w[c >> 3] >> (8 * (c & 7))) & 0xFFu;
@@ -236,6 +242,16 @@ __device__ __forceinline__ void bb_prio() {
 template <bool F32R, int CW, int CT, int ML, int RL, bool PERK = false>
 struct BBState {
   static constexpr int T = kBBThreads, W = kBBWaves;
+  // Group bytes as table rows (Packed): the layouts fixed at compile time whose rows and the record of zeros fit a byte -- 8 x 16:
+  // rows 0 .. 127, zeros at 128.  gbyte(c, k): blob k of camera c as a group's byte; grow(c, byte): its table row.
+  static constexpr bool ROWS = bb_group_rows(CT, ML, RL);
+  static constexpr uint32_t kNone = ROWS ? (uint32_t)(CT * ML) : 0xFFu;
+  typedef Packed<CW, kNone> Pk;
+  // The provisional roots listed once per frame (match(), behind stage 0's barrier): the fixed layouts whose blobs of a camera
+  // fit the low half of a wave's lane mask (mbcnt_lo) and whose (camera, blob) numbers c ML + k fit a byte
+  static constexpr bool PLIST = CT > 0 && ML > 0 && RL > 0 && ML < 32 && CT * ML <= 256 && (ML & (ML - 1)) == 0;
+  __device__ __forceinline__ uint32_t gbyte(int c, uint32_t k) const { return ROWS ? (uint32_t)c * (uint32_t)ML + k : k; }
+  __device__ __forceinline__ size_t grow(int c, uint32_t b) const { return ROWS ? (size_t)b : (size_t)c * M + b; }
   const FrameArgs& p;
   BBCamTables<CT, PERK> cv;
   const int C_, M, R, RS;  // R = K_max (root limit, output stride), RS = root slots of the layout
@@ -251,6 +267,36 @@ struct BBState {
     wave = t >> 6;
   }
   __device__ __forceinline__ int cn() const { return CT > 0 ? CT : C_; }
+  // Measuring build (-DMOCAP_BB_PHASE_CLOCKS, lib/libmocap_core_phaseclocks.so, scripts/time_frame_phases.py): wave 0 reads the
+  // cycle counter behind the barriers that separate a frame's phases and keeps one 32-bit sum per phase (a workgroup's cycles of
+  // one launch fit); the sums go to the counters behind the caller's status array when the workgroup leaves the frame loop
+  // (frame_bb_body.inc), the way the self-check build hands over its counts.  The clocks cost registers and wave 0 its issue
+  // slots: the figures are SHARES of a frame, not times.  Without the define pc_mark() is empty and every code object is,
+  // instruction for instruction, what it is without this text.
+  enum { PC_OTHER = 0, PC_PAIRS0, PC_PAIRS1, PC_B1_TABLE, PC_ROW_COPY, PC_PHASE_C, PC_SEED_PASS, PC_SEED_PUSH, PC_EVAL, PC_TEST, PC_PHASE_E, PC_COUNT };
+#ifdef MOCAP_BB_PHASE_CLOCKS
+  uint32_t pc_last = 0, pc_sum[PC_COUNT] = {};
+  template <int PH>
+  __device__ __forceinline__ void pc_mark() {
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == 0) {  // (wave-uniform: the counter and the sums stay scalar)
+      const uint32_t now = (uint32_t)__builtin_readcyclecounter();
+      pc_sum[PH] += now - pc_last;
+      pc_last = now;
+    }
+  }
+  __device__ __forceinline__ void pc_start() { pc_last = (uint32_t)__builtin_readcyclecounter(); }
+  __device__ __forceinline__ void pc_flush() const {
+    // (the caller's launch only: the status array of the re-submit's second pass, FrameArgs::n_frames_dev, is the library's own
+    // and has the self-check builds' two spare slots)
+    if (threadIdx.x == 0 && !p.n_frames_dev)
+      for (int k = 0; k < PC_COUNT; k++) atomicAdd(&p.status[p.n_frames + k], (int)(pc_sum[k] >> 8));  // (units of 256 cycles: the grid's sum fits 31 bits)
+  }
+#else
+  template <int PH>
+  __device__ __forceinline__ void pc_mark() {}
+  __device__ __forceinline__ void pc_start() {}
+  __device__ __forceinline__ void pc_flush() const {}
+#endif
   double* bt;
   float2 *bxy, *bxy_nx;
   int32_t* cnt_nx;
@@ -399,7 +445,7 @@ struct BBState {
         const bool mine_grp = (j & ~(GS - 1)) == gl0 && j != lane;
         rank += (hit && mine_grp && (dj < d || (dj == d && j < lane))) ? 1 : 0;
       }
-      if (hit) hits[((size_t)r * C + i) * M + rank] = (uint8_t)k;
+      if (hit) hits[((size_t)r * C + i) * M + rank] = (uint8_t)gbyte(i, (uint32_t)k);
       const unsigned long long g0 = (__ballot(hit && rank == 0) >> gl0) & gall;
       // removal by value (helpers.py:391): every blob with the closest hit's coordinates is claimed
       bool same = false;
@@ -494,6 +540,12 @@ struct BBState {
     uint8_t* nh_s = nullptr;
     uint8_t* hits_s = nullptr;
     unsigned long long* pclaim = (unsigned long long*)scr;
+    // PLIST: the provisional roots in (camera, blob) order, one byte j ML + k each, in act[] (written in phase C, read by the
+    // search: dead while matching; C ML bytes at most, R C are there); p_end[j]: the pairs and the provisional roots of cameras
+    // 1 .. j as one word, pairs << 16 | roots (both < 2^16: C ML blobs), in goff[] (phase C's scan writes it: dead as well).
+    // In LDS rather than in registers: as wave-uniform values they cost the headline kernel 14 more scalar spills to vector lanes
+    uint8_t* plist = act;
+    uint32_t* p_end = goff;
     {
       int Mmax = 0;
       for (int c = 1; c < C; c++) Mmax = cnt[c] > Mmax ? cnt[c] : Mmax;  // wave-uniform
@@ -506,6 +558,21 @@ struct BBState {
           // read the claim words while another wave's ds_or of stage 0 was still queued: provisional sets that differed between
           // waves, one wrong frame in ~10^5)
           block_sync_lds();  // the camera-0 roots' claims are complete
+          pc_mark<PC_PAIRS0>();
+          if constexpr (PLIST) {
+            // behind this barrier the provisional roots are fixed: every wave lists them once -- a lane per blob of one camera
+            // takes its rank from the camera's unclaimed mask and the running base, and leaves (camera, blob) in the list's slot
+            // of that rank; all waves write the same bytes.  No lane walks the cameras or a mask's set bits afterwards.
+#pragma unroll
+            for (int j = 1; j < CT; j++) {
+              const uint32_t U = ~((const uint32_t*)claimw)[2 * j] & ((1u << cnt[j]) - 1u);   // (cnt <= ML < 32; the same in every lane)
+              if (lane < ML && ((U >> lane) & 1u)) plist[__builtin_amdgcn_mbcnt_lo(U, (uint32_t)n_prov)] = (uint8_t)(j * ML + lane);
+              n_prov += __popc(U);
+              n_ppairs += __popc(U) * (CT - 1 - j);
+              if (lane == 0) p_end[j] = ((uint32_t)n_ppairs << 16) | (uint32_t)n_prov;
+            }
+            wave_lds_sync();
+          } else
           for (int j = 1; j < C; j++) {
             const int np = __popcll(U_of(j));
             n_prov += np;
@@ -527,6 +594,28 @@ struct BBState {
               r = pi / (C - 1);
               i = 1 + (pi - r * (C - 1));
               L = epiline(r, i);
+            } else if constexpr (PLIST) {
+              // the pair's camera: the first whose prefix of pair counts exceeds the pair's number (pi < n_ppairs = the pairs of p_end[C - 2]);
+              // its provisional root by one division, the root's blob from the list
+              int j = 1;
+              uint32_t before = 0;  // pairs << 16 | roots of the cameras before the pair's
+              const uint32_t key = ((uint32_t)pi << 16) | 0xFFFFu;  // key >= p_end[jj]  <=>  pi >= its pairs
+              uint32_t pe[CT > 2 ? CT - 2 : 1];
+#pragma unroll
+              for (int jj = 1; jj <= CT - 2; jj++) pe[jj - 1] = p_end[jj];  // (independent reads at constant addresses)
+#pragma unroll
+              for (int jj = 1; jj <= CT - 2; jj++) {
+                const bool ge = key >= pe[jj - 1];
+                j += ge ? 1 : 0;
+                before = ge ? pe[jj - 1] : before;
+              }
+              const uint32_t acc = before >> 16, pb = before & 0xFFFFu;
+              uint32_t ord, off;
+              divmod_tiny((uint32_t)pi - acc, (uint32_t)(CT - 1 - j), ord, off);  // (< 64 x 15, span <= 14)
+              r = (int)(pb + ord);
+              const int k = plist[r] & (ML - 1);
+              i = j + 1 + (int)off;
+              L = epiline_of(j, k, i);
             } else {
               int j = 1, acc = 0, pb = 0, span = C - 2;
               unsigned long long U = 0ull;
@@ -577,7 +666,7 @@ struct BBState {
                   bk = k;
                 }
               }
-              hl[pos] = (uint8_t)bk;
+              hl[pos] = (uint8_t)gbyte(i, (uint32_t)bk);
               if (pos == 0) {
                 p0 = pts[bk];
                 for (unsigned long long t = hm; t; t &= t - 1) {
@@ -639,12 +728,20 @@ struct BBState {
       }
     }
     __syncthreads();
+    pc_mark<PC_PAIRS1>();
     fresh_tid();
     if (wave == 0) bb_prio<kPrioSerial>();
     if (wave == 0 && pre) {
       // B1, pre-matched: lane p <-> provisional root p = the p-th unclaimed blob of cameras 1 .. C-1 in (camera, blob) order.
       // A provisional root is real when no root created at an earlier camera claims its blob (helpers.py:391,402-406).
       int jp = 0, kp = 0;
+      if constexpr (PLIST) {
+        if (lane < n_prov) {  // (the list: every wave wrote it before stage 1, two barriers ago)
+          const int row = plist[lane];
+          jp = row / ML;
+          kp = row & (ML - 1);
+        }
+      } else
       if (lane < n_prov) {
         int acc = 0;
         unsigned long long U = 0ull;
@@ -777,6 +874,7 @@ struct BBState {
     }
     bb_prio<kPrioPhase>();
     __syncthreads();
+    pc_mark<PC_B1_TABLE>();
     if (pre) {
       // the real provisional roots' rows leave the staging area for their final place: one lane per (new root, camera)
       const int n_new = misc[MI_NROOTS] - n0;
@@ -792,6 +890,7 @@ struct BBState {
         }
       }
       __syncthreads();  // (the staging rows are the search's arrays: phase C initialises them next)
+      pc_mark<PC_ROW_COPY>();
     }
 
     // C: candidate counts per root
@@ -803,9 +902,9 @@ struct BBState {
       int views = 1, na = 0;
       bool over = false;
       // what every block of the root has in common (block_pk): the root's own blob and the single-hit cameras' blobs
-      Packed<CW> pkb;
+      Pk pkb;
       pkb.clear();
-      pkb.set(rc, root_blob[r]);
+      pkb.set(rc, gbyte(rc, root_blob[r]));
       uint32_t sm = 1u << rc;
       for (int c = rc + 1; c < C; c++) {
         const unsigned n = nh[(size_t)r * C + c];
@@ -889,28 +988,29 @@ struct BBState {
     }
     bb_prio<kPrioPhase>();
     __syncthreads();
+    pc_mark<PC_PHASE_C>();
   }
 
   // ---------------------------------------------------------------- phase D
   // DLT matrix of candidate `rem` of root r with the first `skip` multi-hit cameras left open (skip = 0: the whole
   // group, rem = candidate index; skip = bnl[r]: the block's partial group, rem = block index).  Returns the views.
   // B += the DLT contribution of blob k of camera c, the camera at position j among the group's seen cameras
-  __device__ __forceinline__ void add_view(double (&B)[10], int c, uint32_t k, int j) const {
+  __device__ __forceinline__ void add_view(double (&B)[10], int c, uint32_t k, int j) const {  // k: the group's byte
     if (PERK && j != c) {
-      const float2 w = bxy[(size_t)c * M + k];
+      const float2 w = bxy[grow(c, k)];
       double Bc[10];
       dlt_contribution(Bc, cv.base + 12 * ((size_t)j * cn() + c), (double)w.x, (double)w.y);  // (per-lane position: vector loads, L1/L2-resident table)
 #pragma unroll
       for (int e = 0; e < 10; e++) B[e] = B[e] + Bc[e];
     } else {
-      const double* t = bt + ((size_t)c * M + k) * 10;
+      const double* t = bt + grow(c, k) * 10;
 #pragma unroll
       for (int e = 0; e < 10; e++) B[e] = B[e] + t[e];
     }
   }
 
   template <bool WITH_B>
-  __device__ __forceinline__ int group_matrix(int r, uint32_t rem, int skip, double (&B)[10], Packed<CW>& pk) const {
+  __device__ __forceinline__ int group_matrix(int r, uint32_t rem, int skip, double (&B)[10], Pk& pk) const {
     const int C = cn();
     const int rc = root_cam[r];
     const uint8_t* nhr = nh + (size_t)r * C;
@@ -923,10 +1023,10 @@ struct BBState {
       for (int e = 0; e < 10; e++) B[e] = 0.0;
     }
     for (int c = 0; c < C; c++) {
-      uint32_t k = 0xFFu;
+      uint32_t k = kNone;
       bool seen = false;
       if (c == rc) {
-        k = root_blob[r];
+        k = gbyte(c, root_blob[r]);
         seen = true;
       } else if (c > rc) {
         const uint32_t n = nhr[c];
@@ -944,7 +1044,7 @@ struct BBState {
           ka++;
         }
       }
-      if (k != 0xFFu) {
+      if (k != kNone) {
         if (WITH_B) add_view(B, c, k, j);
         v++;
         pk.set(c, k);
@@ -956,8 +1056,8 @@ struct BBState {
 
   // Blob indices of block gh of root r: what the root's blocks share (pkbase: the root's blob, the single-hit cameras) plus the
   // block's own fixed digits -- the multi-hit cameras act[bnl[r] .. nact[r]-1], typically one to three; the open digits' and the
-  // absent cameras' bytes stay 0xFF.  (group_matrix walks all cameras for the same bytes; it remains the self-check build's decoder.)
-  __device__ __forceinline__ void block_pk(int r, uint32_t gh, Packed<CW>& pk) const {
+  // absent cameras' bytes stay kNone.  (group_matrix walks all cameras for the same bytes; it remains the self-check build's decoder.)
+  __device__ __forceinline__ void block_pk(int r, uint32_t gh, Pk& pk) const {
     const int C = cn();
 #pragma unroll
     for (int k = 0; k < CW; k++) pk.w[k] = pkbase[(size_t)r * CW + k];
@@ -978,7 +1078,7 @@ struct BBState {
   // that is open or absent adds the record of zeros, as in fetch_candidate (same bits as skipping it).  Per-camera K: a view's
   // position is the number of SEEN cameras before it, the open ones included (the root's `seen` mask), add_view's rule.
   // Returns the views of the partial group.
-  __device__ __forceinline__ int block_matrix(int r, uint32_t gh, Packed<CW>& pk, double (&B)[10]) const {
+  __device__ __forceinline__ int block_matrix(int r, uint32_t gh, Pk& pk, double (&B)[10]) const {
     const int C = cn();
     block_pk(r, gh, pk);
 #pragma unroll
@@ -988,13 +1088,13 @@ struct BBState {
 #pragma unroll CT > 0 ? CT : 1
       for (int c = 0; c < C; c++) {
         const uint32_t k = pk.get(c);
-        if (k != 0xFFu) add_view(B, c, k, __popc(sm & ((1u << c) - 1u)));
+        if (k != kNone) add_view(B, c, k, __popc(sm & ((1u << c) - 1u)));
       }
     } else {
 #pragma unroll CT > 0 ? CT : 1
       for (int c = 0; c < C; c++) {
         const uint32_t k = pk.get(c);
-        const double* t = bt + (size_t)(k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
+        const double* t = bt + (size_t)(ROWS ? k : k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
 #pragma unroll
         for (int ee = 0; ee < 10; ee++) B[ee] = B[ee] + t[ee];
       }
@@ -1007,7 +1107,7 @@ struct BBState {
   // of zeros: x + (+0.0) = x for every x the sum can hold -- it starts at +0.0, so it is never -0.0 -- the same bits
   // without a save-exec / branch / restore around every camera).  Returns the views (the root's: every candidate of a root
   // has the same cameras).
-  __device__ __forceinline__ int fetch_candidate(uint32_t lo, uint32_t i, int& r, uint32_t& gl, Packed<CW>& pk, double (&B)[10]) const {
+  __device__ __forceinline__ int fetch_candidate(uint32_t lo, uint32_t i, int& r, uint32_t& gl, Pk& pk, double (&B)[10]) const {
     const int C = cn();
     const BRec rec = recs[lo];
     r = (int)(rec.rs & 0xFFu);
@@ -1035,13 +1135,13 @@ struct BBState {
 #pragma unroll CT > 0 ? CT : 1
       for (int c = 0; c < C; c++) {
         const uint32_t k = pk.get(c);
-        if (k != 0xFFu) add_view(B, c, k, j++);
+        if (k != kNone) add_view(B, c, k, j++);
       }
     } else {
 #pragma unroll CT > 0 ? CT : 1
       for (int c = 0; c < C; c++) {
         const uint32_t k = pk.get(c);
-        const double* t = bt + (size_t)(k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
+        const double* t = bt + (size_t)(ROWS ? k : k != 0xFFu ? (uint32_t)c * (uint32_t)M + k : (uint32_t)C * (uint32_t)M) * 10;
 #pragma unroll
         for (int ee = 0; ee < 10; ee++) B[ee] = B[ee] + t[ee];
       }
@@ -1081,7 +1181,7 @@ struct BBState {
     auto root_of_block = [&](uint32_t b_first_of_wave, uint32_t b) {
       return coop_last_le([&](int r) { return boff[r]; }, nroots, b_first_of_wave, b, lane);
     };
-    auto push_block = [&](int r, uint32_t gh, const Packed<CW>& pk) {
+    auto push_block = [&](int r, uint32_t gh, const Pk& pk) {
       const uint32_t old = (uint32_t)atomicAdd(ctr, (int32_t)(((uint32_t)bpl[r] << 10) | 1u));
       const uint32_t slot = old & 0x3FFu;
       BRec rec;
@@ -1111,7 +1211,7 @@ struct BBState {
       int my_r = -1;
       uint32_t my_gh = 0;
       unsigned long long my_key = 0ull;
-      Packed<CW> my_pk;
+      Pk my_pk;
       my_pk.clear();
       for (uint32_t s0 = 0; s0 < nblocks; s0 += T) {
         const uint32_t b = s0 + (uint32_t)tid;
@@ -1120,7 +1220,7 @@ struct BBState {
         if (b < nblocks) {
           const uint32_t gh = b - boff[r];
           double B[10], tr = 0.0;
-          Packed<CW> pk;
+          Pk pk;
           const int v = block_matrix(r, gh, pk, B);
           double s1d = __builtin_huge_val();  // a one-view partial group carries no information: never dropped, any seed
           float s1 = 0.0f;
@@ -1137,6 +1237,7 @@ struct BBState {
         }
       }
       block_sync_lds_only();
+      pc_mark<PC_SEED_PASS>();
       if (nblocks <= (uint32_t)T) {
         if (my_r >= 0 && seedkey[my_r] == my_key) {  // (keys are unique inside a root: exactly one lane per root with blocks)
           seedgh[my_r] = my_gh;
@@ -1148,13 +1249,14 @@ struct BBState {
           const uint32_t gh = 0xFFFFFFFFu - (uint32_t)seedkey[r];
           seedgh[r] = gh;
           seedkey[r] = 0ull;
-          Packed<CW> pk;
+          Pk pk;
           block_pk(r, gh, pk);
           push_block(r, gh, pk);
         }
       }
       bb_prio<kPrioEval>();
       block_sync_lds_only();
+      pc_mark<PC_SEED_PUSH>();
     }
     // ---- 2. the queued records' candidates (spread over all lanes, whatever root they belong to), then the next
     // blocks' tests, until nothing is left
@@ -1176,15 +1278,21 @@ struct BBState {
           uint32_t lo = 0;
           if (i0 + (uint32_t)(wave * 64) < ne)  // wave-uniform
             lo = (uint32_t)coop_last_le(rec_start, (int)ns, i0 + (uint32_t)(wave * 64), have ? i : ne - 1, lane);
-          Packed<CW> pk;  // the candidate's blob bytes: they go into the winner's record with the point
+          Pk pk;  // the candidate's blob bytes: they go into the winner's record with the point
           pk.clear();
           if (have) {
             double B[10];
             const int v = fetch_candidate(lo, i, r, gl, pk, B);
+            if constexpr (ROWS) {
+              // (the table sum and the views below take the same eight bytes: extracted once, they would stay in eight registers
+              // across the whole solve -- the views extract theirs again from the two words)
+#pragma unroll
+              for (int k = 0; k < CW; k++) asm volatile("" : "+v"(pk.w[k]));
+            }
             auto obs_p = [&](int c, double& x, double& y) -> bool {
               const uint32_t k = pk.get(c);
-              if (k == 0xFFu) return false;
-              const float2 w = bxy[(size_t)c * M + k];
+              if (k == kNone) return false;
+              const float2 w = bxy[grow(c, k)];
               x = (double)w.x;
               y = (double)w.y;
               return true;
@@ -1199,7 +1307,7 @@ struct BBState {
               int j2 = 0;
               for (int c = 0; c < C; c++) {
                 const uint32_t k = pk.get(c);
-                if (k != 0xFFu) add_view(B2, c, k, j2++);
+                if (k != kNone) add_view(B2, c, k, j2++);
               }
               solve_and_score<!PERK, true, F32R>(cv, B2, v, obs_p, X2, e2);
               atomicAdd(&p.status[p.n_frames], 1);
@@ -1237,6 +1345,7 @@ struct BBState {
           }
         }
         block_sync_lds_only();  // every lane is done with the records: new ones may be queued (through the other counter)
+        pc_mark<PC_EVAL>();
         if (tid == 0) *ctr = 0;
         {
           int32_t* t = ctr;
@@ -1257,7 +1366,7 @@ struct BBState {
       // when the cached blocks need no decode: found in round 5 as 1 wrong frame in ~10^4 with 2-candidate blocks).
       bool do_push = false;
       uint32_t gh = 0;
-      Packed<CW> pk;
+      Pk pk;
       pk.clear();
       if (b < nblocks) {
         gh = b - boff[r];
@@ -1285,12 +1394,12 @@ struct BBState {
             const uint32_t pl = bpl[r];
             for (uint32_t l = 0; l < pl; l++) {
               double B2[10], X2[3], e2 = inf;
-              Packed<CW> pk2;
+              Pk pk2;
               const int v2 = group_matrix<true>(r, gh * pl + l, 0, B2, pk2);
               auto obs2 = [&](int c, double& x, double& y) -> bool {
                 const uint32_t k = pk2.get(c);
-                if (k == 0xFFu) return false;
-                const float2 w = bxy[(size_t)c * M + k];
+                if (k == kNone) return false;
+                const float2 w = bxy[grow(c, k)];
                 x = (double)w.x;
                 y = (double)w.y;
                 return true;
@@ -1306,6 +1415,7 @@ struct BBState {
       block_sync_lds_only();
       if (do_push) push_block(r, gh, pk);
       block_sync_lds_only();
+      pc_mark<PC_TEST>();
     }
     wait_own_stores();  // the winners' records have reached L2 (stores are acknowledged from there) before any lane reads one
     __syncthreads();
@@ -1334,14 +1444,14 @@ struct BBState {
   // The winners do not live in LDS (12 doubles per root and wave: 4.5 of the frame's 33.8 KB, the difference between four
   // and five frames per CU) and are not solved for a second time either: the lane that ends an evaluation round as the holder of
   // a (wave, root) slot leaves its candidate's point -- solve_and_score's own bits -- and the group's packed blob bytes (the
-  // Packed<CW> it evaluated: one byte per camera, 0xFF = not in the group) in the slot's record of the workgroup's workspace
+  // Packed it evaluated: one byte per camera, kNone = not in the group) in the slot's record of the workgroup's workspace
   // (search(), the delivery): 24 + 8 CW bytes per slot in memory the workgroup rewrites frame after frame, i.e. in L2.
   // Slots are per wave, so no two waves ever write the same record and the merge of the four slots picks the record with them.
   static constexpr uint32_t kRecBytes = bb_rec_bytes(CW);
   __device__ __forceinline__ unsigned char* winner_rec(int s) const {  // (a uniform base + a 32-bit lane offset: the address stays out of the vector registers)
     return p.ws + (size_t)blockIdx.x * p.ws_stride + (size_t)(kRecBytes * (uint32_t)s);
   }
-  __device__ __forceinline__ void store_winner(int s, const double (&X)[3], const Packed<CW>& pk) const {
+  __device__ __forceinline__ void store_winner(int s, const double (&X)[3], const Pk& pk) const {
     unsigned long long* rec = (unsigned long long*)winner_rec(s);
     if constexpr (CW == 1) {
       // 32 bytes at a multiple of 32 (the workspace is 256-byte aligned, so is the stride): two 16-byte stores
@@ -1359,9 +1469,13 @@ struct BBState {
     }
   }
   // two bytes of a group (low 16 bits of `two`) as two entries of a correspondence row: 0xFF -> -1, any other byte (a blob
-  // index, <= 63) -> itself
+  // index, <= 63) -> itself; bytes that are table rows: C ML (the only byte with bit 7 set) -> -1, any other -> its blob, row & (ML - 1)
   __device__ static __forceinline__ uint32_t row_word(uint32_t two) {
     const uint32_t x = (two & 0xFFu) | ((two & 0xFF00u) << 8);
+    if constexpr (ROWS) {
+      static_assert(!ROWS || kNone == 0x80u, "row_word: the record of zeros is the byte with bit 7 set");
+      return (x & ((uint32_t)(ML - 1) * 0x00010001u)) | ((x >> 7) & 0x00010001u) * 0xFFFFu;
+    }
     const uint32_t none = ((x + 0x00010001u) >> 8) & 0x00010001u;  // 1 where the byte was 0xFF
     return x | none * 0xFF00u;
   }
@@ -1399,7 +1513,7 @@ struct BBState {
     } else {
       for (int c = 0; c < C; c++) {
         const uint32_t k = (uint32_t)(w[3 + (CW == 1 ? 0 : c >> 3)] >> (8 * (c & 7))) & 0xFFu;
-        co[c] = k == 0xFFu ? (int16_t)-1 : (int16_t)k;
+        co[c] = k == kNone ? (int16_t)-1 : (int16_t)(ROWS ? k & (uint32_t)(ML - 1) : k);
       }
     }
     store_point(p, o, X);  // incl. the fused world-coordinate epilogue (helpers.py:96-103)

@@ -21,10 +21,12 @@
   if (item >= 0) st.prefetch_lds(item);
   wait_own_stores();
   __syncthreads();
+  st.pc_start();  // (the measuring build's phase clocks, BBState::pc_mark: empty otherwise)
   while (item >= 0) {
     const int64_t frame = item;
     bb_prio<kPrioPhase>();
     st.stage(frame);
+    st.template pc_mark<BB_STATE::PC_OTHER>();  // the frame's last barrier to its first: the swap, the status stores, the loop
     st.match();
     bb_prio<kPrioEval>();
     const int next = st.misc[MI_NEXT];
@@ -50,8 +52,10 @@
     wait_own_stores();  // ... and loads: the next frame's blobs are in LDS
     bb_prio<kPrioEval>();
     __syncthreads();  // the frame's LDS state is dead: the next one may be staged
+    st.template pc_mark<BB_STATE::PC_PHASE_E>();  // ... with the search's last wait and barrier (the winners' records are in L2)
     item = next;
   }
+  st.pc_flush();
   // the last workgroup to leave puts the queue counters back to zero: the next launch needs no memset
   if (tid == 0 && q_add(&q.counters[QC_EXITED], 1) == (int)gridDim.x - 1)
     for (int c = 0; c < QC_COUNT; c++) q_store(&q.counters[c], 0);
