@@ -610,6 +610,58 @@ int mocap_track_frame_ids_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const
                               int32_t* d_drone, int32_t* d_n_obj, const double* d_t, int32_t* d_mk_id, int32_t* d_mk_hits,
                               int32_t* d_mk_n_tracks, int32_t* d_mk_status);
 
+/* ---------------------------------------------------------------- point consolidation (the core's own contract)
+ * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
+ * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three
+ * points that share image blobs.  This stage, between the frame path (its re-submit included) and everything that reads its points,
+ * compacts each frame's points to a set in which no two share a blob.  Opt-in and the core's own: with the mode off every entry
+ * point writes the bytes it wrote before, and the mocap_match_triangulate* family never consolidates.
+ *
+ * Per frame f, over the points k in 0 .. n_out[f]) with their rows corr[f][k][0 .. C):
+ *   views(k)   the number of cameras c with corr[k][c] >= 0
+ *   conflict   i and j conflict iff corr[i][c] >= 0 and corr[i][c] == corr[j][c] for some camera c
+ *   key(k)     (-views(k), bits(err[k]) as an unsigned 64-bit integer, k), compared lexicographically: a total order, no tolerance
+ *              and no floating-point arithmetic (more views first, then the smaller error bits, then the smaller index)
+ *   selection  the kept set is what this walk yields: the points in ascending key, a point kept iff it conflicts with no point
+ *              kept before it.  A function of the input alone (the device computes it in rounds, in any order).  A suppressed
+ *              point suppresses nothing: in a chain A-B-C with key(A) < key(B) < key(C), A and C not in conflict, A and C are
+ *              kept and B is dropped.
+ *   compaction the kept points move, in place, to the slots 0 .. kept count) in ascending original index; the rows of xyz, err
+ *              and corr move together and n_out[f] becomes the kept count.  The slots from the new n_out up to the old one keep
+ *              whatever they held.  xyz is moved, never read for a decision: the rule is the same before and after the world
+ *              transform.
+ * A frame is processed iff status[f] & (MOCAP_ST_ROOT_OVERFLOW | MOCAP_ST_CAND_OVERFLOW | MOCAP_ST_HIT_OVERFLOW) == 0 and
+ * 0 <= n_out[f] <= K_max and every entry of its first n_out[f] rows lies in -1 .. 255.  Every other frame is left byte for byte as
+ * it is.
+ *
+ * mocap_set_point_consolidation: MOCAP_CONSOLIDATE_OFF (0, the default) | MOCAP_CONSOLIDATE_BLOBS (1); any other value is
+ * MOCAP_E_ARG and nothing changes.  The mode is honoured by every mocap_track_frame* entry point (host, images, _jpeg, and the
+ * _dev forms of plain, filtered, bodies and ids): the object search and the export, the rigid bodies, the marker tracker, the
+ * object filter and the epipolar-line overlay all see the consolidated points.  With the mode on K_max <= MOCAP_PC_MAX_POINTS
+ * (more is MOCAP_E_LIMIT) and a _dev call with d_corr == NULL is MOCAP_E_ARG.
+ *
+ * mocap_consolidate_points_dev / mocap_consolidate_points: the staged call on arrays as the frame path writes them, whatever the
+ * mode; C comes from mocap_set_cameras (MOCAP_E_NOCAMS without).
+ *   xyz [F][K_max][3], err [F][K_max], corr [F][K_max][C], n_pts [F]   in and out (mocap_match_triangulate's xyz, err, corr, n_out)
+ *   status [F]        in, may be NULL (= 0 for every frame)
+ *   src [F][K_max]    out, may be NULL: the original slot of each kept point (entries from the kept count on are not written)
+ *   n_in [F]          out, may be NULL: the count before consolidation, -1 = the frame was not processed
+ *   K_max             1 .. MOCAP_PC_MAX_POINTS (256): below is MOCAP_E_ARG, above MOCAP_E_LIMIT with the figure in the text
+ * One workgroup per frame, lane = point: one wave while K_max <= 64, 256 lanes above.  The "_dev" form
+ * enqueues on the context's stream (for batches); the host form uploads, runs and downloads, every array whole.
+ * Out of scope: re-triangulating a kept point from the union of its twins' blobs, a 3-D merge radius, more than 256 point slots
+ * per frame. */
+#define MOCAP_PC_MAX_POINTS 256
+enum {
+  MOCAP_CONSOLIDATE_OFF = 0,   /* the frame path's points as the reference's algorithm gives them (default) */
+  MOCAP_CONSOLIDATE_BLOBS = 1  /* no two points of a frame share a blob */
+};
+int mocap_set_point_consolidation(mocap_ctx* ctx, int mode);
+int mocap_consolidate_points(mocap_ctx* ctx, int64_t n_frames, int K_max, double* xyz, double* err, int16_t* corr, int32_t* n_pts,
+                             const int32_t* status, int32_t* src, int32_t* n_in);
+int mocap_consolidate_points_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, double* d_xyz, double* d_err, int16_t* d_corr,
+                                 int32_t* d_n_pts, const int32_t* d_status, int32_t* d_src, int32_t* d_n_in);
+
 /* ---------------------------------------------------------------- object filter
  * `filtered_objects` of the live loop (helpers.py:109, self.kalman_filter.predict_location(objects)): per drone index a
  * cv.KalmanFilter(9, 6) in float32 (constant acceleration, measurement = position and finite-difference velocity, nearest

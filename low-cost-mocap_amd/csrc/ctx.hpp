@@ -129,6 +129,7 @@ struct mocap_ctx {
   int mt_T = 0, mt_max_missed = 0;
   double mt_g2 = 0.0, mt_alpha = 0.0;
   DevBuf mt_state;          // MarkerTrackState: the track slots and next_id
+  int consolidate = 0;      // MOCAP_CONSOLIDATE_* (mocap_set_point_consolidation): the live loop's points compacted to one per blob, off by default
   DevBuf calib_ws;          // calibration tail: one partial per workgroup (pair sums | floor factors), csrc/calib_tail.hip
   // preview-stream JPEG encoder (csrc/jpeg_capi.hip): header and divisors of the last (H, T * W, quality), workspace of a chunk
   int jpeg_key[3] = {0, 0, 0};
@@ -183,6 +184,10 @@ int bodies_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double*
 int markers_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const MarkersIO& io);
 int markers_times_check(mocap_ctx* ctx, const char* who, int64_t n_frames, const double* t);  // host time stamps: all finite
 int markers_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const MarkersIO& io);
+// point consolidation (point_consolidate_capi.hip): the stage of the live loop between the re-submit and everything that reads the points
+int consolidate_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max);
+int consolidate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, double* d_xyz, double* d_err, int16_t* d_corr, int32_t* d_n_pts,
+                           const int32_t* d_status, int32_t* d_src, int32_t* d_n_in);
 
 // copier for copy_fields (io_fields.hpp) on the context's stream
 struct StreamCopy {

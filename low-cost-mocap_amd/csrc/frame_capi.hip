@@ -780,6 +780,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (!rc && stages.bodies) rc = bodies_check(ctx, "mocap_track_frame_bodies", n_frames, K_max, *stages.bodies);
   if (!rc && stages.markers) rc = markers_check(ctx, "mocap_track_frame_ids", n_frames, K_max, *stages.markers);
   if (!rc && stages.markers) rc = markers_times_check(ctx, "mocap_track_frame_ids", n_frames, stages.markers->t);
+  if (!rc && ctx->consolidate) rc = consolidate_check(ctx, "mocap_track_frame", n_frames, K_max);
   if (rc) return rc;
   if (jo) {  // the preview stream: the processed frames of the blob stage as one JPEG per frame set
     const char* bad = jpeg::check_args(n_frames, ctx->img_C, ctx->img_S, ctx->img_S, jo->quality, jo->capacity);
@@ -935,6 +936,9 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     // the reference has none (helpers.py:394-400) -- before the export; queued behind the first pass, no host round trip
     rc = resubmit_dev_locked(ctx, in, K_max, d, nullptr);
     if (rc) return rc;
+    // opt-in (mocap_set_point_consolidation): the export and every stage behind it see the consolidated points
+    if (ctx->consolidate) rc = consolidate_dev_locked(ctx, n_frames, K_max, d.xyz, d.err, d.corr, d.n_out, d.status, nullptr, nullptr);
+    if (rc) return rc;
     HIP_TRY(ctx, launch_track_export(la, ea, ctx->stream));
     // the stages read the frame's points where the frame path left them (device memory), the filter the export's objects in
     // the pinned block; time stamps travel through that block, every output lands in it
@@ -994,10 +998,14 @@ int track_dev_locked(mocap_ctx* ctx, const char* who, const FrameBatch& b, int K
   if (stages.filter) rc = filter_check(ctx, who, b.n_frames, o.O_max, *stages.filter);
   if (!rc && stages.bodies) rc = bodies_check(ctx, who, b.n_frames, K_max, *stages.bodies);
   if (!rc && stages.markers) rc = markers_check(ctx, who, b.n_frames, K_max, *stages.markers);
+  if (!rc && ctx->consolidate) rc = consolidate_check(ctx, who, b.n_frames, K_max);
+  if (!rc && ctx->consolidate && b.n_frames > 0 && !o.pts.corr) rc = ctx->fail(MOCAP_E_ARG, "%s: point consolidation is on and needs d_corr", who);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   rc = match_dev_locked(ctx, b, K_max, G_cap, o.pts);
   if (!rc) rc = resubmit_dev_locked(ctx, b, K_max, o.pts, nullptr);
+  if (!rc && ctx->consolidate && b.n_frames > 0)
+    rc = consolidate_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.err, o.pts.corr, o.pts.n_out, o.pts.status, nullptr, nullptr);
   if (!rc && (stages.filter || o.O_max > 0))
     rc = locate_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.err, o.pts.n_out, o.O_max, o.pos, o.heading, o.oerr, o.drone, nullptr, o.n_obj);
   if (!rc && stages.bodies) rc = bodies_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, *stages.bodies);

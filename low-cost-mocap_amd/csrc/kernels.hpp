@@ -279,6 +279,34 @@ struct MarkerTrackArgs {
 };
 hipError_t launch_marker_tracker(const MarkerTrackArgs& a, hipStream_t stream);
 
+// point consolidation (the core's own contract, include/mocap_core.h "point consolidation"), csrc/point_consolidate.hip: each
+// frame's points compacted in place to the set in which no two share a blob.  One workgroup per frame: one wave while
+// K_max <= 64, 256 lanes above.
+constexpr int kPcMaxPoints = 256;       // mirrored from include/mocap_core.h (MOCAP_PC_MAX_POINTS)
+constexpr int kPcBlobs = 256;           // a row entry is -1 .. 255: columns of the owner table
+constexpr int kPcRowEntries = 8192;     // int16 entries of the row buffer (16 KB): a frame of n points is staged whole while n * C fits
+constexpr int kPcStatusSkip = 1 | 2 | 4;  // MOCAP_ST_ROOT_OVERFLOW | CAND_OVERFLOW | HIT_OVERFLOW: the frame's outputs are invalid
+struct ConsolidateArgs {
+  int64_t n_frames;
+  int C, K_max;
+  double* xyz;                // [F][K_max][3]   moved, never read for a decision
+  double* err;                // [F][K_max]
+  int16_t* corr;              // [F][K_max][C]
+  int32_t* n_pts;             // [F]             in: points of the frame, out: points kept
+  const int32_t* status;      // [F] or null (= 0)
+  int32_t* src;               // [F][K_max] or null: the original slot of each kept point
+  int32_t* n_in;              // [F] or null: the count before, -1 = frame not processed
+};
+// the kernel's LDS: error bits [K_max] u64 | owner table [C][256] u32 | views, kept-by-rank [K_max] i32 | chunk counts [16] | rows
+__host__ __device__ inline int pc_row_entries(int C, int K_max) {
+  const int all = C * K_max;
+  return all < kPcRowEntries ? all : kPcRowEntries;
+}
+__host__ __device__ inline size_t pc_lds_bytes(int C, int K_max) {
+  return (size_t)K_max * 8 + (size_t)C * kPcBlobs * 4 + (size_t)K_max * 8 + 16 * 4 + (size_t)pc_row_entries(C, K_max) * 2;
+}
+hipError_t launch_point_consolidate(const ConsolidateArgs& a, hipStream_t stream);
+
 // calibration tail over a capture's frame-path outputs (reference index.py:158-194, :290-309), csrc/calib_tail.hip
 constexpr int kCalibThreads = 256;      // frames per workgroup: the grid is ceil(F / 256), a function of F alone
 constexpr int kPairSlabDoubles = 3;     // per workgroup: sum of pair distances, pairs, frames skipped

@@ -44,6 +44,9 @@ OPT_F32_ROUNDING = 1
 MT_MAX_TRACKS, MT_MAX_POINTS = 64, 64   # mocap_set_marker_tracker: track slots, points per frame
 MT_ST_FULL = 1            # per frame: a finite point found no free track slot (its id is -1)
 MT_ST_BAD_TIME = 2        # ... the frame's time stamp is not finite: no output, the state untouched
+CONSOLIDATE_OFF = 0       # mocap_set_point_consolidation: the frame path's points as the reference's algorithm gives them, the default
+CONSOLIDATE_BLOBS = 1     # ... compacted so that no two points of a frame share a blob (include/mocap_core.h)
+PC_MAX_POINTS = 256       # ... point slots per frame the consolidation takes
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
@@ -92,6 +95,9 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_track_frame_ids_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
+    "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_object_filter": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _dbl, _dbl]),
     "mocap_reset_object_filter": (_i32, [_vp, _dbl]),
     "mocap_filter_objects": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -215,6 +221,7 @@ class MocapCore:
         self.centroid_mode = CENTROID_REFERENCE   # CENTROID_* (set_centroid_mode), the library's default
         self.rigid_bodies_n = 0      # bodies registered by set_rigid_bodies, 0 = none
         self.marker_tracker = None   # (gate, max_missed, vel_alpha, T_max) of set_marker_tracker, None = off
+        self.point_consolidation = CONSOLIDATE_OFF   # CONSOLIDATE_* (set_point_consolidation), the library's default
 
     def close(self):
         if getattr(self, "_h", None):
@@ -794,6 +801,36 @@ class MocapCore:
             self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), float(gate_px), int(K_max), int(G_cap), _vp(d_xyz),
             _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
             _vp(d_drone or 0), _vp(d_n_obj or 0), _vp(d_t), _vp(d_id), _vp(d_hits), _vp(d_n_tracks), _vp(d_mk_status)))
+
+    # ------------------------------------------------------------------ point consolidation (each blob supports one point)
+    def set_point_consolidation(self, mode):
+        """mocap_set_point_consolidation: CONSOLIDATE_OFF (default) | CONSOLIDATE_BLOBS = every track_frame* entry point compacts a
+        frame's points to a set in which no two share a blob, in front of everything that reads them.  A mode the core refuses
+        (MOCAP_E_ARG) raises and changes nothing."""
+        self._check(self.lib.mocap_set_point_consolidation(self._h, int(mode)))
+        self.point_consolidation = int(mode)
+
+    def consolidate_points(self, xyz, err, corr, n_pts, status=None):
+        """mocap_consolidate_points over host arrays as the frame path writes them (xyz [F][K_max][3], err [F][K_max], corr
+        [F][K_max][C], n_pts [F], status [F] or None = 0).  The inputs are not touched; returns {"xyz", "err", "corr", "n_pts"}
+        compacted, "src" [F][K_max] = the original slot of each kept point (-1 from the kept count on) and "n_in" [F] = the
+        count before, -1 = the frame was not processed."""
+        xyz = np.array(xyz, dtype=np.float64, order="C")
+        F, K_max, _ = xyz.shape
+        err = np.array(err, dtype=np.float64, order="C").reshape(F, K_max)
+        corr = np.array(corr, dtype=np.int16, order="C")
+        assert corr.shape == (F, K_max, self.C) or not self.C
+        n_pts = np.array(n_pts, dtype=np.int32, order="C").reshape(F)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(F)
+        src = np.full((F, K_max), -1, dtype=np.int32)
+        n_in = np.full(F, -1, dtype=np.int32)
+        self._check(self.lib.mocap_consolidate_points(self._h, F, K_max, _p(xyz), _p(err), _p(corr), _p(n_pts), _p(status), _p(src),
+                                                      _p(n_in)))
+        return {"xyz": xyz, "err": err, "corr": corr, "n_pts": n_pts, "src": src, "n_in": n_in}
+
+    def consolidate_points_dev(self, n_frames, K_max, d_xyz, d_err, d_corr, d_n_pts, d_status=0, d_src=0, d_n_in=0):
+        self._check(self.lib.mocap_consolidate_points_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_err), _vp(d_corr),
+                                                          _vp(d_n_pts), _vp(d_status or 0), _vp(d_src or 0), _vp(d_n_in or 0)))
 
     # ------------------------------------------------------------------ object filter (`filtered_objects`)
     def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):

@@ -50,6 +50,7 @@ _state = {
     "centroid": capi.CENTROID_REFERENCE,   # capi.CENTROID_* of set_centroid_mode: integer centroids by default
     "bodies": None,          # set_rigid_bodies: (names, marker arrays, tol, max_rms, work_cap), None = no body registered
     "markers": None,         # set_marker_tracker: (gate, max_missed, vel_alpha, T_max), None = tracker off
+    "consolidate": capi.CONSOLIDATE_OFF,   # capi.CONSOLIDATE_* of set_point_consolidation: the reference's points by default
 }
 
 
@@ -81,6 +82,18 @@ def set_centroid_mode(mode):
         raise ValueError(f"unknown centroid mode {mode}")
     with _state["lock"]:
         _state["centroid"] = mode
+
+
+def set_point_consolidation(on):
+    """Each blob supports at most one object point (mocap_set_point_consolidation, include/mocap_core.h): with `on` true
+    track_frame*, camera_read_track and the payload built from them return a frame's points compacted to a set in which no two
+    share an image blob -- one point per marker instead of the reference's twins.  Off by default; remembered, and applied to a
+    core handed over later.  find_point_correspondance_and_object_points stays the reference's function."""
+    mode = capi.CONSOLIDATE_BLOBS if on else capi.CONSOLIDATE_OFF
+    with _state["lock"]:
+        _state["consolidate"] = mode
+        if _state["core"] is not None:
+            _state["core"].set_point_consolidation(mode)
 
 
 def _apply_overlay(core):
@@ -185,6 +198,8 @@ def _upload_cameras(camera_poses):
     if key != _state["cam_key"]:
         core.set_cameras(K, R, t)
         _state["cam_key"] = key
+    if getattr(core, "point_consolidation", capi.CONSOLIDATE_OFF) != _state["consolidate"]:   # a core handed over by set_core
+        core.set_point_consolidation(_state["consolidate"])
     return core
 
 
