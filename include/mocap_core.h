@@ -494,7 +494,8 @@ int mocap_track_frame_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const flo
  *   assign [8] i8  point index per marker, -1 = unassigned (markers >= N: -1)
  *   R [9] f64 row-major, t [3] f64: world = R body + t      rms f64      score f64 (the winner's)
  *   status i32   0 | MOCAP_RB_ST_RMS | MOCAP_RB_ST_WORK_CAP
- * Out of scope: identity over time, filtering of the poses, a second-best search, more than 64 points per frame. */
+ * Out of scope: identity over time (the "body tracker" section below), filtering of the poses, a second-best search, more than
+ * 64 points per frame. */
 #define MOCAP_RB_MAX_BODIES 8
 #define MOCAP_RB_MAX_MARKERS 8
 #define MOCAP_RB_MAX_POINTS 64
@@ -609,6 +610,115 @@ int mocap_track_frame_ids_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const
                               int32_t* d_n_pts, int32_t* d_status, int O_max, double* d_pos, double* d_heading, double* d_oerr,
                               int32_t* d_drone, int32_t* d_n_obj, const double* d_t, int32_t* d_mk_id, int32_t* d_mk_hits,
                               int32_t* d_mk_n_tracks, int32_t* d_mk_status);
+
+/* ---------------------------------------------------------------- body tracker (the core's own contract)
+ * The registered rigid bodies over time.  The rigid-body stage treats a frame on its own: a body with a symmetry changes its
+ * labelling, and so its R, from frame to frame; a body with fewer than three visible markers vanishes; nothing ties body b of
+ * this frame to body b of the last.  This stage associates each frame's points against the pose predicted from the last one,
+ * falls back on the per-frame search, and coasts through a few frames of occlusion.  Opt-in and the core's own: with the
+ * tracker off every entry point that existed before writes the bytes it wrote before.
+ *
+ * State (on the device, in the context): one slot per registered body b < MOCAP_RB_MAX_BODIES, each with
+ *   live (i32), R[9], p[3], v[3], t_seen (f64), missed, hits (i32)       world = R body + p (p is the t of "rigid bodies")
+ *
+ * mocap_set_body_tracker: on = 1 allocates and clears the state (and clears it when called again); on = 0 switches the tracker
+ * off and frees the state, the other arguments are ignored; any other value is MOCAP_E_ARG.
+ *   gate        metres, finite and > 0; g2 = gate * gate is formed once on the host in double
+ *   max_missed  >= 0: frames a body may coast before its slot is retired
+ *   vel_alpha   in [0, 1]: weight of the newest finite-difference velocity
+ * A bad value returns MOCAP_E_ARG and NOTHING changes.  tol, max_rms, the models and the posable tables are those of
+ * mocap_set_rigid_bodies.  A successful mocap_set_rigid_bodies (B = 0 included) clears the tracker's state -- the slots mean
+ * other bodies now -- and keeps its settings; with the tracker off that call does exactly what it did before.
+ *
+ * One frame at time t.  Inputs: the frame's points x_j, j < n (the first n_pts[f] of its K_max slots; K_max <= 64, more is
+ * MOCAP_E_ARG; n_pts[f] outside 0 .. K_max counts as 0, the "no valid slot" rule), and for every body the per-frame search's
+ * found[b] and assign[b][8] for this same frame: the search runs first, over the whole batch in parallel, exactly as
+ * mocap_locate_rigid_bodies_dev does, and the tracker reads its result arrays.
+ * All arithmetic is IEEE double, no fused operation, in the order written; sums of three terms are (a + b) + c.  Cl is the set
+ * of points claimed so far in this frame; it starts empty.  Bodies are taken in index order.
+ *   1. Prediction (live_b only).  dt = t - t_seen; p^ = p + v * dt per component when dt > 0, else p^ = p; R^ = R (the
+ *      orientation is held).
+ *   2. Guided association (live_b only), up to two rounds; round 1 starts from (Rc, pc) = (R^, p^).
+ *      Predicted markers m^_i[r] = ((Rc[3r] q_i0 + Rc[3r+1] q_i1) + Rc[3r+2] q_i2) + pc[r], i < N.
+ *      A pair (marker i, point j) is admissible iff j < n, x_j has three finite coordinates, j is not in Cl and
+ *      d2 = dx dx + dy dy + dz dz < g2 (strict), d = x_j - m^_i, the sum taken in x, y, z order.
+ *      The admissible pairs are taken in ascending lexicographic (d2, i, j); a pair is committed when neither its marker nor
+ *      its point is taken.
+ *      The round PASSES iff the assigned marker subset is posable (the body's 256-bit table) and the pose of that assignment --
+ *      the procedure of "rigid bodies", unchanged: centroids, S, Horn's matrix, cyclic Jacobi, quaternion -> R, t, rms in
+ *      centred coordinates -- has rms <= max_rms.
+ *      Round 1 fails: guided fails.  Round 1 passes: round 2 repeats association and fit from round 1's (R, t) over the same
+ *      point set (round 1's points are free again); round 2 stands if it passes, otherwise round 1 stands.
+ *   3. Outcome, the first that applies.
+ *      GUIDED  step 2 gave a result.
+ *      SEARCH  found[b] == 1 and none of the search's assigned points is in Cl: the assignment is the search's, the pose is
+ *              recomputed by the same procedure (the same arithmetic: the search's own R, t, rms).
+ *      COAST   live_b.  missed += 1; missed > max_missed: the slot is retired (live = 0) and the frame's outputs for the body
+ *              are those of NONE.  Otherwise the outputs carry (R^, p^) with n_used = 0, assign all -1 and rms = 0.  Nothing is
+ *              claimed; R, p, v, t_seen are kept.
+ *      NONE
+ *   4. Update on GUIDED / SEARCH.  Slot live and dt > 0: u = (t_new - p) / dt per component, v = v + vel_alpha * (u - v);
+ *      slot live and dt <= 0: v unchanged; slot not live: v = 0, hits = 0.  Then R = R_new, p = t_new, t_seen = t, missed = 0,
+ *      hits += 1, live = 1, and the assigned points join Cl.
+ * A non-finite t: status MOCAP_BT_ST_BAD_TIME, the frame's outputs are zero and the state is untouched -- the "_dev" forms
+ * report it this way; the host forms reject a non-finite t with MOCAP_E_ARG before anything runs.
+ * Cutting a session into calls of any lengths gives bit-identical outputs and state.
+ *
+ * Outputs, all [F][B_max] but status; zero-filled where source = NONE and in the slots beyond the registered bodies:
+ *   tracked i32   1 for GUIDED / SEARCH / COAST          source i32   MOCAP_BT_SRC_NONE | _GUIDED | _SEARCH | _COAST
+ *   n_used i32    assigned markers                        assign [8] i8  point index per marker, -1 = unassigned
+ *   R [9], t [3], rms f64: world = R body + t             hits, missed i32  the slot's, after the frame
+ *   status [F] i32  0 | MOCAP_BT_ST_BAD_TIME
+ * Every entry point of this section returns MOCAP_E_ARG with the tracker off, with K_max > 64, with B_max below the registered
+ * bodies, or with a null buffer.  With no bodies registered the outputs are zero-filled.
+ * Out of scope: angular velocity in the prediction (a body that turns while fully hidden re-acquires through the search and
+ * may change labelling there), a partial update from one or two markers, low-pass filtering of the poses, more than 64 points. */
+enum {
+  MOCAP_BT_SRC_NONE = 0,    /* the body has no pose in this frame */
+  MOCAP_BT_SRC_GUIDED = 1,  /* associated against the predicted pose */
+  MOCAP_BT_SRC_SEARCH = 2,  /* (re-)acquired from the per-frame search */
+  MOCAP_BT_SRC_COAST = 3    /* not seen: the predicted pose */
+};
+enum {
+  MOCAP_BT_ST_BAD_TIME = 1  /* the frame's time stamp is not finite: no output, the state untouched */
+};
+int mocap_set_body_tracker(mocap_ctx* ctx, int on, double gate, int max_missed, double vel_alpha);
+/* clears all slots; enqueued on the context's stream */
+int mocap_reset_body_tracker(mocap_ctx* ctx);
+/* n_frames consecutive frames, in order: t [F], xyz [F][K_max][3], n_pts [F] (mocap_match_triangulate's xyz and n_out) -> the
+ * outputs above.  The search runs into context-owned scratch, then one wave walks the frames, lane = point, both on the
+ * context's stream.  The "_dev" form enqueues (for batches); the host form uploads, runs and downloads. */
+int mocap_track_bodies(mocap_ctx* ctx, int64_t n_frames, const double* t, int K_max, const double* xyz, const int32_t* n_pts,
+                       int B_max, int32_t* tracked, int32_t* source, int32_t* n_used, int8_t* assign, double* R, double* t_pose,
+                       double* rms, int32_t* hits, int32_t* missed, int32_t* status);
+int mocap_track_bodies_dev(mocap_ctx* ctx, int64_t n_frames, const double* d_t, int K_max, const double* d_xyz,
+                           const int32_t* d_n_pts, int B_max, int32_t* d_tracked, int32_t* d_source, int32_t* d_n_used,
+                           int8_t* d_assign, double* d_R, double* d_t_pose, double* d_rms, int32_t* d_hits, int32_t* d_missed,
+                           int32_t* d_status);
+/* all eight slots as they are (synchronises): live, t_seen, missed, hits [8], R [8][9], p, v [8][3] (host) */
+int mocap_get_body_tracks(mocap_ctx* ctx, int32_t* live, double* R, double* p, double* v, double* t_seen, int32_t* missed,
+                          int32_t* hits);
+/* mocap_track_frame_bodies / mocap_track_frame_bodies_dev with t [F] in and the tracker's outputs appended; every other
+ * argument and every shared output (the search's rb_* included) as there, bit for bit.  The host form queues the tracker
+ * behind the rigid-body kernel and writes into the same pinned block: still one enqueue and one event wait.  Point
+ * consolidation is honoured like in the other forms. */
+int mocap_track_frame_bodies_tracked(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                                     double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr,
+                                     int32_t* n_pts, int32_t* status, int O_max, double* pos, double* heading, double* oerr,
+                                     int32_t* drone, int32_t* n_obj, int B_max, int32_t* rb_found, int32_t* rb_n_used,
+                                     int8_t* rb_assign, double* rb_R, double* rb_t, double* rb_rms, double* rb_score,
+                                     int32_t* rb_status, const double* t, int32_t* bt_tracked, int32_t* bt_source,
+                                     int32_t* bt_n_used, int8_t* bt_assign, double* bt_R, double* bt_t, double* bt_rms,
+                                     int32_t* bt_hits, int32_t* bt_missed, int32_t* bt_status);
+int mocap_track_frame_bodies_tracked_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
+                                         const int32_t* d_counts, double gate_px, int K_max, int64_t G_cap, double* d_xyz,
+                                         double* d_err, int16_t* d_corr, int32_t* d_n_pts, int32_t* d_status, int O_max,
+                                         double* d_pos, double* d_heading, double* d_oerr, int32_t* d_drone, int32_t* d_n_obj,
+                                         int B_max, int32_t* d_rb_found, int32_t* d_rb_n_used, int8_t* d_rb_assign,
+                                         double* d_rb_R, double* d_rb_t, double* d_rb_rms, double* d_rb_score,
+                                         int32_t* d_rb_status, const double* d_t, int32_t* d_bt_tracked, int32_t* d_bt_source,
+                                         int32_t* d_bt_n_used, int8_t* d_bt_assign, double* d_bt_R, double* d_bt_t,
+                                         double* d_bt_rms, int32_t* d_bt_hits, int32_t* d_bt_missed, int32_t* d_bt_status);
 
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,

@@ -143,6 +143,11 @@ struct mocap_ctx {
   double rb_tol = 0.0, rb_max_rms = 0.0;
   long long rb_work_cap = 0;
   DevBuf rb_models;         // RigidBodyModel [rb_B]: markers, pair distances and the posability mask of every body
+  // body tracker (mocap_set_body_tracker, csrc/body_track_capi.hip): bt_on == 0 = off
+  int bt_on = 0, bt_max_missed = 0;
+  double bt_g2 = 0.0, bt_alpha = 0.0;
+  DevBuf bt_state;          // BodyTrackState: one slot per registered body
+  DevBuf bt_search;         // mocap_track_bodies*: the per-frame search's outputs, which the tracker reads
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);
@@ -184,6 +189,11 @@ int bodies_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double*
 int markers_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const MarkersIO& io);
 int markers_times_check(mocap_ctx* ctx, const char* who, int64_t n_frames, const double* t);  // host time stamps: all finite
 int markers_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, const MarkersIO& io);
+// body tracker (body_track_capi.hip): behind the rigid-body stage, whose found / assign arrays of the same frames it reads
+int tracked_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, int B_max, const TrackedIO& io);
+int tracked_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts, int B_max,
+                       const int32_t* d_rb_found, const int8_t* d_rb_assign, const TrackedIO& io);
+int tracked_clear_locked(mocap_ctx* ctx);  // all slots cleared, on the stream; nothing with the tracker off
 // point consolidation (point_consolidate_capi.hip): the stage of the live loop between the re-submit and everything that reads the points
 int consolidate_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max);
 int consolidate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, double* d_xyz, double* d_err, int16_t* d_corr, int32_t* d_n_pts,

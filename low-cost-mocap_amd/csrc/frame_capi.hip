@@ -746,15 +746,17 @@ struct TrackStages {
   const JpegOut* jpeg = nullptr;       // mocap_track_frame_images_jpeg: the preview stream
   const BodiesIO* bodies = nullptr;    // mocap_track_frame_bodies: the rigid-body locator
   const MarkersIO* markers = nullptr;  // mocap_track_frame_ids: time stamps in, the marker tracker's outputs out
+  const TrackedIO* tracked = nullptr;  // mocap_track_frame_bodies_tracked: behind `bodies`, time stamps in, the body tracker's outputs out
   TrackStages() = default;
   TrackStages(const FilterIO& io) : filter(&io) {}
   TrackStages(const JpegOut& io) : jpeg(&io) {}
   TrackStages(const BodiesIO& io) : bodies(&io) {}
   TrackStages(const MarkersIO& io) : markers(&io) {}
+  TrackStages(const BodiesIO& rb, const TrackedIO& io) : bodies(&rb), tracked(&io) {}
 };
 
 // images != null: raw frames [F][C][rows][cols][3] (host); else b.blobs / b.counts (host) are the input.  The filter, the
-// bodies and the markers are described once (io_fields.hpp): their arrays are carved from the same pinned block as the frame's
+// bodies, the markers and the tracked bodies are described once (io_fields.hpp): their arrays are carved from the same pinned block as the frame's
 // outputs, their kernels are queued behind the export and write into that block, their outputs are copied to the caller -- the
 // call still waits for one event.  The JPEG stream stays written out here: its slots have a 16-byte stride in the block and only
 // the bytes that exist are copied back, which no field list says.
@@ -777,7 +779,10 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (images && (!o.blobs || !o.counts || !o.blob_status)) return ctx->fail(MOCAP_E_ARG, "mocap_track_frame_images: null blob buffer");
   int rc = MOCAP_OK;
   if (stages.filter) rc = filter_check(ctx, "mocap_track_frame_filtered", n_frames, o.O_max, *stages.filter);
-  if (!rc && stages.bodies) rc = bodies_check(ctx, "mocap_track_frame_bodies", n_frames, K_max, *stages.bodies);
+  const char* who_bodies = stages.tracked ? "mocap_track_frame_bodies_tracked" : "mocap_track_frame_bodies";
+  if (!rc && stages.tracked) rc = tracked_check(ctx, who_bodies, n_frames, K_max, stages.bodies->B_max, *stages.tracked);
+  if (!rc && stages.bodies) rc = bodies_check(ctx, who_bodies, n_frames, K_max, *stages.bodies);
+  if (!rc && stages.tracked) rc = markers_times_check(ctx, who_bodies, n_frames, stages.tracked->t);
   if (!rc && stages.markers) rc = markers_check(ctx, "mocap_track_frame_ids", n_frames, K_max, *stages.markers);
   if (!rc && stages.markers) rc = markers_times_check(ctx, "mocap_track_frame_ids", n_frames, stages.markers->t);
   if (!rc && ctx->consolidate) rc = consolidate_check(ctx, "mocap_track_frame", n_frames, K_max);
@@ -803,6 +808,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   FilterIO hf{};
   BodiesIO hb{(int)n.B};
   MarkersIO hm{};
+  TrackedIO ht{};
   auto lay_host = [&](void* base) {
     Carver c(base);
     h_blobs = c.take<float>(F * C * M_max * 2);
@@ -826,6 +832,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     }
     if (stages.bodies) carve(c, hb, n);
     if (stages.markers) carve(c, hm, n);
+    if (stages.tracked) carve(c, ht, n);
     return c.off;
   };
   const size_t host_total = lay_host(nullptr);
@@ -943,6 +950,8 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     // the stages read the frame's points where the frame path left them (device memory), the filter the export's objects in
     // the pinned block; time stamps travel through that block, every output lands in it
     if (stages.bodies) rc = bodies_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hb);
+    if (!rc && stages.tracked) rc = copy_fields<true>(ht, *stages.tracked, n, HostCopy{});
+    if (!rc && stages.tracked) rc = tracked_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hb.B_max, hb.found, hb.assign, ht);
     if (!rc && stages.markers) rc = copy_fields<true>(hm, *stages.markers, n, HostCopy{});
     if (!rc && stages.markers) rc = markers_dev_locked(ctx, n_frames, K_max, d.xyz, d.n_out, hm);
     if (!rc && stages.filter) rc = copy_fields<true>(hf, *stages.filter, n, HostCopy{});
@@ -974,6 +983,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (stages.filter) copy_fields<false>(*stages.filter, hf, n, HostCopy{});
   if (stages.bodies) copy_fields<false>(*stages.bodies, hb, n, HostCopy{});
   if (stages.markers) copy_fields<false>(*stages.markers, hm, n, HostCopy{});
+  if (stages.tracked) copy_fields<false>(*stages.tracked, ht, n, HostCopy{});
   for (size_t f = 0; f < F && jo; f++) {
     jo->size[f] = h_jsize[f];
     memcpy(jo->jpeg + f * (size_t)jo->capacity, h_jpeg + f * j_stride, (size_t)(h_jsize[f] < jo->capacity ? h_jsize[f] : jo->capacity));
@@ -996,6 +1006,7 @@ int track_dev_locked(mocap_ctx* ctx, const char* who, const FrameBatch& b, int K
                      const TrackStages& stages) {
   int rc = MOCAP_OK;
   if (stages.filter) rc = filter_check(ctx, who, b.n_frames, o.O_max, *stages.filter);
+  if (!rc && stages.tracked) rc = tracked_check(ctx, who, b.n_frames, K_max, stages.bodies->B_max, *stages.tracked);
   if (!rc && stages.bodies) rc = bodies_check(ctx, who, b.n_frames, K_max, *stages.bodies);
   if (!rc && stages.markers) rc = markers_check(ctx, who, b.n_frames, K_max, *stages.markers);
   if (!rc && ctx->consolidate) rc = consolidate_check(ctx, who, b.n_frames, K_max);
@@ -1009,6 +1020,9 @@ int track_dev_locked(mocap_ctx* ctx, const char* who, const FrameBatch& b, int K
   if (!rc && (stages.filter || o.O_max > 0))
     rc = locate_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.err, o.pts.n_out, o.O_max, o.pos, o.heading, o.oerr, o.drone, nullptr, o.n_obj);
   if (!rc && stages.bodies) rc = bodies_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, *stages.bodies);
+  if (!rc && stages.tracked)
+    rc = tracked_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, stages.bodies->B_max, stages.bodies->found,
+                            stages.bodies->assign, *stages.tracked);
   if (!rc && stages.markers) rc = markers_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, *stages.markers);
   if (!rc && stages.filter) rc = filter_dev_locked(ctx, b.n_frames, o.O_max, o.pos, o.heading, o.drone, o.n_obj, *stages.filter);
   return rc ? rc : ctx->mark_enqueued();
@@ -1086,6 +1100,43 @@ extern "C" int mocap_track_frame_bodies_dev(mocap_ctx* ctx, int64_t n_frames, in
   const TrackOut o{{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr}, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj};
   const BodiesIO io{B_max, d_rb_found, d_rb_n_used, d_rb_assign, d_rb_R, d_rb_t, d_rb_rms, d_rb_score, d_rb_status};
   return track_dev_locked(ctx, "mocap_track_frame_bodies_dev", FrameBatch{n_frames, M_max, d_blobs, d_counts, gate_px}, K_max, G_cap, o, io);
+}
+
+// mocap_track_frame_bodies / _dev with the body tracker (csrc/body_track.hip) behind the rigid-body stage
+extern "C" int mocap_track_frame_bodies_tracked(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts,
+                                                double gate_px, int K_max, int64_t G_cap, double* xyz, double* err, int16_t* corr,
+                                                int32_t* n_pts, int32_t* status, int O_max, double* pos, double* heading, double* oerr,
+                                                int32_t* drone, int32_t* n_obj, int B_max, int32_t* rb_found, int32_t* rb_n_used,
+                                                int8_t* rb_assign, double* rb_R, double* rb_t, double* rb_rms, double* rb_score,
+                                                int32_t* rb_status, const double* t, int32_t* bt_tracked, int32_t* bt_source,
+                                                int32_t* bt_n_used, int8_t* bt_assign, double* bt_R, double* bt_t, double* bt_rms,
+                                                int32_t* bt_hits, int32_t* bt_missed, int32_t* bt_status) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const TrackOut o{{xyz, err, corr, n_pts, status, nullptr}, O_max, pos, heading, oerr, drone, n_obj};
+  const BodiesIO rb{B_max, rb_found, rb_n_used, rb_assign, rb_R, rb_t, rb_rms, rb_score, rb_status};
+  const TrackedIO io{t, bt_tracked, bt_source, bt_n_used, bt_assign, bt_R, bt_t, bt_rms, bt_hits, bt_missed, bt_status};
+  return track_locked(ctx, nullptr, FrameBatch{n_frames, M_max, blobs, counts, gate_px}, K_max, G_cap, o, TrackStages{rb, io});
+}
+
+extern "C" int mocap_track_frame_bodies_tracked_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs,
+                                                    const int32_t* d_counts, double gate_px, int K_max, int64_t G_cap, double* d_xyz,
+                                                    double* d_err, int16_t* d_corr, int32_t* d_n_pts, int32_t* d_status, int O_max,
+                                                    double* d_pos, double* d_heading, double* d_oerr, int32_t* d_drone,
+                                                    int32_t* d_n_obj, int B_max, int32_t* d_rb_found, int32_t* d_rb_n_used,
+                                                    int8_t* d_rb_assign, double* d_rb_R, double* d_rb_t, double* d_rb_rms,
+                                                    double* d_rb_score, int32_t* d_rb_status, const double* d_t, int32_t* d_bt_tracked,
+                                                    int32_t* d_bt_source, int32_t* d_bt_n_used, int8_t* d_bt_assign, double* d_bt_R,
+                                                    double* d_bt_t, double* d_bt_rms, int32_t* d_bt_hits, int32_t* d_bt_missed,
+                                                    int32_t* d_bt_status) {
+  if (!ctx) return MOCAP_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const TrackOut o{{d_xyz, d_err, d_corr, d_n_pts, d_status, nullptr}, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj};
+  const BodiesIO rb{B_max, d_rb_found, d_rb_n_used, d_rb_assign, d_rb_R, d_rb_t, d_rb_rms, d_rb_score, d_rb_status};
+  const TrackedIO io{d_t, d_bt_tracked, d_bt_source, d_bt_n_used, d_bt_assign, d_bt_R, d_bt_t, d_bt_rms, d_bt_hits, d_bt_missed,
+                     d_bt_status};
+  return track_dev_locked(ctx, "mocap_track_frame_bodies_tracked_dev", FrameBatch{n_frames, M_max, d_blobs, d_counts, gate_px}, K_max, G_cap,
+                          o, TrackStages{rb, io});
 }
 
 // mocap_track_frame / mocap_track_frame_dev with the marker tracker (csrc/marker_track.hip) behind the object search

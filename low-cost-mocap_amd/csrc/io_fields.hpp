@@ -1,4 +1,4 @@
-// io_fields.hpp -- the argument blocks of the optional stages of the C ABI (object filter, rigid bodies, marker tracker) and
+// io_fields.hpp -- the argument blocks of the optional stages of the C ABI (object filter, rigid bodies, marker tracker, body tracker) and
 // the ONE list of each block's arrays: every layout, staging copy and copy-back of a stage goes through these lists, so a
 // field's type and element count are written once.  No HIP here: tests/native/io_fields_check.cpp compiles this for the host.
 #pragma once
@@ -87,6 +87,35 @@ struct MarkersIO {
     fn(&MarkersIO::hits, n.F * n.K);
     fn(&MarkersIO::n_tracks, n.F);
     fn(&MarkersIO::status, n.F);
+  }
+};
+// body tracker behind the rigid bodies (body_track_capi.hip); every pointer device-accessible, arrays [F][B_max] but t, status
+struct TrackedIO {
+  const double* t;    // [F] time stamps
+  int32_t* tracked;
+  int32_t* source;
+  int32_t* n_used;
+  int8_t* assign;     // [F][B_max][8]
+  double* R;          // [F][B_max][9]
+  double* p;          // [F][B_max][3]: the pose's translation (the t of BodiesIO)
+  double* rms;
+  int32_t* hits;
+  int32_t* missed;
+  int32_t* status;    // [F]
+  template <class Fn>
+  static void fields(const IoDims& n, Fn&& fn) {
+    const size_t FB = n.F * n.B;
+    fn(&TrackedIO::t, n.F);
+    fn(&TrackedIO::tracked, FB);
+    fn(&TrackedIO::source, FB);
+    fn(&TrackedIO::n_used, FB);
+    fn(&TrackedIO::assign, FB * BodiesIO::kAssign);
+    fn(&TrackedIO::R, FB * 9);
+    fn(&TrackedIO::p, FB * 3);
+    fn(&TrackedIO::rms, FB);
+    fn(&TrackedIO::hits, FB);
+    fn(&TrackedIO::missed, FB);
+    fn(&TrackedIO::status, n.F);
   }
 };
 

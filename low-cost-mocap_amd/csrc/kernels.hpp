@@ -279,6 +279,43 @@ struct MarkerTrackArgs {
 };
 hipError_t launch_marker_tracker(const MarkerTrackArgs& a, hipStream_t stream);
 
+// body tracker (the core's own contract, include/mocap_core.h "body tracker"), csrc/body_track.hip: the registered rigid bodies
+// followed from frame to frame -- association against the predicted pose, the per-frame search as the fall-back, coasting.
+// The state of the recurrence lives in one device record per context.
+constexpr int BT_SRC_NONE_ = 0, BT_SRC_GUIDED_ = 1, BT_SRC_SEARCH_ = 2, BT_SRC_COAST_ = 3;  // mirrored from include/mocap_core.h (MOCAP_BT_*)
+constexpr int BT_ST_BAD_TIME_ = 1;
+struct BodyTrackState {       // all zero = no body tracked; one slot per registered body
+  int32_t live[kRbMaxBodies];
+  double R[kRbMaxBodies][9], p[kRbMaxBodies][3], v[kRbMaxBodies][3];  // world = R body + p
+  double t_seen[kRbMaxBodies];
+  int32_t missed[kRbMaxBodies], hits[kRbMaxBodies];
+};
+struct BodyTrackArgs {
+  int64_t n_frames;
+  int K_max, B, B_max;        // point slots per frame (<= 64); registered bodies; body slots per frame of the arrays (>= B)
+  int max_missed;
+  double g2, vel_alpha;       // gate * gate (formed on the host)
+  double max_rms;             // of mocap_set_rigid_bodies
+  const RigidBodyModel* models;  // [B]
+  const double* t;            // [F] time stamps
+  const double* xyz;          // [F][K_max][3]
+  const int32_t* n_pts;       // [F]
+  const int32_t* rb_found;    // [F][B_max]      the per-frame search's results for the same frames
+  const int8_t* rb_assign;    // [F][B_max][8]
+  BodyTrackState* state;
+  int32_t* tracked;           // [F][B_max]
+  int32_t* source;            // [F][B_max]
+  int32_t* n_used;            // [F][B_max]
+  int8_t* assign;             // [F][B_max][8]
+  double* R;                  // [F][B_max][9]
+  double* p;                  // [F][B_max][3]
+  double* rms;                // [F][B_max]
+  int32_t* hits;              // [F][B_max]
+  int32_t* missed;            // [F][B_max]
+  int32_t* status;            // [F]
+};
+hipError_t launch_body_tracker(const BodyTrackArgs& a, hipStream_t stream);
+
 // point consolidation (the core's own contract, include/mocap_core.h "point consolidation"), csrc/point_consolidate.hip: each
 // frame's points compacted in place to the set in which no two share a blob.  One workgroup per frame: one wave while
 // K_max <= 64, 256 lanes above.

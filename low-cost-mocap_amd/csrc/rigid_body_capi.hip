@@ -61,7 +61,7 @@ extern "C" int mocap_set_rigid_bodies(mocap_ctx* ctx, int B, const int32_t* n_ma
   if (B < 0 || B > kRbMaxBodies) return ctx->fail(MOCAP_E_ARG, "mocap_set_rigid_bodies: B=%d outside 0 .. %d", B, kRbMaxBodies);
   if (B == 0) {
     ctx->rb_B = 0;
-    return MOCAP_OK;
+    return tracked_clear_locked(ctx);  // (the body tracker's slots mean other bodies now; nothing with the tracker off)
   }
   if (!n_markers || !markers) return ctx->fail(MOCAP_E_ARG, "mocap_set_rigid_bodies: null buffer");
   if (!(tol > 0.0) || !(max_rms > 0.0) || !std::isfinite(tol) || !std::isfinite(max_rms) || work_cap < 0)
@@ -103,7 +103,7 @@ extern "C" int mocap_set_rigid_bodies(mocap_ctx* ctx, int B, const int32_t* n_ma
   ctx->rb_tol = tol;
   ctx->rb_max_rms = max_rms;
   ctx->rb_work_cap = work_cap > 0 ? (long long)work_cap : kRbDefaultWorkCap;
-  return MOCAP_OK;
+  return tracked_clear_locked(ctx);  // (the body tracker's slots mean other bodies now; nothing with the tracker off)
 }
 
 int bodies_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max, const BodiesIO& io) {

@@ -44,6 +44,8 @@ OPT_F32_ROUNDING = 1
 MT_MAX_TRACKS, MT_MAX_POINTS = 64, 64   # mocap_set_marker_tracker: track slots, points per frame
 MT_ST_FULL = 1            # per frame: a finite point found no free track slot (its id is -1)
 MT_ST_BAD_TIME = 2        # ... the frame's time stamp is not finite: no output, the state untouched
+BT_SRC_NONE, BT_SRC_GUIDED, BT_SRC_SEARCH, BT_SRC_COAST = 0, 1, 2, 3   # mocap_track_bodies: where a body's pose of a frame comes from
+BT_ST_BAD_TIME = 1        # per frame: the time stamp is not finite: no output, the state untouched
 CONSOLIDATE_OFF = 0       # mocap_set_point_consolidation: the frame path's points as the reference's algorithm gives them, the default
 CONSOLIDATE_BLOBS = 1     # ... compacted so that no two points of a frame share a blob (include/mocap_core.h)
 PC_MAX_POINTS = 256       # ... point slots per frame the consolidation takes
@@ -95,6 +97,17 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_track_frame_ids_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_set_body_tracker": (_i32, [_vp, _i32, _dbl, _i32, _dbl]),
+    "mocap_reset_body_tracker": (_i32, [_vp]),
+    "mocap_track_bodies": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_bodies_dev": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_get_body_tracks": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_bodies_tracked": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                                _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp]),
+    "mocap_track_frame_bodies_tracked_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                                    _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -221,6 +234,7 @@ class MocapCore:
         self.centroid_mode = CENTROID_REFERENCE   # CENTROID_* (set_centroid_mode), the library's default
         self.rigid_bodies_n = 0      # bodies registered by set_rigid_bodies, 0 = none
         self.marker_tracker = None   # (gate, max_missed, vel_alpha, T_max) of set_marker_tracker, None = off
+        self.body_tracker = None     # (gate, max_missed, vel_alpha) of set_body_tracker, None = off
         self.point_consolidation = CONSOLIDATE_OFF   # CONSOLIDATE_* (set_point_consolidation), the library's default
 
     def close(self):
@@ -801,6 +815,84 @@ class MocapCore:
             self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), float(gate_px), int(K_max), int(G_cap), _vp(d_xyz),
             _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
             _vp(d_drone or 0), _vp(d_n_obj or 0), _vp(d_t), _vp(d_id), _vp(d_hits), _vp(d_n_tracks), _vp(d_mk_status)))
+
+    # ------------------------------------------------------------------ body tracker (the registered bodies over time)
+    def set_body_tracker(self, gate=0.03, max_missed=10, vel_alpha=0.5, on=True):
+        """mocap_set_body_tracker: allocates and clears the tracker's slots (one per registered body).  gate in metres = how far a
+        marker may be from where the predicted pose puts it; max_missed = frames a body may coast; vel_alpha in [0, 1];
+        on=False switches the tracker off.  Settings the core refuses (MOCAP_E_ARG) raise and change nothing."""
+        self._check(self.lib.mocap_set_body_tracker(self._h, 1 if on else 0, float(gate), int(max_missed), float(vel_alpha)))
+        self.body_tracker = (float(gate), int(max_missed), float(vel_alpha)) if on else None
+
+    def reset_body_tracker(self):
+        self._check(self.lib.mocap_reset_body_tracker(self._h))
+
+    @staticmethod
+    def _tracked_outputs(F, B_max):
+        return {"tracked": np.zeros((F, B_max), dtype=np.int32), "source": np.zeros((F, B_max), dtype=np.int32),
+                "bt_n_used": np.zeros((F, B_max), dtype=np.int32), "bt_assign": np.zeros((F, B_max, RB_MAX_MARKERS), dtype=np.int8),
+                "bt_R": np.zeros((F, B_max, 3, 3)), "bt_t": np.zeros((F, B_max, 3)), "bt_rms": np.zeros((F, B_max)),
+                "bt_hits": np.zeros((F, B_max), dtype=np.int32), "bt_missed": np.zeros((F, B_max), dtype=np.int32),
+                "bt_status": np.zeros(F, dtype=np.int32)}
+
+    @staticmethod
+    def _tracked_ptrs(o):
+        return [_p(o[k]) for k in ("tracked", "source", "bt_n_used", "bt_assign", "bt_R", "bt_t", "bt_rms", "bt_hits", "bt_missed",
+                                   "bt_status")]
+
+    def track_bodies(self, t, xyz, n_pts, B_max=None):
+        """mocap_track_bodies over host arrays t [F], xyz [F][K_max][3] (K_max <= 64), n_pts [F], consecutive frames in order ->
+        {"tracked", "source" (BT_SRC_*), "bt_n_used", "bt_hits", "bt_missed" [F][B], "bt_assign" int8 [F][B][8], "bt_R" [F][B][3][3],
+        "bt_t" [F][B][3], "bt_rms" [F][B], "bt_status" [F]}; the entries of a body without a pose (source 0) are zero.  B_max: body
+        slots per frame, default = the registered bodies."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        F, K_max, _ = xyz.shape
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        B_max = self.rigid_bodies_n if B_max is None else int(B_max)
+        o = self._tracked_outputs(F, B_max)
+        self._check(self.lib.mocap_track_bodies(self._h, F, _p(t), K_max, _p(xyz), _p(n_pts), B_max, *self._tracked_ptrs(o)))
+        return o
+
+    def track_bodies_dev(self, n_frames, d_t, K_max, d_xyz, d_n_pts, B_max, d_tracked, d_source, d_n_used, d_assign, d_R, d_t_pose,
+                         d_rms, d_hits, d_missed, d_status):
+        self._check(self.lib.mocap_track_bodies_dev(self._h, int(n_frames), _vp(d_t), int(K_max), _vp(d_xyz), _vp(d_n_pts), int(B_max),
+                                                    _vp(d_tracked), _vp(d_source), _vp(d_n_used), _vp(d_assign), _vp(d_R),
+                                                    _vp(d_t_pose), _vp(d_rms), _vp(d_hits), _vp(d_missed), _vp(d_status)))
+
+    def get_body_tracks(self):
+        """mocap_get_body_tracks (synchronises): all eight slots as they are, {"live", "missed", "hits" [8], "R" [8][3][3],
+        "p", "v" [8][3], "t_seen" [8]}; slot b belongs to registered body b."""
+        B = RB_MAX_BODIES
+        o = {"live": np.zeros(B, dtype=np.int32), "R": np.zeros((B, 3, 3)), "p": np.zeros((B, 3)), "v": np.zeros((B, 3)),
+             "t_seen": np.zeros(B), "missed": np.zeros(B, dtype=np.int32), "hits": np.zeros(B, dtype=np.int32)}
+        self._check(self.lib.mocap_get_body_tracks(self._h, *[_p(o[k]) for k in ("live", "R", "p", "v", "t_seen", "missed", "hits")]))
+        return o
+
+    def track_frame_bodies_tracked(self, blobs, counts, t, gate_px=5.0, K_max=None, G_cap=1 << 20, O_max=8, B_max=None):
+        """mocap_track_frame_bodies_tracked: track_frame_bodies with the body tracker behind the rigid-body stage, t [F] = the
+        frames' time stamps; the same dict plus the keys of track_bodies.  A frame holds at most 64 points (K_max <= 64)."""
+        blobs, counts, F, M, K_max = self._track_blobs(blobs, counts, K_max)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        B_max = self.rigid_bodies_n if B_max is None else int(B_max)
+        o = self._track_outputs(F, K_max, O_max)
+        o.update(self._body_outputs(F, B_max))
+        o.update(self._tracked_outputs(F, B_max))
+        self._check(self.lib.mocap_track_frame_bodies_tracked(self._h, F, M, _p(blobs), _p(counts), float(gate_px), K_max, int(G_cap),
+                                                              *self._track_ptrs(o, O_max), B_max, *self._body_ptrs(o), _p(t),
+                                                              *self._tracked_ptrs(o)))
+        return o
+
+    def track_frame_bodies_tracked_dev(self, n_frames, M_max, d_blobs, d_counts, gate_px, K_max, G_cap, d_xyz, d_err, d_corr, d_n_pts,
+                                       d_status, O_max, d_pos, d_heading, d_oerr, d_drone, d_n_obj, B_max, d_found, d_n_used,
+                                       d_assign, d_R, d_t, d_rms, d_score, d_rb_status, d_time, d_bt_tracked, d_bt_source,
+                                       d_bt_n_used, d_bt_assign, d_bt_R, d_bt_t, d_bt_rms, d_bt_hits, d_bt_missed, d_bt_status):
+        self._check(self.lib.mocap_track_frame_bodies_tracked_dev(
+            self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), float(gate_px), int(K_max), int(G_cap), _vp(d_xyz),
+            _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
+            _vp(d_drone or 0), _vp(d_n_obj or 0), int(B_max), _vp(d_found), _vp(d_n_used), _vp(d_assign), _vp(d_R), _vp(d_t),
+            _vp(d_rms), _vp(d_score), _vp(d_rb_status), _vp(d_time), _vp(d_bt_tracked), _vp(d_bt_source), _vp(d_bt_n_used),
+            _vp(d_bt_assign), _vp(d_bt_R), _vp(d_bt_t), _vp(d_bt_rms), _vp(d_bt_hits), _vp(d_bt_missed), _vp(d_bt_status)))
 
     # ------------------------------------------------------------------ point consolidation (each blob supports one point)
     def set_point_consolidation(self, mode):

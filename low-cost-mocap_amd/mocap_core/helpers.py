@@ -50,6 +50,7 @@ _state = {
     "centroid": capi.CENTROID_REFERENCE,   # capi.CENTROID_* of set_centroid_mode: integer centroids by default
     "bodies": None,          # set_rigid_bodies: (names, marker arrays, tol, max_rms, work_cap), None = no body registered
     "markers": None,         # set_marker_tracker: (gate, max_missed, vel_alpha, T_max), None = tracker off
+    "body_tracker": None,    # set_body_tracker: (gate, max_missed, vel_alpha), None = tracker off
     "consolidate": capi.CONSOLIDATE_OFF,   # capi.CONSOLIDATE_* of set_point_consolidation: the reference's points by default
 }
 
@@ -528,6 +529,78 @@ def track_frame_bodies(image_points, camera_poses, is_locating_objects=True, O_m
         return np.array([]), np.array([]), [], []
     return (res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else []),
             _bodies_list(res))
+
+
+def set_body_tracker(gate=0.03, max_missed=10, vel_alpha=0.5, on=True):
+    """Switches the body tracker on (mocap_set_body_tracker, include/mocap_core.h) and clears its slots: from now on
+    track_bodies() / track_frame_bodies_tracked() follow every registered body from frame to frame -- a symmetric body keeps its
+    labelling, a body with fewer than three visible markers coasts for up to max_missed frames, identical bodies keep their
+    points.  gate = how far (in the unit of the object points) a marker may be from where the predicted pose puts it; vel_alpha
+    in [0, 1] = weight of the newest velocity; on=False switches the tracker off.  Settings the core refuses raise
+    capi.MocapError and change nothing."""
+    with _state["lock"]:
+        get_core().set_body_tracker(gate=gate, max_missed=max_missed, vel_alpha=vel_alpha, on=on)
+        _state["body_tracker"] = (float(gate), int(max_missed), float(vel_alpha)) if on else None
+
+
+def _tracked_core():
+    """Registration and tracker live in the context: a core handed over by set_core gets both on first use (callers hold the lock)."""
+    core = _bodies_core()
+    reg = _state["body_tracker"]
+    if reg is not None and getattr(core, "body_tracker", None) != reg:
+        core.set_body_tracker(gate=reg[0], max_missed=reg[1], vel_alpha=reg[2])
+    return core
+
+
+_BT_SOURCE = {capi.BT_SRC_GUIDED: "guided", capi.BT_SRC_SEARCH: "search", capi.BT_SRC_COAST: "coast"}
+
+
+def _tracked_list(res, f=0):
+    """One frame's tracked bodies: {"name", "R" 3x3, "t" [3], "rms", "markers": point index per marker, -1 = not seen, "source":
+    "guided" | "search" | "coast", "hits", "missed"}; a coasting body carries its predicted pose and no markers."""
+    reg = _state["bodies"]
+    if reg is None:
+        return []
+    return [{"name": reg[0][b], "R": res["bt_R"][f, b].copy(), "t": res["bt_t"][f, b].copy(), "rms": float(res["bt_rms"][f, b]),
+             "markers": res["bt_assign"][f, b, :reg[1][b].shape[0]].astype(int).tolist(),
+             "source": _BT_SOURCE[int(res["source"][f, b])], "hits": int(res["bt_hits"][f, b]), "missed": int(res["bt_missed"][f, b])}
+            for b in range(len(reg[0])) if res["tracked"][f, b]]
+
+
+def track_bodies(object_points, now=None):
+    """The registered bodies among one frame's object points (at most 64), followed over time: list of {"name", "R", "t", "rms",
+    "markers", "source", "hits", "missed"}, world = R body + t, bodies without a pose left out.  Frames are handed over in time
+    order; `now` defaults to time.time().  Needs set_rigid_bodies() and set_body_tracker()."""
+    now = time.time() if now is None else float(now)
+    P = np.asarray(object_points, dtype=np.float64).reshape(-1, 3)
+    n = P.shape[0]
+    with _state["lock"]:
+        res = _tracked_core().track_bodies([now], P[None] if n else np.zeros((1, 1, 3)), [n])
+    return _tracked_list(res)
+
+
+def track_frame_bodies_tracked(image_points, camera_poses, now=None, is_locating_objects=True, O_max=8):
+    """track_frame_bodies with the body tracker in the same core call.  Returns (errors, object_points, objects, bodies):
+    track_frame's three values and the list track_bodies returns for the frame's object points; hand `bodies` to
+    object_points_payload(..., bodies=bodies).  `now` defaults to time.time()."""
+    now = time.time() if now is None else float(now)
+    for image_points_i in image_points:
+        try:
+            image_points_i.remove([None, None])
+        except Exception:
+            pass
+    with _state["lock"]:
+        core = _upload_cameras(camera_poses)
+        _tracked_core()
+        blobs, counts, _ = pack_frame(image_points)
+        res = core.track_frame_bodies_tracked(blobs, counts, [now], gate_px=5.0, O_max=O_max if is_locating_objects else 0)
+    if int(res["status"][0]) != 0:
+        raise capi.MocapError(_status_message(int(res["status"][0])))
+    k = int(res["n_pts"][0])
+    if k == 0:   # (a body may coast through a frame without points)
+        return np.array([]), np.array([]), [], _tracked_list(res)
+    return (res["err"][0, :k].copy(), res["xyz"][0, :k].copy(), (_objects_list(res) if is_locating_objects else []),
+            _tracked_list(res))
 
 
 def set_marker_tracker(gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):
