@@ -772,6 +772,85 @@ int mocap_consolidate_points(mocap_ctx* ctx, int64_t n_frames, int K_max, double
 int mocap_consolidate_points_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, double* d_xyz, double* d_err, int16_t* d_corr,
                                  int32_t* d_n_pts, const int32_t* d_status, int32_t* d_src, int32_t* d_n_in);
 
+/* ---------------------------------------------------------------- point refinement (the core's own contract)
+ * Least-squares points with each camera's own K.  Every point of the sections above is the reference's DLT point: the null vector
+ * of an algebraic system, built -- for rigs with one intrinsic matrix per camera -- with the intrinsics taken by compacted index
+ * (helpers.py:296-307), so a group that skips a camera is triangulated, and scored, with the wrong K for every later view.  This
+ * stage re-triangulates each kept group by minimising the true reprojection error: a fixed number of Levenberg-Marquardt steps in
+ * double on the device, from the DLT point.  Opt-in and the core's own: with the mode off every entry point writes the bytes it
+ * wrote before, and the mocap_match_triangulate* family never refines.
+ *
+ * Per point, the views are the cameras c, ascending, that see it: corr[c] >= 0 in the frame-path forms, an observation without a
+ * NaN in the observation forms.  Observations (u_c, v_c) are doubles (the float32 blobs widened exactly); v = number of views.
+ *   camera table   P_c = K_c [R_c | t_c] with the camera's OWN K_c (any 3 x 3 matrix, skew included), built on the host once per
+ *                  mocap_set_cameras:  P[i][j] = K[i][0] RT[0][j] + K[i][1] RT[1][j] + K[i][2] RT[2][j], RT = [R | t], left to right.
+ *   start          the DLT point mocap_triangulate gives for the same observations (compacted-index quirk included), in camera-0
+ *                  coordinates, recomputed with the device functions of that call.  xyz is WRITTEN, NEVER READ: the stage is
+ *                  indifferent to whether a world transform is set.
+ *   evaluation     at X = (X, Y, Z), per view:  a = P00 X + P01 Y + P02 Z + P03, b and w likewise from rows 1 and 2, each summed
+ *                  left to right.  VALID iff every w is finite and > 0.  pu = a / w, pv = b / w, ru = pu - u_c, rv = pv - v_c;
+ *                  cost = 0, then per view cost = cost + ru ru, cost = cost + rv rv.
+ *   normal eq.     per view  Ju[k] = (P0k - pu P2k) / w,  Jv[k] = (P1k - pv P2k) / w,  k < 3.  The six entries of H (00 01 02 11 12 22)
+ *                  and the three of g start at 0 and take, per view,  H_ij = H_ij + Ju[i] Ju[j],  H_ij = H_ij + Jv[i] Jv[j],  then
+ *                  g_k = g_k + Ju[k] ru,  g_k = g_k + Jv[k] rv.
+ *   one step       d0 = H00 + lam H00, a11 = H11 + lam H11, a22 = H22 + lam H22 (the off-diagonal entries are H's);
+ *                  L D L^T without pivoting:  l10 = H01 / d0, l20 = H02 / d0, d1 = a11 - l10 H01, t21 = H12 - l20 H01, l21 = t21 / d1,
+ *                  d2 = (a22 - l20 H02) - l21 t21;   z0 = -g0, z1 = -g1 - l10 z0, z2 = (-g2 - l20 z0) - l21 z1;   y_i = z_i / d_i;
+ *                  e2 = y2, e1 = y1 - l21 e2, e0 = (y0 - l10 e1) - l20 e2;   trial = X + e per component.
+ *                  ACCEPTED iff d0, d1, d2 are finite and > 0, the evaluation at the trial is valid and cost_trial < cost (strict).
+ *                  Accepted: X = trial (cost, H, g those of the trial), lam = lam / 10.  Otherwise X stays, lam = lam * 10.
+ *   iteration      lam = 1e-3, then exactly `iters` steps, no early exit.
+ *   result         xyz = the last accepted X (the start when no step was accepted); err = cost / (2 v), px^2, plain double, no
+ *                  float32 rounding: the frame path's quantity with the right matrices.  In the frame-path forms the point leaves
+ *                  through the frame path's own store, so the world transform applies when one is set.
+ * All arithmetic is IEEE double, no fused operation, `/` IEEE division, in the order written.
+ *
+ * A point is left UNTOUCHED -- xyz and err byte for byte -- and says why in info, when
+ *   MOCAP_RF_FEW_VIEWS   it has fewer than 2 views;
+ *   MOCAP_RF_BAD_INDEX   a corr entry >= 0 is >= counts[f][c] or >= M_max (that blob is not read);
+ *   MOCAP_RF_BAD_OBS     an observation (of an entry with a good index) has a coordinate that is not finite;
+ *   MOCAP_RF_BAD_START   none of the above, and the start is not finite or its evaluation is not valid.
+ * The first three are found in one pass over the row and may come together.  In the observation forms xyz and err are outputs
+ * only: an untouched row is NaN there (fewer than 2 views: as in mocap_triangulate).
+ * A FRAME is left byte for byte when status[f] & (MOCAP_ST_ROOT_OVERFLOW | MOCAP_ST_CAND_OVERFLOW | MOCAP_ST_HIT_OVERFLOW) or when
+ * n_pts[f] lies outside 0 .. K_max (the consolidation's rule); slots >= n_pts[f] are never written.  corr, n_pts and status are
+ * never changed.
+ *   info [F][K_max] i32, may be NULL: 0 = the slot is beyond n_pts[f] or the frame was skipped; otherwise MOCAP_RF_REFINED with
+ *   the number of accepted steps in bits 8-15 (info >> MOCAP_RF_STEPS_SHIFT), or the reasons above.
+ *
+ * mocap_set_point_refinement: iters = 0 is off (the default), 1 .. MOCAP_REFINE_MAX_ITERS is on; anything else is MOCAP_E_ARG and
+ * nothing changes.  Four steps reach the converged optimum to 2e-8 relative on this project's rigs.  The mode is honoured by every
+ * mocap_track_frame* entry point (host, images, _jpeg, and the _dev forms of plain, filtered, bodies, ids and bodies_tracked): one
+ * more kernel behind the re-submit and BEFORE the consolidation, so the consolidation's key, the object search and the export, the
+ * rigid bodies, the trackers, the object filter and the epipolar-line overlay all see refined points and refined errors.  With the
+ * mode on a _dev call with d_corr == NULL is MOCAP_E_ARG.
+ *
+ * mocap_refine_points_dev / mocap_refine_points: the staged call on arrays as the frame path writes them (blobs, counts in;
+ * mocap_match_triangulate's xyz, err in and out; corr, n_out, status in), whatever the mode; iters 1 .. 16, any K_max >= 1;
+ * MOCAP_E_NOCAMS without cameras.  mocap_triangulate_refined / _dev: the same refinement for explicit correspondences, obs
+ * [N][C][2] with NaN for unseen as mocap_triangulate takes them; xyz [N][3], err [N] (may be NULL), info [N] (may be NULL); the
+ * world transform does not apply, as in mocap_triangulate.  One lane per point; the "_dev" forms enqueue on the context's stream.
+ * Out of scope: a robust cost, lens distortion in the model, changing which group wins a root (the search selects by the
+ * reference's err), re-triangulating from the union of consolidated twins' blobs. */
+#define MOCAP_REFINE_MAX_ITERS 16
+enum {
+  MOCAP_RF_REFINED = 1,     /* the point was refined: xyz and err are the stage's */
+  MOCAP_RF_FEW_VIEWS = 2,   /* untouched: fewer than 2 views */
+  MOCAP_RF_BAD_INDEX = 4,   /* untouched: a corr entry beyond counts[f][c] or M_max */
+  MOCAP_RF_BAD_OBS = 8,     /* untouched: an observation that is not finite */
+  MOCAP_RF_BAD_START = 16   /* untouched: the DLT start is not finite or lies behind a camera */
+};
+#define MOCAP_RF_STEPS_SHIFT 8
+int mocap_set_point_refinement(mocap_ctx* ctx, int iters);
+int mocap_refine_points(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* blobs, const int32_t* counts, int K_max, int iters,
+                        double* xyz, double* err, const int16_t* corr, const int32_t* n_pts, const int32_t* status, int32_t* info);
+int mocap_refine_points_dev(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs, const int32_t* d_counts, int K_max,
+                            int iters, double* d_xyz, double* d_err, const int16_t* d_corr, const int32_t* d_n_pts,
+                            const int32_t* d_status, int32_t* d_info);
+int mocap_triangulate_refined(mocap_ctx* ctx, int64_t N, const double* obs, int iters, double* xyz, double* err, int32_t* info);
+int mocap_triangulate_refined_dev(mocap_ctx* ctx, int64_t N, const double* d_obs, int iters, double* d_xyz, double* d_err,
+                                  int32_t* d_info);
+
 /* ---------------------------------------------------------------- object filter
  * `filtered_objects` of the live loop (helpers.py:109, self.kalman_filter.predict_location(objects)): per drone index a
  * cv.KalmanFilter(9, 6) in float32 (constant acceleration, measurement = position and finite-difference velocity, nearest

@@ -280,10 +280,10 @@ extern "C" int mocap_set_cameras(mocap_ctx* ctx, int C, const double* K, const d
   ctx->ht.assign(t, t + 3 * C);
   bool uniform = true;
   for (int i = 1; i < C && uniform; i++) uniform = memcmp(K, K + 9 * i, 72) == 0;
-  // layout of the device table block (doubles): Pq | RT | K4 | F | K9
+  // layout of the device table block (doubles): Pq | RT | K4 | F | K9 | P
   const size_t nPq = uniform ? (size_t)12 * C : (size_t)12 * C * C;
   const size_t nRT = (size_t)12 * C, nK4 = (size_t)4 * C, nF = (size_t)9 * C * C, nK9 = (size_t)9 * C;
-  std::vector<double> h(nPq + nRT + nK4 + nF + nK9, 0.0);
+  std::vector<double> h(nPq + nRT + nK4 + nF + nK9 + nRT, 0.0);
   double* Pq = h.data();
   double* RT = Pq + nPq;
   double* K4 = RT + nRT;
@@ -310,6 +310,7 @@ extern "C" int mocap_set_cameras(mocap_ctx* ctx, int C, const double* K, const d
     for (int b = 0; b < C; b++)
       if (a != b) fundamental(Ptrue.data() + 12 * a, Ptrue.data() + 12 * b, F + 9 * ((size_t)a * C + b));
   memcpy(K9, K, sizeof(double) * 9 * C);
+  memcpy(K9 + nK9, Ptrue.data(), sizeof(double) * 12 * C);  // each camera's own K: the table of the point refinement
   ctx->hF.assign(F, F + nF);
 
   // a frame call may be in flight on another stream of the same context: the mutex serialises
@@ -328,6 +329,7 @@ extern "C" int mocap_set_cameras(mocap_ctx* ctx, int C, const double* K, const d
   ctx->cv.K4 = ctx->cv.RT + nRT;
   ctx->cv.F = ctx->cv.K4 + nK4;
   ctx->d_K9 = ctx->cv.F + nF;
+  ctx->d_Pown = ctx->d_K9 + nK9;
   // EigCut (mocap_device.hpp): the bound equates the DLT rows' residual with cv.projectPoints', which holds when every
   // K is [[fx,0,cx],[0,fy,cy],[0,0,1]] (projectPoints reads fx, fy, cx, cy only); then P[2] = (R[2], t[2])
   bool plainK = true;

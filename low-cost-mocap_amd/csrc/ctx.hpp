@@ -85,6 +85,7 @@ struct mocap_ctx {
   std::vector<double> hK, hR, ht, hF;  // host copies (intrinsics are reused by bundle adjustment)
   DevBuf tables;            // Pq | RT | K4 | F | K9
   const double* d_K9 = nullptr;
+  const double* d_Pown = nullptr;  // [C][12]: K_c [R_c|t_c], each camera's own K (point refinement)
   mocap::CamView cv{};
   // bundle adjustment: pinned host staging (async copies that really are async) and the event the
   // LM loop spin-waits on (hipStreamSynchronize may sleep on an interrupt: +50..400 us per wait)
@@ -130,6 +131,7 @@ struct mocap_ctx {
   double mt_g2 = 0.0, mt_alpha = 0.0;
   DevBuf mt_state;          // MarkerTrackState: the track slots and next_id
   int consolidate = 0;      // MOCAP_CONSOLIDATE_* (mocap_set_point_consolidation): the live loop's points compacted to one per blob, off by default
+  int refine_iters = 0;     // mocap_set_point_refinement: Levenberg-Marquardt steps on the live loop's points, 0 = off (the default)
   DevBuf calib_ws;          // calibration tail: one partial per workgroup (pair sums | floor factors), csrc/calib_tail.hip
   // preview-stream JPEG encoder (csrc/jpeg_capi.hip): header and divisors of the last (H, T * W, quality), workspace of a chunk
   int jpeg_key[3] = {0, 0, 0};
@@ -198,6 +200,11 @@ int tracked_clear_locked(mocap_ctx* ctx);  // all slots cleared, on the stream; 
 int consolidate_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int K_max);
 int consolidate_dev_locked(mocap_ctx* ctx, int64_t n_frames, int K_max, double* d_xyz, double* d_err, int16_t* d_corr, int32_t* d_n_pts,
                            const int32_t* d_status, int32_t* d_src, int32_t* d_n_in);
+// point refinement (point_refine_capi.hip): the stage of the live loop between the re-submit and the consolidation
+int refine_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int M_max, int K_max, int iters);
+int refine_dev_locked(mocap_ctx* ctx, int64_t n_frames, int M_max, const float* d_blobs, const int32_t* d_counts, int K_max, int iters,
+                      double* d_xyz, double* d_err, const int16_t* d_corr, const int32_t* d_n_pts, const int32_t* d_status,
+                      int32_t* d_info);
 
 // copier for copy_fields (io_fields.hpp) on the context's stream
 struct StreamCopy {

@@ -755,6 +755,28 @@ struct TrackStages {
   TrackStages(const BodiesIO& rb, const TrackedIO& io) : bodies(&rb), tracked(&io) {}
 };
 
+// The opt-in stages on the points themselves, between the re-submit and everything that reads the points, in their order:
+// refinement (mocap_set_point_refinement), then consolidation (mocap_set_point_consolidation) -- the consolidation's key, the
+// export, the object search and every stage behind see the refined points and errors.  Described here once for the host and the
+// device forms; with both modes off nothing is checked and nothing is queued.  `have_corr`: a _dev form got a d_corr.
+int point_stages_check(mocap_ctx* ctx, const char* who, const FrameBatch& b, int K_max, bool have_corr) {
+  int rc = MOCAP_OK;
+  if (ctx->refine_iters) rc = refine_check(ctx, who, b.n_frames, b.M_max, K_max, ctx->refine_iters);
+  if (!rc && ctx->refine_iters && b.n_frames > 0 && !have_corr) rc = ctx->fail(MOCAP_E_ARG, "%s: point refinement is on and needs d_corr", who);
+  if (!rc && ctx->consolidate) rc = consolidate_check(ctx, who, b.n_frames, K_max);
+  if (!rc && ctx->consolidate && b.n_frames > 0 && !have_corr) rc = ctx->fail(MOCAP_E_ARG, "%s: point consolidation is on and needs d_corr", who);
+  return rc;
+}
+// (`in`: the blobs and counts the frame pass read, device-visible; `d`: its outputs)
+int point_stages_dev_locked(mocap_ctx* ctx, const FrameBatch& in, int K_max, const FrameOut& d) {
+  int rc = MOCAP_OK;
+  if (in.n_frames <= 0) return rc;
+  if (ctx->refine_iters)
+    rc = refine_dev_locked(ctx, in.n_frames, in.M_max, in.blobs, in.counts, K_max, ctx->refine_iters, d.xyz, d.err, d.corr, d.n_out, d.status, nullptr);
+  if (!rc && ctx->consolidate) rc = consolidate_dev_locked(ctx, in.n_frames, K_max, d.xyz, d.err, d.corr, d.n_out, d.status, nullptr, nullptr);
+  return rc;
+}
+
 // images != null: raw frames [F][C][rows][cols][3] (host); else b.blobs / b.counts (host) are the input.  The filter, the
 // bodies, the markers and the tracked bodies are described once (io_fields.hpp): their arrays are carved from the same pinned block as the frame's
 // outputs, their kernels are queued behind the export and write into that block, their outputs are copied to the caller -- the
@@ -785,7 +807,7 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
   if (!rc && stages.tracked) rc = markers_times_check(ctx, who_bodies, n_frames, stages.tracked->t);
   if (!rc && stages.markers) rc = markers_check(ctx, "mocap_track_frame_ids", n_frames, K_max, *stages.markers);
   if (!rc && stages.markers) rc = markers_times_check(ctx, "mocap_track_frame_ids", n_frames, stages.markers->t);
-  if (!rc && ctx->consolidate) rc = consolidate_check(ctx, "mocap_track_frame", n_frames, K_max);
+  if (!rc) rc = point_stages_check(ctx, "mocap_track_frame", b, K_max, true);  // (the device block always has the rows)
   if (rc) return rc;
   if (jo) {  // the preview stream: the processed frames of the blob stage as one JPEG per frame set
     const char* bad = jpeg::check_args(n_frames, ctx->img_C, ctx->img_S, ctx->img_S, jo->quality, jo->capacity);
@@ -943,8 +965,8 @@ int track_locked(mocap_ctx* ctx, const uint8_t* images, const FrameBatch& b, int
     // the reference has none (helpers.py:394-400) -- before the export; queued behind the first pass, no host round trip
     rc = resubmit_dev_locked(ctx, in, K_max, d, nullptr);
     if (rc) return rc;
-    // opt-in (mocap_set_point_consolidation): the export and every stage behind it see the consolidated points
-    if (ctx->consolidate) rc = consolidate_dev_locked(ctx, n_frames, K_max, d.xyz, d.err, d.corr, d.n_out, d.status, nullptr, nullptr);
+    // opt-in (point_stages_dev_locked): the export and every stage behind it see the refined, consolidated points
+    rc = point_stages_dev_locked(ctx, in, K_max, d);
     if (rc) return rc;
     HIP_TRY(ctx, launch_track_export(la, ea, ctx->stream));
     // the stages read the frame's points where the frame path left them (device memory), the filter the export's objects in
@@ -1009,14 +1031,12 @@ int track_dev_locked(mocap_ctx* ctx, const char* who, const FrameBatch& b, int K
   if (!rc && stages.tracked) rc = tracked_check(ctx, who, b.n_frames, K_max, stages.bodies->B_max, *stages.tracked);
   if (!rc && stages.bodies) rc = bodies_check(ctx, who, b.n_frames, K_max, *stages.bodies);
   if (!rc && stages.markers) rc = markers_check(ctx, who, b.n_frames, K_max, *stages.markers);
-  if (!rc && ctx->consolidate) rc = consolidate_check(ctx, who, b.n_frames, K_max);
-  if (!rc && ctx->consolidate && b.n_frames > 0 && !o.pts.corr) rc = ctx->fail(MOCAP_E_ARG, "%s: point consolidation is on and needs d_corr", who);
+  if (!rc) rc = point_stages_check(ctx, who, b, K_max, o.pts.corr != nullptr);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   rc = match_dev_locked(ctx, b, K_max, G_cap, o.pts);
   if (!rc) rc = resubmit_dev_locked(ctx, b, K_max, o.pts, nullptr);
-  if (!rc && ctx->consolidate && b.n_frames > 0)
-    rc = consolidate_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.err, o.pts.corr, o.pts.n_out, o.pts.status, nullptr, nullptr);
+  if (!rc) rc = point_stages_dev_locked(ctx, b, K_max, o.pts);
   if (!rc && (stages.filter || o.O_max > 0))
     rc = locate_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.err, o.pts.n_out, o.O_max, o.pos, o.heading, o.oerr, o.drone, nullptr, o.n_obj);
   if (!rc && stages.bodies) rc = bodies_dev_locked(ctx, b.n_frames, K_max, o.pts.xyz, o.pts.n_out, *stages.bodies);

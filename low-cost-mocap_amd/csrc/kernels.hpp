@@ -344,6 +344,33 @@ __host__ __device__ inline size_t pc_lds_bytes(int C, int K_max) {
 }
 hipError_t launch_point_consolidate(const ConsolidateArgs& a, hipStream_t stream);
 
+// point refinement (the core's own contract, include/mocap_core.h "point refinement"), csrc/point_refine.hip: each kept group
+// re-triangulated by a fixed number of Levenberg-Marquardt steps on the true reprojection error (csrc/refine_lm.hpp), from the
+// DLT point of the same observations.  One lane per point slot, waves of their own workgroup (a live call has a few slots).
+constexpr int kRefineThreads = 64;
+struct RefineArgs {
+  CamView cv;                 // the DLT start reads Pq, by compacted index like every DLT of the core
+  const double* P;            // [C][12]: K_c [R_c|t_c], each camera's own K (mocap_set_cameras)
+  int iters;                  // 1 .. 16
+  // the frame-path form (obs == null): arrays as the frame path writes them
+  int64_t n_frames;
+  int M, K_max;
+  const float* blobs;         // [F][C][M][2]
+  const int32_t* counts;      // [F][C]
+  const int16_t* corr;        // [F][K_max][C]   never written
+  const int32_t* n_pts;       // [F]             never written
+  const int32_t* status;      // [F] or null (= 0)
+  const double* world;        // null, or the 4x4 to-world matrix of store_point
+  // the observation form (obs != null): N rows of [C][2], NaN = unseen
+  int64_t N;
+  const double* obs;
+  // both
+  double* xyz;                // [F][K_max][3] | [N][3]   written, never read
+  double* err;                // [F][K_max]    | [N]
+  int32_t* info;              // [F][K_max]    | [N], or null
+};
+hipError_t launch_point_refine(const RefineArgs& a, hipStream_t stream);
+
 // calibration tail over a capture's frame-path outputs (reference index.py:158-194, :290-309), csrc/calib_tail.hip
 constexpr int kCalibThreads = 256;      // frames per workgroup: the grid is ceil(F / 256), a function of F alone
 constexpr int kPairSlabDoubles = 3;     // per workgroup: sum of pair distances, pairs, frames skipped

@@ -49,6 +49,9 @@ BT_ST_BAD_TIME = 1        # per frame: the time stamp is not finite: no output, 
 CONSOLIDATE_OFF = 0       # mocap_set_point_consolidation: the frame path's points as the reference's algorithm gives them, the default
 CONSOLIDATE_BLOBS = 1     # ... compacted so that no two points of a frame share a blob (include/mocap_core.h)
 PC_MAX_POINTS = 256       # ... point slots per frame the consolidation takes
+REFINE_MAX_ITERS = 16     # mocap_set_point_refinement: Levenberg-Marquardt steps at most (0 = off, the default)
+RF_REFINED, RF_FEW_VIEWS, RF_BAD_INDEX, RF_BAD_OBS, RF_BAD_START = 1, 2, 4, 8, 16   # ... a point's info word: refined, or why not
+RF_STEPS_SHIFT = 8        # ... and the accepted steps, info >> 8
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
@@ -111,6 +114,11 @@ SIGNATURES = {
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_set_point_refinement": (_i32, [_vp, _i32]),
+    "mocap_refine_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_refine_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_triangulate_refined": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "mocap_triangulate_refined_dev": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     "mocap_set_object_filter": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _dbl, _dbl]),
     "mocap_reset_object_filter": (_i32, [_vp, _dbl]),
     "mocap_filter_objects": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -236,6 +244,7 @@ class MocapCore:
         self.marker_tracker = None   # (gate, max_missed, vel_alpha, T_max) of set_marker_tracker, None = off
         self.body_tracker = None     # (gate, max_missed, vel_alpha) of set_body_tracker, None = off
         self.point_consolidation = CONSOLIDATE_OFF   # CONSOLIDATE_* (set_point_consolidation), the library's default
+        self.point_refinement = 0    # Levenberg-Marquardt steps of set_point_refinement, 0 = off, the library's default
 
     def close(self):
         if getattr(self, "_h", None):
@@ -923,6 +932,54 @@ class MocapCore:
     def consolidate_points_dev(self, n_frames, K_max, d_xyz, d_err, d_corr, d_n_pts, d_status=0, d_src=0, d_n_in=0):
         self._check(self.lib.mocap_consolidate_points_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_err), _vp(d_corr),
                                                           _vp(d_n_pts), _vp(d_status or 0), _vp(d_src or 0), _vp(d_n_in or 0)))
+
+    # ------------------------------------------------------------------ point refinement (least-squares points, each camera's own K)
+    def set_point_refinement(self, iters):
+        """mocap_set_point_refinement: 0 = off (default), 1 .. REFINE_MAX_ITERS = every track_frame* entry point re-triangulates
+        each kept group by that many Levenberg-Marquardt steps on the true reprojection error, in front of the consolidation and
+        everything that reads the points.  A value the core refuses (MOCAP_E_ARG) raises and changes nothing."""
+        self._check(self.lib.mocap_set_point_refinement(self._h, int(iters)))
+        self.point_refinement = int(iters)
+
+    def refine_points(self, blobs, counts, xyz, err, corr, n_pts, status=None, iters=4):
+        """mocap_refine_points over host arrays as the frame path takes and writes them (blobs [F][C][M][2] f32, counts [F][C];
+        xyz [F][K_max][3], err [F][K_max], corr [F][K_max][C], n_pts [F], status [F] or None = 0).  The inputs are not touched;
+        returns {"xyz", "err"} with the refined points in place and "info" [F][K_max] (RF_* bits, accepted steps from bit 8)."""
+        blobs = np.ascontiguousarray(blobs, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        F, C, M, _ = blobs.shape
+        xyz = np.array(xyz, dtype=np.float64, order="C")
+        K_max = xyz.shape[1]
+        assert xyz.shape == (F, K_max, 3) and counts.shape == (F, C)
+        err = np.array(err, dtype=np.float64, order="C").reshape(F, K_max)
+        corr = np.ascontiguousarray(corr, dtype=np.int16)
+        assert corr.shape == (F, K_max, C) and (C == self.C or not self.C)
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(F)
+        info = np.full((F, K_max), -1, dtype=np.int32)
+        self._check(self.lib.mocap_refine_points(self._h, F, M, _p(blobs), _p(counts), K_max, int(iters), _p(xyz), _p(err), _p(corr),
+                                                 _p(n_pts), _p(status), _p(info)))
+        return {"xyz": xyz, "err": err, "info": info}
+
+    def refine_points_dev(self, n_frames, M_max, d_blobs, d_counts, K_max, iters, d_xyz, d_err, d_corr, d_n_pts, d_status=0, d_info=0):
+        self._check(self.lib.mocap_refine_points_dev(self._h, int(n_frames), int(M_max), _vp(d_blobs), _vp(d_counts), int(K_max),
+                                                     int(iters), _vp(d_xyz), _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status or 0),
+                                                     _vp(d_info or 0)))
+
+    def triangulate_refined(self, obs, iters=4):
+        """mocap_triangulate_refined: obs [N][C][2] (NaN = unseen) -> (xyz [N][3], err [N], info [N]); rows the stage does not
+        refine (fewer than 2 views, an infinite observation, a start behind a camera) are NaN and say why in info."""
+        obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, self.C, 2)
+        N = obs.shape[0]
+        xyz = np.empty((N, 3))
+        err = np.empty(N)
+        info = np.full(N, -1, dtype=np.int32)
+        self._check(self.lib.mocap_triangulate_refined(self._h, N, _p(obs), int(iters), _p(xyz), _p(err), _p(info)))
+        return xyz, err, info
+
+    def triangulate_refined_dev(self, N, d_obs, iters, d_xyz, d_err=0, d_info=0):
+        self._check(self.lib.mocap_triangulate_refined_dev(self._h, int(N), _vp(d_obs), int(iters), _vp(d_xyz), _vp(d_err or 0),
+                                                           _vp(d_info or 0)))
 
     # ------------------------------------------------------------------ object filter (`filtered_objects`)
     def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):

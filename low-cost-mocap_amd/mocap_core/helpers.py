@@ -52,6 +52,7 @@ _state = {
     "markers": None,         # set_marker_tracker: (gate, max_missed, vel_alpha, T_max), None = tracker off
     "body_tracker": None,    # set_body_tracker: (gate, max_missed, vel_alpha), None = tracker off
     "consolidate": capi.CONSOLIDATE_OFF,   # capi.CONSOLIDATE_* of set_point_consolidation: the reference's points by default
+    "refine": 0,             # set_point_refinement: Levenberg-Marquardt steps per object point, 0 = the reference's DLT points
 }
 
 
@@ -95,6 +96,21 @@ def set_point_consolidation(on):
         _state["consolidate"] = mode
         if _state["core"] is not None:
             _state["core"].set_point_consolidation(mode)
+
+
+def set_point_refinement(iters):
+    """Least-squares object points with each camera's own intrinsic matrix (mocap_set_point_refinement, include/mocap_core.h):
+    with iters in 1 .. capi.REFINE_MAX_ITERS, find_point_correspondance_and_object_points, track_frame*, camera_read_track and the
+    payload built from them return each point moved from the reference's DLT point to the minimum of its reprojection error by
+    that many Levenberg-Marquardt steps (4 reach the optimum), and its error taken there.  0 (default) = the reference's points.
+    Remembered, and applied to a core handed over later."""
+    iters = int(iters)
+    if not 0 <= iters <= capi.REFINE_MAX_ITERS:
+        raise ValueError(f"point refinement takes 0 .. {capi.REFINE_MAX_ITERS} iterations, not {iters}")
+    with _state["lock"]:
+        _state["refine"] = iters
+        if _state["core"] is not None:
+            _state["core"].set_point_refinement(iters)
 
 
 def _apply_overlay(core):
@@ -201,6 +217,8 @@ def _upload_cameras(camera_poses):
         _state["cam_key"] = key
     if getattr(core, "point_consolidation", capi.CONSOLIDATE_OFF) != _state["consolidate"]:   # a core handed over by set_core
         core.set_point_consolidation(_state["consolidate"])
+    if getattr(core, "point_refinement", 0) != _state["refine"]:
+        core.set_point_refinement(_state["refine"])
     return core
 
 
@@ -225,6 +243,26 @@ def triangulate_points(image_points, camera_poses):
         if obs.shape[0] == 0:
             return np.array([])
         xyz, _ = core.triangulate(obs)
+    missing = np.isnan(xyz[:, 0])
+    if not missing.any():
+        return xyz
+    out = xyz.astype(object)
+    out[missing] = None
+    return out
+
+
+def triangulate_points_refined(image_points, camera_poses, iters=None):
+    """triangulate_points with the point refinement of include/mocap_core.h behind it (mocap_triangulate_refined): each row's DLT
+    point moved to the minimum of its reprojection error, every camera with its own intrinsic matrix.  iters: None = the count of
+    set_point_refinement, or 4 when that is off.  Rows the stage does not refine -- fewer than two views, a start behind a
+    camera -- are [None, None, None]."""
+    C = len(camera_poses)
+    with _state["lock"]:
+        core = _upload_cameras(camera_poses)
+        obs = _obs_array(image_points, C)
+        if obs.shape[0] == 0:
+            return np.array([])
+        xyz, _, _ = core.triangulate_refined(obs, iters=(_state["refine"] or 4) if iters is None else int(iters))
     missing = np.isnan(xyz[:, 0])
     if not missing.any():
         return xyz
@@ -311,6 +349,9 @@ def find_point_correspondance_and_object_points(image_points, camera_poses, fram
         core = _upload_cameras(camera_poses)
         blobs, counts, _ = pack_frame(image_points)
         res = core.match_triangulate_auto(blobs, counts, gate_px=5.0)
+        if _state["refine"] and int(res["status"][0]) == 0:      # set_point_refinement: the staged call on the frame's own arrays
+            res.update({k: v for k, v in core.refine_points(blobs, counts, res["xyz"], res["err"], res["corr"], res["n_out"], res["status"],
+                                                           iters=_state["refine"]).items() if k != "info"})
         if _state["overlay"] & capi.OVERLAY_EPILINES and int(res["status"][0]) == 0:
             frames = _draw_epilines(core, frames, blobs, counts, res)
     if int(res["status"][0]) != 0:
