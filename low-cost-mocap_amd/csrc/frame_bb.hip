@@ -77,7 +77,9 @@ struct BBLayout {
       misc, bpl, nh, hits, act, root_blob, root_cam, nact, bnl, bv, pkbase, seen, bcache, total;
   int ncache;
   __host__ __device__ static size_t al(size_t x, size_t a) { return (x + a - 1) / a * a; }
-  __host__ __device__ BBLayout(int C, int M, int R, int CW, int wg_per_cu) {
+  // row_words (the layouts fixed at compile time, 8 cameras: BBState::ROWS): a root's rows of nh and act are eight bytes at a
+  // multiple of eight -- the search and phase C read a row as ONE word (the few bytes come out of the block cache)
+  __host__ __device__ BBLayout(int C, int M, int R, int CW, int wg_per_cu, bool row_words = false) {
     size_t o = 0;
     auto take = [&](size_t bytes, size_t a) {
       o = al(o, a);
@@ -111,9 +113,9 @@ struct BBLayout {
     misc = take(4 * 16, 4);
     bpl = take(2 * (size_t)R, 2);
     seen = take(2 * (size_t)R, 2);  // per root: the cameras it sees, one bit each (per-camera K: a view's position)
-    nh = take((size_t)R * C, 1);
+    nh = take((size_t)R * C, row_words ? 8 : 1);
     hits = take((size_t)R * C * M, 1);
-    act = take((size_t)R * C, 1);
+    act = take((size_t)R * C, row_words ? 8 : 1);
     root_blob = take((size_t)R, 1);
     root_cam = take((size_t)R, 1);
     nact = take((size_t)R, 1);
@@ -152,9 +154,9 @@ static int frame_bb_root_slots(int C, int M, int R) {
   const int f = bb_fixed_slots(C, M, R);
   return f ? f : R;
 }
-size_t frame_bb_lds_bytes(int C, int M, int R) { return BBLayout(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R))).total; }
+size_t frame_bb_lds_bytes(int C, int M, int R) { return BBLayout(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R)), bb_fixed_slots(C, M, R) != 0).total; }
 static size_t frame_bb_lds_bytes_min(int C, int M, int R) {
-  const BBLayout L(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R)));
+  const BBLayout L(C, M, frame_bb_root_slots(C, M, R), bb_cw(C), bb_wg_per_cu(bb_fixed_slots(C, M, R)), bb_fixed_slots(C, M, R) != 0);
   return L.total - kBBCacheEntry * (size_t)L.ncache;
 }
 bool frame_bb_fits(int C, int M, int R) {
@@ -247,6 +249,12 @@ struct BBState {
   static constexpr bool ROWS = bb_group_rows(CT, ML, RL);
   static constexpr uint32_t kNone = ROWS ? (uint32_t)(CT * ML) : 0xFFu;
   typedef Packed<CW, kNone> Pk;
+  // Round 14, the same layouts: a root's row of nh and of act is ONE 64-bit word (BBLayout: row_words) -- the search's decodes
+  // and phase C take a camera's hit count and a digit's camera from two registers by shift and mask instead of a chain of
+  // dependent byte reads; the pair loop keeps the closest hit while it walks the blobs and orders the rest only.
+  static_assert(!ROWS || (CT == 8 && CW == 1), "a row of nh / act as one word: eight cameras");
+  __device__ __forceinline__ unsigned long long row_word64(const uint8_t* rows, int r) const { return ((const unsigned long long*)rows)[r]; }
+  __device__ static __forceinline__ uint32_t byte_of(unsigned long long w, uint32_t k) { return (uint32_t)(w >> (8u * k)) & 0xFFu; }
   // The provisional roots listed once per frame (match(), behind stage 0's barrier): the fixed layouts whose blobs of a camera
   // fit the low half of a wave's lane mask (mbcnt_lo) and whose (camera, blob) numbers c ML + k fit a byte
   static constexpr bool PLIST = CT > 0 && ML > 0 && RL > 0 && ML < 32 && CT * ML <= 256 && (ML & (ML - 1)) == 0;
@@ -326,7 +334,7 @@ struct BBState {
       cv.base = (const double*)(uintptr_t)(((unsigned long long)thi << 32) | tlo);
       if constexpr (CT == 0) cv.C = C;
     }
-    const BBLayout L(C, M, RS, CW, bb_wg_per_cu(RL));
+    const BBLayout L(C, M, RS, CW, bb_wg_per_cu(RL), ROWS);
     bt = (double*)(smem + L.bt);
     bxy = (float2*)(smem + L.bxy);
     bxy_nx = (float2*)(smem + L.bxy_nx);
@@ -643,6 +651,23 @@ struct BBState {
             return div_by(fabs(L.a * (double)pt.x + L.b * (double)pt.y + L.c), L.den, L.rden);  // helpers.py:373
           };
           unsigned long long hm = 0ull;
+          // (ROWS: the closest hit falls out of the walk -- ascending index, strict <: ties keep the smaller index, pass 2's rule)
+          double bd0 = __builtin_huge_val();
+          int bk0 = 0;
+          if constexpr (ROWS) {
+#pragma unroll 4
+            for (int k = 0; k < Mmax; k++)
+              if (k < Mi) {
+                const double d = dist(k);
+                if (d < p.gate_px) {  // strict <, helpers.py:375,383
+                  hm |= 1ull << k;
+                  if (d < bd0) {
+                    bd0 = d;
+                    bk0 = k;
+                  }
+                }
+              }
+          } else
 #pragma unroll 4
           for (int k = 0; k < Mmax; k++)  // (independent iterations: unrolled, their latencies overlap -- the stage runs on one or two waves)
             if (k < Mi && dist(k) < p.gate_px) hm |= 1ull << k;  // strict <, helpers.py:375,383
@@ -654,10 +679,33 @@ struct BBState {
           unsigned long long rem = hm, claim = 0ull;
           int pos = 0;
           float2 p0 = make_float2(0.f, 0.f);
+          if constexpr (ROWS) {
+            // position 0 is the walk's minimum; a list of one claims itself (a hit's coordinates are finite: equal to themselves);
+            // below, the last hit left of any list is placed without a distance -- no distance is computed twice for lists of
+            // up to two, the usual ones
+            if (hm) {
+              hl[0] = (uint8_t)gbyte(i, (uint32_t)bk0);
+              claim = hm;
+              if (hm & (hm - 1ull)) {
+                claim = 0ull;
+                p0 = pts[bk0];
+                for (unsigned long long t = hm; t; t &= t - 1) {
+                  const int k = __ffsll((long long)t) - 1;
+                  const float2 q = pts[k];
+                  if (q.x == p0.x && q.y == p0.y) claim |= 1ull << k;
+                }
+              }
+              rem = hm & ~(1ull << bk0);
+              pos = 1;
+            }
+          }
           while (__ballot(rem != 0ull)) {
             if (rem) {
               double bd = __builtin_huge_val();
               int bk = 0;
+              if (ROWS && !(rem & (rem - 1ull))) {
+                bk = __ffsll((long long)rem) - 1;
+              } else
               for (unsigned long long t = rem; t; t &= t - 1) {  // ascending index, strict <: ties keep the smaller index
                 const int k = __ffsll((long long)t) - 1;
                 const double d = dist(k);
@@ -667,7 +715,7 @@ struct BBState {
                 }
               }
               hl[pos] = (uint8_t)gbyte(i, (uint32_t)bk);
-              if (pos == 0) {
+              if (!ROWS && pos == 0) {
                 p0 = pts[bk];
                 for (unsigned long long t = hm; t; t &= t - 1) {
                   const int k = __ffsll((long long)t) - 1;
@@ -897,6 +945,69 @@ struct BBState {
     fresh_tid();
     const int nroots = misc[MI_NROOTS];
     for (int r = tid; r < nroots; r += T) {
+      if constexpr (ROWS) {
+        // the same per root from registers: the nh row as one word, the first hit of every camera read unconditionally (independent
+        // reads; a single-hit camera's is used), the act row built in a register and stored once, the block size from the digits'
+        // counts kept beside it -- no load behind a store, no a[k] -> nh[...] chain
+        const uint32_t rc = root_cam[r], rb = root_blob[r];
+        unsigned long long nw = row_word64(nh, r);
+        const uint8_t* hr = hits + (size_t)r * (CT * ML);
+        uint32_t h1[CT];
+#pragma unroll
+        for (int c = 1; c < CT; c++) h1[c] = hr[c * ML];
+        // cameras at or below the root's own: nothing writes their bytes for this root (stage 0 writes cameras >= 1 of camera-0
+        // roots, the row copy c > root_cam) -- whatever an earlier frame's root left in the slot is masked out
+        nw &= (~0ull << (8u * rc)) << 8;
+        Pk pkb;
+        pkb.clear();
+        pkb.set((int)rc, gbyte((int)rc, rb));
+        // the digits, one byte each: camera | (hit count - 1) << 3 (c <= 7, counts <= ML = 16), pushed from the last camera down
+        // so that digit 0, the lowest multi-hit camera, ends up in the low byte -- shifts by a constant only
+        static_assert(CT <= 8 && ML <= 16, "a digit's byte: three bits of camera, four of hit count - 1");
+        unsigned long long ew = 0ull;
+        uint32_t total = 1, views = 1, na = 0, sm = 1u << rc;  // (total: seven counts <= 16 -> < 2^32)
+#pragma unroll
+        for (int c = CT - 1; c >= 1; c--) {
+          const uint32_t n = byte_of(nw, (uint32_t)c);
+          if (n > 1) {
+            ew = (ew << 8) | (unsigned long long)((n << 3) + (uint32_t)(c - 8));
+            na++;
+          }
+          if (n == 1) pkb.set(c, h1[c]);
+          if (n) {
+            sm |= 1u << c;
+            views++;
+            total *= n;
+          }
+        }
+        const unsigned long long aw = ew & 0x0707070707070707ull;                                   // the act row: the digits' cameras
+        const unsigned long long dn = ((ew >> 3) & 0x0F0F0F0F0F0F0F0Full) + 0x0101010101010101ull;  // the digits' hit counts (1 beyond na: not read)
+        // (the loop's rule: over as soon as a prefix product exceeds G_cap -- counts are >= 1, the products monotone: the full one decides)
+        const bool over = (unsigned long long)total > (unsigned long long)p.G_cap;
+        if (over) atomicOr(&misc[MI_STATUS], MOCAP_ST_CAND_OVERFLOW_);
+        ((unsigned long long*)act)[r] = aw;
+        nact[r] = (uint8_t)na;
+        bv[r] = (uint8_t)views;
+        pkbase[r] = pkb.w[0];
+        if (PERK) seen[r] = (uint16_t)sm;
+        rbound[r] = kInfBits;
+        const uint32_t g = (views > 1 && !over) ? total : 0u;
+        gcnt[r] = g;
+        uint32_t pl = 1, nb = over ? 1u : total;  // (the multi-hit counts' product = total: single hits contribute 1)
+        uint32_t nl = 0;
+        while (nl < na && (pl < (uint32_t)p.bb_pl_min || (pl < (uint32_t)p.bb_pl && nb > (uint32_t)p.bb_nb_max))) {
+          const uint32_t n = byte_of(dn, nl++);
+          uint32_t dummy;
+          pl *= n;
+          divmod_small(nb, n, nb, dummy);  // (exact: nb < 2^24 is a multiple of n)
+        }
+        bpl[r] = (uint16_t)pl;
+        bnl[r] = (uint8_t)nl;
+        bnb[r] = g ? nb : 0u;
+        seedkey[r] = 0ull;
+        seedgh[r] = 0xFFFFFFFFu;
+        continue;
+      }
       const int rc = root_cam[r];
       unsigned long long total = 1;
       int views = 1, na = 0;
@@ -1061,6 +1172,23 @@ struct BBState {
     const int C = cn();
 #pragma unroll
     for (int k = 0; k < CW; k++) pk.w[k] = pkbase[(size_t)r * CW + k];
+    if constexpr (ROWS) {
+      // the root's digits and hit counts as two words, read next to the sizes: a digit's camera and count are shifts, only its
+      // hits byte is a dependent read
+      const unsigned long long aw = row_word64(act, r), nw = row_word64(nh, r);
+      const int na = nact[r];
+      const uint8_t* hr = hits + (size_t)r * (CT * ML);
+      uint32_t rem = gh;
+      for (int k = bnl[r]; k < na; k++) {
+        const uint32_t c = byte_of(aw, (uint32_t)k), n = byte_of(nw, c);
+        uint32_t qd, dgt;
+        if (rem < 8192u) divmod_tiny(rem, n, qd, dgt); else
+        divmod_small(rem, n, qd, dgt);
+        rem = qd;
+        pk.set((int)c, hr[c * (uint32_t)ML + dgt]);
+      }
+      return;
+    }
     const uint8_t* a = act + (size_t)r * C;
     const int na = nact[r];
     uint32_t rem = gh;
@@ -1120,6 +1248,17 @@ struct BBState {
       gl = rec.gh * (uint32_t)bpl[r] + rem;
       const uint8_t* a = act + (size_t)r * C;
       const int nl = bnl[r];
+      if constexpr (ROWS) {
+        const unsigned long long aw = row_word64(act, r), nw = row_word64(nh, r);  // (independent of each other and of bpl / bnl)
+        const uint8_t* hr = hits + (size_t)r * (CT * ML);
+        for (int k = 0; k < nl; k++) {
+          const uint32_t c = byte_of(aw, (uint32_t)k);
+          uint32_t qd, dgt;
+          divmod_tiny(rem, byte_of(nw, c), qd, dgt);
+          rem = qd;
+          pk.set((int)c, hr[c * (uint32_t)ML + dgt]);
+        }
+      } else
       for (int k = 0; k < nl; k++) {  // the block's open digits (rem < pl < 2^13, hit counts <= 64: divmod_tiny is exact)
         const int c = a[k];
         uint32_t qd, dgt;
