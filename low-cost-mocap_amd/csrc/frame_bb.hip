@@ -229,6 +229,15 @@ __device__ __forceinline__ void bb_prio() {
   __builtin_amdgcn_s_setprio(P);
 }
 
+// A double rounded to float32 towards +inf (what __double2float_ru returns, for every input, in 7 instructions instead of 17): the
+// nearest float, and where that lies below the value its upper neighbour -- one step in the bit pattern, up for a float >= +0, down
+// for a negative one (-inf -> -FLT_MAX); a NaN or a value the nearest float does not lie below is kept.
+__device__ __forceinline__ float f32_round_up(double v) {
+  const float f = (float)v;
+  const int32_t b = __float_as_int(f);
+  return (double)f < v ? __int_as_float(b + ((b >> 31) | 1)) : f;
+}
+
 // ML, RL: the layout's blobs per camera and root slots when they are known at compile time (with CT: every LDS array
 // sits at a constant address, which takes the base registers, their spills to vector lanes and the address arithmetic
 // out of every phase -- 5.72 -> 5.39 ms per 100 k frames of 8 x 16), 0 = runtime.  ML is the frame's M_max itself (the
@@ -655,21 +664,92 @@ struct BBState {
           double bd0 = __builtin_huge_val();
           int bk0 = 0;
           if constexpr (ROWS) {
-#pragma unroll 4
-            for (int k = 0; k < Mmax; k++)
-              if (k < Mi) {
-                const double d = dist(k);
-                if (d < p.gate_px) {  // strict <, helpers.py:375,383
-                  hm |= 1ull << k;
-                  if (d < bd0) {
-                    bd0 = d;
-                    bk0 = k;
+            // Round 15: no wait, branch or exact distance per blob.  All ML slots of the camera are read as words of two blobs,
+            // whatever the count (slots at or beyond it hold the caller's bytes: the count mask below keeps them out of cand, hence
+            // out of hm, the minimum and the claim); with the float32 line the wide variant's pre-test (frame_kernel.hip
+            // match_pairs_wide; tests/test_wide_pretest_bound_cpu.py) drops the clear misses, and the exact expression decides
+            // what is left -- 1.6 blobs of 16 on the bench stream -- in ascending index, all lanes at once.  Without the float32
+            // roundings the line is a double: the exact expression for all sixteen slots, straight line (a loop over the slots
+            // under the count, one read and its wait per turn, measured 0.06 ms per 100 k frames SLOWER than the parent's walk).
+            static_assert(ML % 2 == 0 && ML < 32, "two blobs per word, the slots as bits of one register");
+            const float4* pw = (const float4*)pts;  // (bxy is 16-byte aligned, a camera's row is ML float2)
+            uint32_t cand = (1u << Mi) - 1u;
+            uint32_t hw = 0u;  // (the hits as one register: ML < 32)
+            if constexpr (F32R) {
+              // omax of the pre-test's bound: the largest coordinate any pair of the frame reads under its count (misc[MI_OMAX] is
+              // filled later, with the per-blob table).  The frame's C ML slots are one word of two blobs per lane; the coordinates
+              // compare as integers with the sign bit off (the order of the floats, NaN above +inf: a NaN under a count leaves the
+              // bound at +inf, everything goes to the exact test), the wave's maximum by four row steps and the four rows' lanes.
+              static_assert(CT * ML == 128, "the frame's slots: one word of two blobs per lane");
+              uint32_t ob;
+              {
+                const float4 v = ((const float4*)bxy)[lane];
+                const int n = cnt[lane / (ML / 2)], k0 = 2 * (lane % (ML / 2));
+                const uint32_t ax = __float_as_uint(v.x) & 0x7FFFFFFFu, ay = __float_as_uint(v.y) & 0x7FFFFFFFu;
+                const uint32_t az = __float_as_uint(v.z) & 0x7FFFFFFFu, aw = __float_as_uint(v.w) & 0x7FFFFFFFu;
+                const uint32_t m0 = k0 < n ? (ax > ay ? ax : ay) : 0u, m1 = k0 + 1 < n ? (az > aw ? az : aw) : 0u;
+                ob = m0 > m1 ? m0 : m1;
+                auto up = [](uint32_t x, uint32_t y) { return x > y ? x : y; };
+                ob = up(ob, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ob, 0xB1, 0xf, 0xf, true));   // quad_perm [1, 0, 3, 2]
+                ob = up(ob, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ob, 0x4E, 0xf, 0xf, true));   // quad_perm [2, 3, 0, 1]
+                ob = up(ob, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ob, 0x141, 0xf, 0xf, true));  // row_half_mirror
+                ob = up(ob, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ob, 0x140, 0xf, 0xf, true));  // row_mirror
+                const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)ob, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)ob, 16);
+                const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)ob, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)ob, 48);
+                ob = up(up(r0, r1), up(r2, r3));  // (wave-uniform: scalar from here)
+                ob = ob < 0x7F800000u ? ob : 0x7F800000u;
+              }
+              const double om = (double)__uint_as_float(ob);
+              const float a32 = (float)L.a, b32 = (float)L.b, c32 = (float)L.c;  // (exact: the line is float32)
+              const float thr = f32_round_up(p.gate_px * L.den * (1.0 + 1e-12) + (2.5 * 0x1p-24) * (2.0 * om + fabs(L.c)) * (1.0 + 1e-6));
+              // the camera's slots from the last to the first, a slot's verdict shifted in as the mask's lowest bit
+              // (<= is false for NaN: an infinite or NaN slot or line passes only where thr is +inf, and then to the exact test)
+              uint32_t pm = 0u;
+#pragma unroll
+              for (int h = ML / 2 - 1; h >= 0; h--) {
+                const float4 v = pw[h];
+                float t0 = fmaf(a32, v.x, fmaf(b32, v.y, c32)), t1 = fmaf(a32, v.z, fmaf(b32, v.w, c32));
+                asm("" : "+v"(t0), "+v"(t1));  // (one scalar multiply-add each: as packed pairs they cost a move per operand)
+                pm = pm + pm + (fabsf(t1) <= thr ? 1u : 0u);
+                pm = pm + pm + (fabsf(t0) <= thr ? 1u : 0u);
+              }
+              cand &= pm;
+              while (__ballot(cand != 0u)) {
+                if (cand) {
+                  const int k = __ffs((int)cand) - 1;
+                  cand &= cand - 1u;
+                  const double d = dist(k);
+                  if (d < p.gate_px) {  // strict <, helpers.py:375,383
+                    hw |= 1u << k;
+                    if (d < bd0) {
+                      bd0 = d;
+                      bk0 = k;
+                    }
                   }
                 }
               }
+            } else {
+#pragma unroll
+              for (int h = 0; h < ML / 2; h++) {
+                const float4 v = pw[h];
+                const double d0 = div_by(fabs(L.a * (double)v.x + L.b * (double)v.y + L.c), L.den, L.rden);  // helpers.py:373
+                const double d1 = div_by(fabs(L.a * (double)v.z + L.b * (double)v.w + L.c), L.den, L.rden);
+                // strict <, helpers.py:375,383; a slot at or beyond the count is no hit whatever it holds
+                const bool h0 = d0 < p.gate_px && ((cand >> (2 * h)) & 1u), h1 = d1 < p.gate_px && ((cand >> (2 * h + 1)) & 1u);
+                hw |= h0 ? 1u << (2 * h) : 0u;
+                const bool b0 = h0 && d0 < bd0;
+                bd0 = b0 ? d0 : bd0;
+                bk0 = b0 ? 2 * h : bk0;
+                hw |= h1 ? 2u << (2 * h) : 0u;
+                const bool b1 = h1 && d1 < bd0;
+                bd0 = b1 ? d1 : bd0;
+                bk0 = b1 ? 2 * h + 1 : bk0;
+              }
+            }
+            hm = hw;
           } else
 #pragma unroll 4
-          for (int k = 0; k < Mmax; k++)  // (independent iterations: unrolled, their latencies overlap -- the stage runs on one or two waves)
+          for (int k = 0; k < Mmax; k++)  // (unrolled by four; the emitted code runs the copies one after the other, each read waited for at once)
             if (k < Mi && dist(k) < p.gate_px) hm |= 1ull << k;  // strict <, helpers.py:375,383
           uint8_t* nhp = stage == 0 ? nh : nh_s;
           uint8_t* hl = (stage == 0 ? hits : hits_s) + ((size_t)r * C + i) * M;
