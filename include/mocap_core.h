@@ -720,6 +720,60 @@ int mocap_track_frame_bodies_tracked_dev(mocap_ctx* ctx, int64_t n_frames, int M
                                          int32_t* d_bt_n_used, int8_t* d_bt_assign, double* d_bt_R, double* d_bt_t,
                                          double* d_bt_rms, int32_t* d_bt_hits, int32_t* d_bt_missed, int32_t* d_bt_status);
 
+/* ---------------------------------------------------------------- rigid-body learning (the core's own contract)
+ * The marker coordinates mocap_set_rigid_bodies wants, learned from a capture of the body in motion: the constellation of the
+ * selected track ids averaged over the capture's frames, and how rigid it was.  Inputs as they lie after a session with the
+ * marker tracker on: xyz [F][K_max][3], n_pts [F] (the frame path's), id [F][K_max] (the tracker's), status [F] or NULL.  Not a
+ * stage of the live loop: with nothing called nothing changes.  All arithmetic is IEEE double, no fused operation.
+ *
+ * Arguments.  MOCAP_E_ARG, `result` untouched, for: n_frames < 1; K_max outside 1 .. 64; N outside 3 .. 8; a negative or repeated
+ * entry in sel [N] (a HOST pointer in both forms); iters outside 1 .. 16; max_rms not > 0 (+inf is allowed: no gate);
+ * ref_frame < -1 or >= n_frames; a null buffer (status may be NULL).
+ * Valid frame (the calibration tail's rule): status[f] == 0 when a status array is given, and 0 <= n_pts[f] <= K_max.  Slots
+ *   >= n_pts[f] are never read.
+ * Gather.  In a valid frame marker m is PRESENT at the lowest j < n_pts[f] with id[f][j] == sel[m] and three finite coordinates in
+ *   xyz[f][j]; no such j: absent.  In a frame that is not valid every marker is absent.
+ * Reference frame.  ref_frame, or with ref_frame = -1 the lowest valid frame in which all N markers are present.  No such frame,
+ *   or the given frame not valid and complete: `result` is zero but for [126] = -1 and [128] = MOCAP_LB_ST_NO_REF; the call returns 0.
+ *   Template Q^0_m = p_m - c over that frame's N points, c = (sum of the p_m in marker order) * (1.0 / N), per coordinate.
+ * Round r = 1 .. iters.  A frame with >= 3 present markers is POSED against Q^(r-1) on its present subset, with the arithmetic of the
+ *   rigid-body section's pose, operation for operation: count c; inv = 1.0 / c; centroids qb, pb = (sums in marker order) * inv;
+ *   S[i][j] = sum in marker order of (q - qb)_i (p - pb)_j; Horn's 4 x 4 matrix; cyclic Jacobi; the eigenvector of the largest
+ *   eigenvalue (the lowest index on a tie) divided by its norm ((w w + x x) + y y) + z z -> R; t_i = pb_i - ((R_i0 qb_0 + R_i1 qb_1) +
+ *   R_i2 qb_2); rms = sqrt(ss * inv), ss the sum in (marker, coordinate) order of the squares of ((R_i0 u_0 + R_i1 u_1) + R_i2 u_2) -
+ *   (p - pb)_i, u = q - qb.  The frame is USED in round r iff rms <= max_rms.
+ *   A used frame maps each present marker back: d = p_m - t, y_k = (R_0k d_0 + R_1k d_1) + R_2k d_2 (y = R^T d), and contributes
+ *   y (3 values), 1 to the marker's count, ((e_0 e_0 + e_1 e_1) + e_2 e_2), e = y - Q^(r-1)_m, to the marker's squared error; 1 to
+ *   the frames used and rms * rms to the rms sum.  These are reduced over all frames through the tree below.
+ *   Q^r_m = (sum y_m) / count_m per coordinate; a marker with count 0 keeps Q^(r-1)_m and sets MOCAP_LB_ST_MARKER_UNSEEN (the flag
+ *   stays set through the later rounds).  Then the centroid of all N markers, taken like c above, is subtracted.  The body frame
+ *   keeps the orientation the body had in the reference frame; there is no principal-axis step.
+ * Pair statistics (independent of the rounds).  For each pair i < j over the frames in which both are present: c_ij the count,
+ *   d_ij = (sum D) / c_ij with the rigid-body section's D, and in a second pass s_ij = sqrt((sum (D - d_ij)^2) / c_ij); both 0 when
+ *   c_ij = 0.  A marker that is not on the body shows as a large s_ij.
+ * One tree, a function of F alone (the calibration tail's): one lane per frame, 256 frames per workgroup, grid ceil(F / 256); lane
+ *   -> wave by shuffles (offsets 32 .. 1, v = v + other), wave -> workgroup through LDS in wave order, one partial per workgroup into
+ *   a slab; a final launch of one wave whose lane l folds the slab entries [l ceil(P / 64), ...) in index order from 0.0, then the
+ *   same shuffle tree.  No atomics.  The final launch of a round leaves Q^r in device memory for the next: the call is one chain of
+ *   4 + 2 iters launches on the context's stream, no host round trip inside it.
+ * result [MOCAP_LB_RESULT] doubles:
+ *   [0, 24)   markers [8][3], rows >= N zero            [24, 32)  per-marker rms of the last round, sqrt(sum |y - q|^2 / count)
+ *   [32, 40)  per-marker counts of the last round       [40, 68)  d_ij, (i, j) lexicographic over 8 markers, unused zero
+ *   [68, 96)  s_ij          [96, 124) c_ij              [124] frames used in the last round      [125] valid frames
+ *   [126] reference frame index      [127] rms of the last round, sqrt(sum rms^2 / used), 0 when none      [128] status flags
+ * The "_dev" form enqueues on the context's stream (d_result device-accessible); the host form uploads, runs and downloads. */
+#define MOCAP_LB_RESULT 129 /* doubles */
+enum {
+  MOCAP_LB_ST_NO_REF = 1,        /* no valid frame shows every selected marker (or the given ref_frame does not) */
+  MOCAP_LB_ST_MARKER_UNSEEN = 2  /* a marker had no used frame in some round and kept its previous position */
+};
+int mocap_learn_rigid_body(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int32_t* n_pts, const int32_t* id,
+                           const int32_t* status, int N, const int32_t* sel, int64_t ref_frame, int iters, double max_rms,
+                           double* result);
+int mocap_learn_rigid_body_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts,
+                               const int32_t* d_id, const int32_t* d_status, int N, const int32_t* sel, int64_t ref_frame,
+                               int iters, double max_rms, double* d_result);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

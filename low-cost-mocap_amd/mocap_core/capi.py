@@ -52,6 +52,9 @@ PC_MAX_POINTS = 256       # ... point slots per frame the consolidation takes
 REFINE_MAX_ITERS = 16     # mocap_set_point_refinement: Levenberg-Marquardt steps at most (0 = off, the default)
 RF_REFINED, RF_FEW_VIEWS, RF_BAD_INDEX, RF_BAD_OBS, RF_BAD_START = 1, 2, 4, 8, 16   # ... a point's info word: refined, or why not
 RF_STEPS_SHIFT = 8        # ... and the accepted steps, info >> 8
+LB_RESULT = 129           # mocap_learn_rigid_body: doubles of its `result`
+LB_ST_NO_REF = 1          # ... status flags: no valid frame shows every selected marker (or the given ref_frame does not)
+LB_ST_MARKER_UNSEEN = 2   # ... a marker had no used frame in some round and kept its previous position
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
@@ -111,6 +114,8 @@ SIGNATURES = {
     "mocap_track_frame_bodies_tracked_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                                     _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_learn_rigid_body": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _dbl, _vp]),
+    "mocap_learn_rigid_body_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _dbl, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -759,6 +764,47 @@ class MocapCore:
             _vp(d_err), _vp(d_corr), _vp(d_n_pts), _vp(d_status), int(O_max), _vp(d_pos or 0), _vp(d_heading or 0), _vp(d_oerr or 0),
             _vp(d_drone or 0), _vp(d_n_obj or 0), int(B_max), _vp(d_found), _vp(d_n_used), _vp(d_assign), _vp(d_R), _vp(d_t),
             _vp(d_rms), _vp(d_score), _vp(d_rb_status)))
+
+    # ------------------------------------------------------------------ rigid-body learning (a body's markers from a capture)
+    @staticmethod
+    def learned_body(result, N):
+        """The `result` doubles of mocap_learn_rigid_body -> the dict learn_rigid_body returns."""
+        r = np.asarray(result, dtype=np.float64).reshape(LB_RESULT)
+        N = int(N)
+        pair = {k: np.zeros((N, N)) for k in ("pair_mean", "pair_std", "pair_frames")}
+        p = 0
+        for i in range(RB_MAX_MARKERS):
+            for j in range(i + 1, RB_MAX_MARKERS):
+                if j < N:
+                    for k, base in (("pair_mean", 40), ("pair_std", 68), ("pair_frames", 96)):
+                        pair[k][i, j] = pair[k][j, i] = r[base + p]
+                p += 1
+        seen = pair["pair_mean"][np.triu_indices(N, 1)][pair["pair_frames"][np.triu_indices(N, 1)] > 0]
+        return {"markers": r[:24].reshape(RB_MAX_MARKERS, 3)[:N].copy(), "marker_rms": r[24:24 + N].copy(),
+                "marker_frames": r[32:32 + N].astype(np.int64), "pair_mean": pair["pair_mean"], "pair_std": pair["pair_std"],
+                "pair_frames": pair["pair_frames"].astype(np.int64), "frames_used": int(r[124]), "frames_valid": int(r[125]),
+                "ref_frame": int(r[126]), "rms": float(r[127]), "status": int(r[128]),
+                "min_pair_distance": float(seen.min()) if seen.size else 0.0}
+
+    def learn_rigid_body(self, xyz, n_pts, ids, sel, status=None, ref_frame=-1, iters=4, max_rms=float("inf")):
+        """mocap_learn_rigid_body over host arrays xyz [F][K_max][3] (K_max <= 64), n_pts [F], ids [F][K_max] (the marker tracker's),
+        status [F] or None; sel = the 3 .. 8 track ids of the body's markers -> {"markers" [N][3] body coordinates (what
+        set_rigid_bodies takes), "marker_rms", "marker_frames" [N], "pair_mean", "pair_std", "pair_frames" [N][N] symmetric,
+        "frames_used", "frames_valid", "ref_frame", "rms", "status" (LB_ST_* flags), "min_pair_distance"}."""
+        xyz, n_pts, status, F, K_max = self._capture(xyz, n_pts, status)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(F, K_max)
+        sel = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+        res = np.zeros(LB_RESULT)
+        self._check(self.lib.mocap_learn_rigid_body(self._h, F, K_max, _p(xyz), _p(n_pts), _p(ids), _p(status), sel.size, _p(sel),
+                                                    int(ref_frame), int(iters), float(max_rms), _p(res)))
+        return self.learned_body(res, sel.size)
+
+    def learn_rigid_body_dev(self, n_frames, K_max, d_xyz, d_n_pts, d_id, d_status, sel, ref_frame, iters, max_rms, d_result):
+        """Device pointers (ints; d_status may be 0); sel: host ids; d_result: device-accessible double[LB_RESULT]."""
+        sel = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+        self._check(self.lib.mocap_learn_rigid_body_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_n_pts), _vp(d_id),
+                                                        _vp(d_status or 0), sel.size, _p(sel), int(ref_frame), int(iters),
+                                                        float(max_rms), _vp(d_result)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

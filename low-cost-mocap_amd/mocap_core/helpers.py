@@ -519,6 +519,74 @@ def set_rigid_bodies(bodies, tol=0.01, max_rms=0.005, work_cap=0):
         _state["bodies"] = (names, markers, float(tol), float(max_rms), int(work_cap)) if bodies else None
 
 
+def _default_selection(ids, n_pts, status):
+    """learn_rigid_body's sel=None rule: the track ids present (among a frame's first n_pts slots) in at least half of the
+    valid frames, ascending."""
+    F, K_max = ids.shape
+    valid = (n_pts >= 0) & (n_pts <= K_max)
+    if status is not None:
+        valid &= status == 0
+    n_valid = int(valid.sum())
+    live = valid[:, None] & (np.arange(K_max)[None, :] < n_pts[:, None]) & (ids >= 0)
+    frames, seen = np.nonzero(live)
+    pairs = np.unique(np.stack([frames, ids[frames, seen]], axis=1), axis=0) if frames.size else np.zeros((0, 2), dtype=np.int64)
+    found, counts = np.unique(pairs[:, 1], return_counts=True)
+    sel = [int(i) for i, c in zip(found, counts) if 2 * int(c) >= n_valid]
+    if not 3 <= len(sel) <= capi.RB_MAX_MARKERS:
+        raise ValueError(f"learn_rigid_body: {len(sel)} track ids are present in at least half of the {n_valid} valid frames, a body "
+                         f"has 3 .. {capi.RB_MAX_MARKERS} markers (frames per id: {dict(zip(found.tolist(), counts.tolist()))}); pass sel")
+    return sel
+
+
+def learn_rigid_body(capture, sel=None, name="body", **kw):
+    """A body's marker set learned from a capture of it in motion (mocap_learn_rigid_body, include/mocap_core.h).  capture =
+    {"xyz" [F][K_max][3], "n_pts" | "n_out" [F], "id" [F][K_max], "status" [F] (optional)}: the frame path's points and the marker
+    tracker's ids, as NumPy arrays or as torch tensors on the core's GPU (those are read in place, only the result crosses PCIe).
+    sel = the track ids of the body's markers; None = the ids present in at least half of the valid frames (ValueError unless that
+    gives 3 .. 8).  kw: ref_frame, iters, max_rms.  Returns MocapCore.learn_rigid_body's dict plus "name" and "sel": hand it to
+    set_rigid_bodies([learned], tol=...) with tol < learned["min_pair_distance"] / 2.  No frame that shows every selected marker
+    raises capi.MocapError."""
+    xyz = capture["xyz"]
+    n_pts = capture["n_pts"] if "n_pts" in capture else capture["n_out"]
+    ids, status = capture["id"], capture.get("status")
+    ref_frame, iters, max_rms = int(kw.pop("ref_frame", -1)), int(kw.pop("iters", 4)), float(kw.pop("max_rms", float("inf")))
+    if kw:
+        raise TypeError(f"learn_rigid_body: unexpected arguments {sorted(kw)}")
+    resident = getattr(xyz, "is_cuda", False)
+    if resident:
+        import torch
+        F, K_max = xyz.shape[0], xyz.shape[1]
+        assert xyz.dtype == torch.float64 and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3
+        assert n_pts.dtype == torch.int32 and n_pts.is_contiguous() and n_pts.is_cuda and n_pts.numel() == F
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.is_cuda and tuple(ids.shape) == (F, K_max)
+        assert status is None or (status.dtype == torch.int32 and status.is_contiguous() and status.is_cuda and status.numel() == F)
+    with _state["lock"]:
+        core = get_core()
+        if resident:
+            if xyz.device.index != core.device_id or any(t is not None and t.device != xyz.device for t in (n_pts, ids, status)):
+                raise ValueError(f"the capture lives on {xyz.device}, the core on GPU {core.device_id}: a resident capture is read in place")
+            torch.cuda.current_stream(xyz.device).synchronize()      # whatever torch itself still has queued on these buffers
+        if sel is None:
+            host = (lambda t: None if t is None else t.cpu().numpy()) if resident else (lambda a: None if a is None else np.asarray(a))
+            sel = _default_selection(host(ids).astype(np.int32), host(n_pts).astype(np.int32).reshape(-1), host(status))
+        sel = [int(i) for i in sel]
+        if resident:
+            result = torch.empty(capi.LB_RESULT, dtype=torch.float64, device=xyz.device)
+            core.learn_rigid_body_dev(F, K_max, xyz.data_ptr(), n_pts.data_ptr(), ids.data_ptr(), 0 if status is None else status.data_ptr(),
+                                      sel, ref_frame, iters, max_rms, result.data_ptr())
+            core.synchronize()
+            learned = core.learned_body(result.cpu().numpy(), len(sel))
+        else:
+            learned = core.learn_rigid_body(np.asarray(xyz), np.asarray(n_pts), np.asarray(ids), sel,
+                                            None if status is None else np.asarray(status), ref_frame, iters, max_rms)
+    if learned["status"] & capi.LB_ST_NO_REF:
+        raise capi.MocapError(f"learn_rigid_body: no valid frame of the capture shows all {len(sel)} selected markers {sel}"
+                              + (f" (ref_frame {ref_frame} does not)" if ref_frame >= 0 else "")
+                              + ": capture again with every marker in view at once, or pass ref_frame = a frame that shows them all")
+    learned["name"], learned["sel"] = str(name), sel
+    return learned
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
