@@ -1107,6 +1107,99 @@ int mocap_ba_solve(mocap_ctx* ctx, double* x, int64_t N, const double* obs, doub
 int mocap_ba_solve_ex(mocap_ctx* ctx, double* x, int64_t N, const double* obs, double ftol, double xtol,
                       double gtol, int max_iter, int f32_residuals, int use_cauchy, double* info, int info_len);
 
+/* ---------------------------------------------------------------- joint bundle adjustment (the core's own contract)
+ * The camera poses AND all 3-D points as unknowns, optionally one focal scale per camera: the true reprojection error, every camera
+ * with its own K, analytic Jacobians, a Huber cost, Levenberg-Marquardt on the Schur-reduced camera system.  The entry points above
+ * restate the reference's bundle_adjustment (helpers.py:244-290) with its limits: dead focal entries, a forward-difference Jacobian
+ * with a float32 step, points that are never variables but re-triangulated by DLT at every evaluation -- with the intrinsics by
+ * compacted index -- and a mean of squared errors per point.  Opt-in and beside them: with nothing called nothing changes.
+ *
+ * Cameras.  Intrinsics from mocap_set_cameras (its R, t are ignored); every K must be plain, [[fx,0,cx],[0,fy,cy],[0,0,1]].  Poses
+ *   are the arguments R [C][9] (row-major), t [C][3], in and out; camera 0 is fixed and NEVER written.  2 <= C <=
+ *   MOCAP_BAJ_MAX_CAMERAS.  obs [N][C][2] with NaN for unseen, as mocap_ba_solve takes them; 1 <= N <= MOCAP_BAJ_MAX_POINTS.
+ * Unknowns.  Per camera c >= 1 a rotation increment w (R <- exp([w]x) R, linearised at w = 0) and t: columns 6 (c - 1) .. + 5 of
+ *   the reduced system, w first.  With MOCAP_BAJ_FOCAL (C >= 3: with two cameras the scale of the focal lengths is not
+ *   observable) one scale s_c per camera, camera 0 included: fx = fx0 s_c, fy = fy0 s_c, column 6 (C - 1) + c; fscale [C] in and
+ *   out (without the flag it is not read and every s_c = 1).  Per point X [3].  n_c = 6 (C - 1) + (C with the flag); NP = n_c + 1
+ *   rounded up to a multiple of 16 (<= 112).
+ * Points.  A point TAKES PART iff it has >= 2 views (observations without a NaN), all of them finite, and a usable position: in
+ *   mocap_ba_joint_solve the DLT point of its views -- dlt_accumulate / solve_point, the device functions of mocap_triangulate,
+ *   on the table P_c = K_c [R_c | t_c] of each camera's OWN K at the poses as they came, P[i][j] = (K[i][0] M[0][j] + K[i][1] M[1][j])
+ *   + K[i][2] M[2][j], M = [R | t] -- which must be finite and have w = ((P20 X0 + P21 X1) + P22 X2) + P23 finite and > 0 in every
+ *   view; in mocap_ba_joint_normal_eq the given X row, which must be finite.  The other points are counted in info and are NaN in
+ *   X_out.
+ * One view of a point at X, camera (R, t, fx, fy, cx, cy), observation (u, v), huber_px = d:
+ *   P_i = (R_i0 X0 + R_i1 X1) + R_i2 X2;  Y_i = P_i + t_i.  The view is USED iff Y2 is finite and > 0 (a view that is not used
+ *   contributes nothing anywhere, and is counted).  xn = Y0 / Y2, yn = Y1 / Y2;  ru = (fx xn + cx) - u, rv = (fy yn + cy) - v;
+ *   s2 = ru ru + rv rv, s = sqrt(s2).  Down-weighted iff d > 0 and s > d: w = d / s, rho = (2 d) s - d d; otherwise w = 1, rho = s2.
+ *   IRLS: every row is scaled by sw = sqrt(w) of the linearisation point:  r = (sw ru, sw rv);
+ *   du0 = sw (fx / Y2), dv1 = sw (fy / Y2), du2 = -(du0 xn), dv2 = -(dv1 yn)          (the rows of sw dr/dY: (du0, 0, du2), (0, dv1, dv2))
+ *   B = dr/dX:      Bu[j] = du0 R_0j + du2 R_2j,   Bv[j] = dv1 R_1j + dv2 R_2j
+ *   A = dr/d(w, t): Au = (du2 P1,  du0 P2 - du2 P0,  -(du0 P1),  du0, 0, du2),   Av = (dv2 P1 - dv1 P2,  -(dv2 P0),  dv1 P0,  0, dv1, dv2)
+ *   focal column:   Au[6] = sw (fx xn), Av[6] = sw (fy yn): the derivative for the update s <- s (1 + delta), at the current fx, fy.
+ * One linearisation at damping lam (Marquardt: lam times the diagonals of V and of U), per point over its used views in camera order:
+ *   rho_p = sum rho;  V (00 01 02 11 12 22):  V_ij = V_ij + (Bu[i] Bu[j] + Bv[i] Bv[j]);  g_p[j] = g_p[j] + (Bu[j] ru + Bv[j] rv), from 0.
+ *   V_lam = L L^T:  a_ii = V_ii + lam V_ii;  l00 = sqrt(a00), l10 = V01 / l00, l20 = V02 / l00, d1 = a11 - l10 l10, l11 = sqrt(d1),
+ *   l21 = (V12 - l20 l10) / l11, d2 = (a22 - l20 l20) - l21 l21, l22 = sqrt(d2).  a00, d1, d2 finite and > 0, else the point is
+ *   SINGULAR for this linearisation: its E and z are zero and it does not move (MOCAP_BAJ_ST_POINT_SINGULAR).
+ *   z = L^-1 g_p:  z0 = g0 / l00, z1 = (g1 - l10 z0) / l11, z2 = ((g2 - l20 z0) - l21 z1) / l22.
+ *   Per used view and parameter k of its camera:  W = (Au[k] Bu[j] + Av[k] Bv[j]), j < 3;  the column of E = L^-1 W^T by the same
+ *   forward substitution.  The columns of cameras that do not see the point are zero.
+ *   Per camera over the points in the tree below:  U (upper triangle of 7 x 7) = sum (Au[i] Au[j] + Av[i] Av[j]),  g_c[i] = sum (Au[i] ru
+ *   + Av[i] rv);  cost = sum of rho_p over the points.
+ *   sum_p E^T E and sum_p E^T z: the point's three rows [E | z] of a row-major matrix [3 N padded to a multiple of 4][NP], padding
+ *   zero, through the FP64 matrix cores (v_mfma_f64_16x16x4_f64) and the fixed slice order of the Gram of mocap_ba_normal_eq.
+ *   Host (plain double loops):  S = U_lam - sum E^T E with U_lam's diagonal U_ii + lam U_ii,  rhs = -g_c + sum E^T z;  S delta = rhs by
+ *   a dense Cholesky (row by row, sums left to right), which fails on a pivot that is not finite or not > 0.
+ * One iteration.  delta from the system at lam; per point y = z + E delta (columns ascending), L^T x = y backwards, X_trial = X - x;
+ *   cameras R <- exp([delta_w]x) R (Rodrigues on the host), t <- t + delta_t, s <- s (1 + delta_s).  The trial is linearised at
+ *   lam' = max(lam / 10, 1e-12), the damping it will have if it is accepted.  ACCEPTED iff S factorised, the trial cost is finite, no
+ *   view of a participating point is unused, and cost_trial < cost (strict): then lam = lam' and the trial's linearisation IS the
+ *   next iteration's system -- it is never computed twice.  REJECTED: lam = 10 lam, and the current point is linearised again at
+ *   the new damping (E and L depend on it).  lam_0 = 1e-3.  The solve stops when an accepted step lowers the cost by <= ftol * cost,
+ *   when lam > 1e12 (MOCAP_BAJ_ST_LAMBDA), or after max_iter passes (MOCAP_BAJ_ST_MAX_ITER); a pass is one trial.
+ * Gauge.  The scale is free: at the end every t and X is multiplied by |t_1 in| / |t_1 out|, so a scale set by
+ *   mocap_determine_scale survives.  A camera with no observation on a participating point (MOCAP_BAJ_ST_CAMERA_UNSEEN), or no
+ *   participating point at all (MOCAP_BAJ_ST_NO_POINTS): the call returns 0 with R, t, fscale untouched and X_out the start.
+ * One tree for U, g_c, the cost and the counters, a function of N alone (the calibration tail's): one lane per point, 256 points per
+ *   workgroup, grid ceil(N / 256) x C; lane -> wave by shuffles, wave -> workgroup through LDS in wave order, one partial per
+ *   workgroup into a slab; one wave per camera folds its slab.  No floating-point atomics anywhere: two calls on the same input
+ *   give the same bytes.  All arithmetic is IEEE double, no fused operation.  A pass is 6 launches (linearise, Gram, Gram reduce,
+ *   camera blocks, fold, back-substitution) and one host round trip, S down and delta up; a rejected trial costs a second one.
+ *
+ * mocap_ba_joint_normal_eq: ONE linearisation at the given poses and the given points X [N][3] (NaN rows do not take part), at
+ *   damping `lambda` (finite, >= 0): S [n_c][n_c], rhs [n_c] and *cost (may be NULL) to the host.  Exported, like mocap_ba_normal_eq,
+ *   so that tests can check the linearisation itself.  info (may be NULL): [5] .. [8] below; MOCAP_BAJ_ST_BAD_DEPTH when a view
+ *   was not used.
+ * mocap_ba_joint_solve: the loop.  X_out [N][3] (may be NULL).  info [MOCAP_BAJ_INFO] (may be NULL):
+ *   [0] passes  [1] accepted steps  [2] cost at the start  [3] cost  [4] final lam  [5] participating points  [6] excluded points
+ *   [7] views down-weighted in the last accepted linearisation  [8] MOCAP_BAJ_ST_* flags  [9] elapsed ms (host clock, the whole
+ *   call)  [10] ms inside the passes between device events  [11] linearisations made.
+ *   mocap_set_ba_progress is honoured: cb(x, n, user) once per accepted step, x in the reference's layout [f0, (f_i, rotvec_i, t_i)],
+ *   n = 1 + 7 (C - 1), f = fx0 s.
+ * MOCAP_E_NOCAMS without cameras.  MOCAP_E_ARG, every output untouched, for: C or N out of range; a K that is not plain; MOCAP_BAJ_FOCAL
+ *   with C = 2; unknown flag bits; huber_px, ftol or lambda negative or not finite; max_iter < 1; a null obs, R, t, X, S or rhs, or a
+ *   null fscale with MOCAP_BAJ_FOCAL.
+ * Out of scope: lens distortion and the principal point as unknowns, more than 16 cameras, a sparse reduced system. */
+#define MOCAP_BAJ_MAX_CAMERAS 16
+#define MOCAP_BAJ_MAX_POINTS 131072
+#define MOCAP_BAJ_INFO 12 /* doubles */
+#define MOCAP_BAJ_FOCAL 1u /* flags: one focal scale per camera is an unknown */
+enum {
+  MOCAP_BAJ_ST_CAMERA_UNSEEN = 1,   /* a camera has no observation on a participating point: nothing was changed */
+  MOCAP_BAJ_ST_NO_POINTS = 2,       /* no point takes part: nothing was changed */
+  MOCAP_BAJ_ST_SINGULAR = 4,        /* the reduced system had no Cholesky factor in some pass (that trial was rejected) */
+  MOCAP_BAJ_ST_POINT_SINGULAR = 8,  /* some point's V_lambda had no Cholesky factor in some linearisation (the point did not move) */
+  MOCAP_BAJ_ST_LAMBDA = 16,         /* stopped because lam > 1e12 */
+  MOCAP_BAJ_ST_MAX_ITER = 32,       /* stopped after max_iter passes */
+  MOCAP_BAJ_ST_BAD_DEPTH = 64       /* mocap_ba_joint_normal_eq: a view was not used (depth not finite or <= 0) */
+};
+int mocap_ba_joint_normal_eq(mocap_ctx* ctx, int64_t N, const double* obs, const double* R, const double* t, const double* fscale,
+                             const double* X, uint32_t flags, double huber_px, double lambda, double* S, double* rhs, double* cost,
+                             double* info);
+int mocap_ba_joint_solve(mocap_ctx* ctx, int64_t N, const double* obs, double* R, double* t, double* fscale, double* X_out,
+                         uint32_t flags, double huber_px, double ftol, int max_iter, double* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
 // and behind each a final launch of one wave that folds the workgroups' partials and writes what the next launch reads: the
 // template of the next round never visits the host.
 //
-// Determinism: the tree of calib_tail.hip.  One lane per frame, kCalibThreads frames per workgroup, lane -> wave by __shfl_down
+// Determinism: the tree of calib_tail.hip (csrc/tree_fold.hpp).  One lane per frame, kCalibThreads frames per workgroup, lane -> wave by __shfl_down
 // (offsets 32 .. 1), wave -> workgroup through LDS in wave order, one partial per workgroup into the slab, one wave whose lane l
 // folds the entries [l * ceil(P / 64), ...) in index order before the same shuffle tree.  No atomics: every value is a function of
 // the inputs and F alone.  FP64 throughout, nothing fused (-ffp-contract=off is the build's rule).
@@ -20,6 +20,7 @@
 #include "body_learn.hpp"
 #include "mocap_device.hpp"
 #include "rb_pose.hpp"
+#include "tree_fold.hpp"
 
 namespace mocap {
 
@@ -27,57 +28,6 @@ namespace {
 
 constexpr int kT = kCalibThreads, kWaves = kCalibThreads / 64, kM = kRbMaxMarkers;
 constexpr int kLbNoRef = 1, kLbMarkerUnseen = 2;  // mirrored from include/mocap_core.h (MOCAP_LB_ST_*)
-
-// lane 0 of the wave ends up with the sum of all 64 lanes; entry kMin (if any) with the minimum
-template <int n, int kMin>
-__device__ __forceinline__ void wave_fold(double (&v)[n]) {
-  for (int off = 32; off; off >>= 1) {
-#pragma unroll
-    for (int i = 0; i < n; i++) {
-      const double o = __shfl_down(v[i], off);
-      v[i] = i == kMin ? (o < v[i] ? o : v[i]) : v[i] + o;
-    }
-  }
-}
-
-// every lane's v -> out[0 .. n) of this workgroup's slab entry (thread 0 writes); s: [kWaves][n] doubles of LDS
-template <int n, int kMin>
-__device__ __forceinline__ void block_fold(double (&v)[n], double (*s)[n], double* out) {
-  wave_fold<n, kMin>(v);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < n; i++) s[wave][i] = v[i];
-  }
-  block_sync_lds();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) {
-#pragma unroll
-      for (int i = 0; i < n; i++) {
-        const double o = s[w][i];
-        v[i] = i == kMin ? (o < v[i] ? o : v[i]) : v[i] + o;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < n; i++) out[i] = v[i];
-  }
-}
-
-// the one wave of a final launch: slab [P][n] -> v of lane 0; `init` = the neutral element of entry kMin
-template <int n, int kMin>
-__device__ __forceinline__ void slab_fold(const double* slab, int64_t P, double init, double (&v)[n]) {
-  const int64_t chunk = (P + 63) / 64, lo = threadIdx.x * chunk, hi = lo + chunk < P ? lo + chunk : P;
-#pragma unroll
-  for (int i = 0; i < n; i++) v[i] = i == kMin ? init : 0.0;
-  for (int64_t e = lo; e < hi; e++) {
-#pragma unroll
-    for (int i = 0; i < n; i++) {
-      const double o = slab[e * n + i];
-      v[i] = i == kMin ? (o < v[i] ? o : v[i]) : v[i] + o;
-    }
-  }
-  wave_fold<n, kMin>(v);
-}
 
 __device__ __forceinline__ bool finite3(const double* p) {
   return fabs(p[0]) < __builtin_inf() && fabs(p[1]) < __builtin_inf() && fabs(p[2]) < __builtin_inf();  // false for NaN

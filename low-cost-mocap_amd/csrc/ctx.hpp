@@ -150,6 +150,10 @@ struct mocap_ctx {
   double bt_g2 = 0.0, bt_alpha = 0.0;
   DevBuf bt_state;          // BodyTrackState: one slot per registered body
   DevBuf bt_search;         // mocap_track_bodies*: the per-frame search's outputs, which the tracker reads
+  // joint bundle adjustment (csrc/ba_joint_capi.hip): two sets of (poses, points, E, L), the Gram slices and the camera slab;
+  // pinned: G and the camera blocks down, the poses and delta up
+  DevBuf baj_ws;
+  PinBuf baj_pin;
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);

@@ -149,4 +149,120 @@ bool CholSecular::solve(double Delta, double& alpha_io, double* p_live) {
   return true;
 }
 
+// ------------------------------------------------------------------ joint bundle adjustment
+void baj_assemble(int C, bool focal, int NP, const double* G, const double* sums, double lambda, double* S, double* rhs) {
+  const int n = 6 * (C - 1) + (focal ? C : 0);
+  auto u = [](int i, int j) { return i * 7 - i * (i - 1) / 2 + (j - i); };  // packed upper triangle of the 7 x 7 block
+  for (int i = 0; i < n * n; i++) S[i] = 0.0;
+  for (int i = 0; i < n; i++) rhs[i] = 0.0;
+  for (int c = 0; c < C; c++) {
+    const double* U = sums + 41 * c;
+    int idx[7];  // the block's rows in S; -1 = not an unknown
+    for (int k = 0; k < 6; k++) idx[k] = c ? 6 * (c - 1) + k : -1;
+    idx[6] = focal ? 6 * (C - 1) + c : -1;
+    for (int i = 0; i < 7; i++) {
+      if (idx[i] < 0) continue;
+      for (int j = i; j < 7; j++) {
+        if (idx[j] < 0) continue;
+        const double v = i == j ? U[u(i, i)] + lambda * U[u(i, i)] : U[u(i, j)];
+        S[idx[i] * n + idx[j]] = v;
+        S[idx[j] * n + idx[i]] = v;
+      }
+      rhs[idx[i]] = -U[28 + i];
+    }
+  }
+  for (int i = 0; i < n; i++) {
+    for (int j = i; j < n; j++) {
+      const double v = S[i * n + j] - G[(size_t)i * NP + j];
+      S[i * n + j] = v;
+      S[j * n + i] = v;
+    }
+    rhs[i] = rhs[i] + G[(size_t)i * NP + n];
+  }
+}
+
+bool baj_chol_solve(int n, double* S, const double* rhs, double* delta) {
+  // S = L L^T, L in the lower triangle, row by row, every sum left to right
+  for (int i = 0; i < n; i++) {
+    for (int j = 0; j <= i; j++) {
+      double s = S[i * n + j];
+      for (int k = 0; k < j; k++) s = s - S[i * n + k] * S[j * n + k];
+      if (i == j) {
+        if (!(s - s == 0.0) || !(s > 0.0)) return false;
+        S[i * n + i] = std::sqrt(s);
+      } else {
+        S[i * n + j] = s / S[j * n + j];
+      }
+    }
+  }
+  for (int i = 0; i < n; i++) {  // L y = rhs
+    double s = rhs[i];
+    for (int k = 0; k < i; k++) s = s - S[i * n + k] * delta[k];
+    delta[i] = s / S[i * n + i];
+  }
+  for (int i = n - 1; i >= 0; i--) {  // L^T delta = y
+    double s = delta[i];
+    for (int k = i + 1; k < n; k++) s = s - S[k * n + i] * delta[k];
+    delta[i] = s / S[i * n + i];
+  }
+  for (int i = 0; i < n; i++)
+    if (!(delta[i] - delta[i] == 0.0)) return false;
+  return true;
+}
+
+void baj_rotate(const double* w, double* R) {
+  const double t2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+  const double th = std::sqrt(t2);
+  // a = sin(th) / th, b = (1 - cos(th)) / th^2; their series below 1e-4 rad (the next terms are < 1e-17 relative)
+  const double a = th < 1e-4 ? 1.0 - t2 / 6.0 : std::sin(th) / th;
+  const double b = th < 1e-4 ? 0.5 - t2 / 24.0 : (1.0 - std::cos(th)) / t2;
+  // E = I + a [w]x + b [w]x^2, [w]x^2 = w w^T - |w|^2 I
+  double E[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) E[3 * i + j] = b * (w[i] * w[j]) + (i == j ? 1.0 - b * t2 : 0.0);
+  E[1] = E[1] - a * w[2];
+  E[2] = E[2] + a * w[1];
+  E[3] = E[3] + a * w[2];
+  E[5] = E[5] - a * w[0];
+  E[6] = E[6] - a * w[1];
+  E[7] = E[7] + a * w[0];
+  double out[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) out[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
+  for (int i = 0; i < 9; i++) R[i] = out[i];
+}
+
+void baj_rotvec(const double* R, double* rv) {
+  // Shepperd: the largest of w^2, x^2, y^2, z^2 first
+  const double tr = R[0] + R[4] + R[8];
+  double q[4];  // w x y z
+  if (tr >= R[0] && tr >= R[4] && tr >= R[8]) {
+    q[0] = 1.0 + tr;
+    q[1] = R[7] - R[5];
+    q[2] = R[2] - R[6];
+    q[3] = R[3] - R[1];
+  } else if (R[0] >= R[4] && R[0] >= R[8]) {
+    q[0] = R[7] - R[5];
+    q[1] = 1.0 + R[0] - R[4] - R[8];
+    q[2] = R[1] + R[3];
+    q[3] = R[2] + R[6];
+  } else if (R[4] >= R[8]) {
+    q[0] = R[2] - R[6];
+    q[1] = R[1] + R[3];
+    q[2] = 1.0 - R[0] + R[4] - R[8];
+    q[3] = R[5] + R[7];
+  } else {
+    q[0] = R[3] - R[1];
+    q[1] = R[2] + R[6];
+    q[2] = R[5] + R[7];
+    q[3] = 1.0 - R[0] - R[4] + R[8];
+  }
+  if (q[0] < 0.0)
+    for (int i = 0; i < 4; i++) q[i] = -q[i];
+  const double s = std::sqrt((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]);
+  const double angle = 2.0 * std::atan2(s, q[0]);
+  const double k = s > 0.0 ? angle / s : 0.0;
+  for (int i = 0; i < 3; i++) rv[i] = k * q[1 + i];
+}
+
 }  // namespace mocap

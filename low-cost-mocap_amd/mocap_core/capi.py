@@ -55,6 +55,17 @@ RF_STEPS_SHIFT = 8        # ... and the accepted steps, info >> 8
 LB_RESULT = 129           # mocap_learn_rigid_body: doubles of its `result`
 LB_ST_NO_REF = 1          # ... status flags: no valid frame shows every selected marker (or the given ref_frame does not)
 LB_ST_MARKER_UNSEEN = 2   # ... a marker had no used frame in some round and kept its previous position
+BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
+BAJ_MAX_POINTS = 131072   # ... points at most
+BAJ_INFO = 12             # ... doubles of `info`
+BAJ_FOCAL = 1             # ... flag: one focal scale per camera is an unknown (needs 3 cameras)
+BAJ_ST_CAMERA_UNSEEN = 1  # ... status: a camera has no observation on a participating point, nothing was changed
+BAJ_ST_NO_POINTS = 2      # ... no point takes part, nothing was changed
+BAJ_ST_SINGULAR = 4       # ... the reduced system had no Cholesky factor in some pass
+BAJ_ST_POINT_SINGULAR = 8 # ... some point's 3 x 3 block had no Cholesky factor in some linearisation
+BAJ_ST_LAMBDA = 16        # ... stopped because the damping passed 1e12
+BAJ_ST_MAX_ITER = 32      # ... stopped after max_iter passes
+BAJ_ST_BAD_DEPTH = 64     # ... ba_joint_normal_eq: a view was not used (depth not finite or <= 0)
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
@@ -168,6 +179,8 @@ SIGNATURES = {
     "mocap_ba_profile": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
     "mocap_ba_solve": (_i32, [_vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _i32, _i32, _i32, _vp]),
     "mocap_ba_solve_ex": (_i32, [_vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _i32, _i32, _i32, _vp, _i32]),
+    "mocap_ba_joint_normal_eq": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "mocap_ba_joint_solve": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _i32, _vp]),
 }
 
 _lib = None
@@ -1222,3 +1235,63 @@ class MocapCore:
                                                     _p(info), info.size), allow=(MOCAP_E_NOCONV,))
         keys = ("iterations", "nfev", "status", "cost0", "cost", "optimality", "m", "elapsed_ms", "njev", "relaunches")
         return x, dict(zip(keys, info.tolist()), converged=(rc == MOCAP_OK))
+
+    # ------------------------------------------------------------------ joint bundle adjustment (poses and points together)
+    _BAJ_INFO_KEYS = ("passes", "accepted", "cost0", "cost", "lambda", "participating", "excluded", "down_weighted", "status",
+                      "elapsed_ms", "device_ms", "linearisations")
+
+    def _baj_inputs(self, obs, R, t, fscale, refine_focal, huber_px):
+        """The checks that need no device, as the library makes them (MOCAP_E_ARG), and the arrays in the C layout."""
+        C = self.C
+        obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, C, 2) if C else np.ascontiguousarray(obs, dtype=np.float64)
+        R = np.array(R, dtype=np.float64, order="C").reshape(-1, 9)
+        t = np.array(t, dtype=np.float64, order="C").reshape(-1, 3)
+        bad = None
+        if C and not (R.shape[0] == C and t.shape[0] == C):
+            bad = f"R and t must hold {C} cameras"
+        elif refine_focal and C == 2:
+            bad = "refine_focal needs at least 3 cameras"
+        elif not (np.isfinite(huber_px) and huber_px >= 0):
+            bad = "huber_px must be finite and >= 0"
+        if bad:
+            e = MocapError(f"mocap_core error {MOCAP_E_ARG}: joint bundle adjustment: {bad}")
+            e.code = MOCAP_E_ARG
+            raise e
+        s = None
+        if refine_focal:
+            s = np.ones(C) if fscale is None else np.array(fscale, dtype=np.float64, order="C").reshape(C)
+        return obs, R, t, s
+
+    def ba_joint_normal_eq(self, obs, R, t, X, fscale=None, refine_focal=False, huber_px=0.0, lam=0.0):
+        """mocap_ba_joint_normal_eq: one linearisation of the joint problem at the poses (R [C][3][3], t [C][3]), the focal scales
+        and the points X [N][3] (NaN rows do not take part) -> {"S" [n_c][n_c], "rhs" [n_c], "cost", "info"}: the Schur-reduced
+        camera system at damping `lam`, columns (omega, t) per camera 1 .. C-1, then one focal scale per camera with refine_focal."""
+        obs, R, t, s = self._baj_inputs(obs, R, t, fscale, refine_focal, huber_px)
+        N = obs.shape[0]
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(N, 3)
+        n_c = 6 * (self.C - 1) + (self.C if refine_focal else 0)
+        S = np.zeros((max(n_c, 0), max(n_c, 0)))
+        rhs = np.zeros(max(n_c, 0))
+        cost = ctypes.c_double()
+        info = np.zeros(BAJ_INFO)
+        self._check(self.lib.mocap_ba_joint_normal_eq(self._h, N, _p(obs), _p(R), _p(t), _p(s), _p(X), BAJ_FOCAL if refine_focal else 0,
+                                                      float(huber_px), float(lam), _p(S), _p(rhs), ctypes.addressof(cost), _p(info)))
+        return {"S": S, "rhs": rhs, "cost": cost.value, "info": dict(zip(self._BAJ_INFO_KEYS, info.tolist()))}
+
+    def ba_joint_solve(self, obs, R, t, fscale=None, refine_focal=False, huber_px=0.0, ftol=1e-10, max_iter=50):
+        """mocap_ba_joint_solve: Levenberg-Marquardt over the poses of cameras 1 .. C-1, every point and (refine_focal) one focal
+        scale per camera -> (R [C][3][3], t [C][3], fscale [C] or None, X [N][3], info).  Camera 0 comes back as it went in, |t_1|
+        too (the gauge); rows of X whose point did not take part are NaN.  set_ba_progress is honoured."""
+        obs, R, t, s = self._baj_inputs(obs, R, t, fscale, refine_focal, huber_px)
+        if not (np.isfinite(ftol) and ftol >= 0) or int(max_iter) < 1:
+            e = MocapError(f"mocap_core error {MOCAP_E_ARG}: joint bundle adjustment: ftol must be finite and >= 0, max_iter >= 1")
+            e.code = MOCAP_E_ARG
+            raise e
+        N = obs.shape[0]
+        X = np.full((N, 3), np.nan)
+        info = np.zeros(BAJ_INFO)
+        self._check(self.lib.mocap_ba_joint_solve(self._h, N, _p(obs), _p(R), _p(t), _p(s), _p(X), BAJ_FOCAL if refine_focal else 0,
+                                                  float(huber_px), float(ftol), int(max_iter), _p(info)))
+        info = dict(zip(self._BAJ_INFO_KEYS, info.tolist()))
+        info["status"] = int(info["status"])
+        return R.reshape(-1, 3, 3), t, s, X, info

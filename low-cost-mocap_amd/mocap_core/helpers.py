@@ -1163,3 +1163,43 @@ def bundle_adjustment(image_points, camera_poses, socketio, return_info=False):
     if socketio is not None:
         socketio.emit("camera-pose", {"camera_poses": camera_pose_to_serializable(poses)})
     return (poses, info) if return_info else poses
+
+
+def bundle_adjustment_joint(image_points, camera_poses, socketio=None, refine_focal=False, huber_px=0.0, max_iter=50, ftol=1e-10,
+                            return_info=False):
+    """The core's own calibration refinement (mocap_ba_joint_solve, include/mocap_core.h "joint bundle adjustment"): the poses of
+    cameras 1 .. C-1 and every 3-D point as unknowns -- with refine_focal also one focal scale per camera, which needs three
+    cameras -- the true reprojection error with each camera's own K, analytic Jacobians, a Huber cost at huber_px (0 = off).
+    Opt-in, beside bundle_adjustment: that function, its two modes and DEFAULT_BA_MODE are what they were.
+
+    Returns camera_poses in the reference's dict shape ({"R": 3x3, "t": 3}; camera 0 as it came, |t_1| as it came: the scale
+    determine_scale set survives); with refine_focal (poses, scales); with return_info the solver's info dict last.  Runs on bundle
+    adjustment's own context under its lock, like bundle_adjustment; `socketio.emit("camera-pose", ...)` once per accepted step, then
+    the final poses."""
+    C = len(camera_poses)
+    if refine_focal and C < 3:
+        raise ValueError("refine_focal needs at least 3 cameras: with two, the scale of the focal lengths is not observable")
+    if not (np.isfinite(huber_px) and huber_px >= 0 and np.isfinite(ftol) and ftol >= 0 and int(max_iter) >= 1):
+        raise ValueError("huber_px and ftol must be finite and >= 0, max_iter at least 1")
+    obs = _obs_array(image_points, C)
+    R, t = _pose_arrays(camera_poses)
+    K = _intrinsics(C)
+
+    def emit(params):
+        socketio.emit("camera-pose", {"camera_poses": camera_pose_to_serializable(_params_to_camera_poses(params))})
+
+    with _state["lock"]:
+        core = _ba_core()
+    with _state["ba_lock"]:
+        core.set_cameras(K, R, t)
+        core.set_ba_progress(emit if socketio is not None else None)
+        try:
+            R1, t1, scales, _, info = core.ba_joint_solve(obs, R, t, refine_focal=refine_focal, huber_px=huber_px, ftol=ftol,
+                                                          max_iter=max_iter)
+        finally:
+            core.set_ba_progress(None)
+    poses = [{"R": R1[c].copy(), "t": t1[c].copy()} for c in range(C)]
+    if socketio is not None:
+        socketio.emit("camera-pose", {"camera_poses": camera_pose_to_serializable(poses)})
+    out = (poses,) + ((scales,) if refine_focal else ()) + ((info,) if return_info else ())
+    return out[0] if len(out) == 1 else out
