@@ -1200,6 +1200,98 @@ int mocap_ba_joint_normal_eq(mocap_ctx* ctx, int64_t N, const double* obs, const
 int mocap_ba_joint_solve(mocap_ctx* ctx, int64_t N, const double* obs, double* R, double* t, double* fscale, double* X_out,
                          uint32_t flags, double huber_px, double ftol, int max_iter, double* info);
 
+/* ---------------------------------------------------------------- camera resection (the core's own contract)
+ * ONE camera's pose from 3-D points in the rig's frame and where that camera saw them (PnP): minimal-sample hypotheses, every
+ * candidate pose scored against every row, a least-squares refinement over the inliers.  The rig's scale, frame and world transform
+ * are those of the points: nothing else is touched.  The reference has no counterpart (a knocked camera means a new calibration
+ * there).  Opt-in and beside everything above: with nothing called nothing changes.  Needs no mocap_set_cameras.
+ *
+ * Inputs.  X [N][3], obs [N][2] (pixels), 1 <= N <= MOCAP_RESECT_MAX_POINTS; a row that holds a NaN or an infinity is skipped; the
+ *   VALID rows keep their order and are numbered 0 .. n-1.  K [9] row-major, plain: [[fx,0,cx],[0,fy,cy],[0,0,1]], fx, fy finite
+ *   and > 0 -- the camera's own matrix, used as it is (no intrinsics-by-index here); a K with skew is refused.  A pose is R [9]
+ *   row-major and t [3], x = R X + t in the camera's frame.  prior_R / prior_t: both or neither.
+ * One view at the pose (R, t):  P_i = (R_i0 X0 + R_i1 X1) + R_i2 X2,  x_i = P_i + t_i;  xn = x0 / x2, yn = x1 / x2;
+ *   du = (fx xn + cx) - u, dv = (fy yn + cy) - v, s2 = du du + dv dv.  INLIER iff x2 > 0 and s2 < thr2 (strict),
+ *   thr2 = threshold_px threshold_px.  IEEE +, -, x, / and comparisons only: counts and masks are reproducible bit for bit.
+ * Sampler.  mix(z): z += 0x9e3779b97f4a7c15; z = (z ^ (z >> 30)) 0xbf58476d1ce4e5b9; z = (z ^ (z >> 27)) 0x94d049bb133111eb;
+ *   z ^ (z >> 31) (splitmix64, 64-bit wrapping).  Draw k of hypothesis h: r_k = mix(seed + (3 h + k) 0x9e3779b97f4a7c15).
+ *   i0 = r0 mod n;  i1 = r1 mod (n - 1), + 1 if >= i0;  i2 = r2 mod (n - 2), + 1 if >= min(i0, i1), then + 1 if >= max(i0, i1):
+ *   three distinct valid rows, a pure function of (seed, h, n).
+ * Three-point solver (Grunert).  Bearings j_k = (x, y, 1) / |(x, y, 1)|, x = (u - cx) / fx, y = (v - cy) / fy.  a = |P2 - P3|,
+ *   b = |P1 - P3|, c = |P1 - P2|; cos alpha = j2.j3, cos beta = j1.j3, cos gamma = j1.j2; q = (a2 - c2) / b2, p = (a2 + c2) / b2.
+ *   The quartic in v = s3 / s1:
+ *     A4 = (q - 1)^2 - 4 (c2 / b2) cos2 alpha
+ *     A3 = 4 [q (1 - q) cos beta - (1 - p) cos alpha cos gamma + 2 (c2 / b2) cos2 alpha cos beta]
+ *     A2 = 2 [q^2 - 1 + 2 q^2 cos2 beta + 2 ((b2 - c2) / b2) cos2 alpha - 4 p cos alpha cos beta cos gamma + 2 ((b2 - a2) / b2) cos2 gamma]
+ *     A1 = 4 [-q (1 + q) cos beta + 2 (a2 / b2) cos2 gamma cos beta - (1 - p) cos alpha cos gamma]
+ *     A0 = (1 + q)^2 - 4 (a2 / b2) cos2 gamma
+ *   solved in closed form (Ferrari on the resolvent cubic m^3 + p' m^2 + (p'^2 / 4 - r') m - q'^2 / 8 of the depressed quartic, its
+ *   largest real root), every real root polished by two Newton steps on the quartic.  Per root v > 0:
+ *   u = [(q - 1) v^2 - 2 q cos beta v + 1 + q] / (2 (cos gamma - v cos alpha)), kept when u > 0;  s1 = b / sqrt(1 + v^2 - 2 v cos beta);
+ *   camera-frame points Q1 = s1 j1, Q2 = u s1 j2, Q3 = v s1 j3;  R = T_cam T_world^T with T the orthonormal triad of a triple (e1
+ *   along 1 -> 2, e3 = e1 x (1 -> 3) normalised, e2 = e3 x e1, as columns);  t = Q1 - R P1.  Up to 4 poses per hypothesis, in root
+ *   order (the roots of y^2 - s y + .. before those of y^2 + s y + .., the + sqrt before the - sqrt).  No pose from a sample that is
+ *   collinear or near-coincident (|e x f|^2 <= 1e-12 b2 c2, or a squared side <= 1e-18 of the longest), or whose |A4| <= 1e-14 max |A_i|.
+ *   The solver calls acos, cos, cbrt, sqrt: its poses are specified by their residuals, not by their bits.
+ * Hypotheses.  H = max(n_hyp, 1).  With a prior, hypothesis 0 IS the prior: one solution, no sample.  Every other hypothesis h
+ *   samples with its own h.  counts[h][s] = inliers of solution s over all valid rows.
+ * Winner.  Most inliers; ties go to the lower (hypothesis, solution).  Chosen on the device; the first linearisation follows on the
+ *   stream without a host round trip.  Fewer than 4 valid rows: MOCAP_RESECT_TOO_FEW.  No candidate with >= min_inliers inliers:
+ *   MOCAP_RESECT_NO_MODEL.  In both cases R, t come back as the prior if there is one, else NaN, and nothing is refined.
+ * Refinement.  Unknowns: a left rotation increment w (R <- exp([w]x) R) and dt (t <- t + dt).  Per inlier row, with a0 = fx / x2,
+ *   b1 = fy / x2, a2 = -(a0 xn), b2 = -(b1 yn)  (D = d(du, dv)/dx has the rows (a0, 0, a2), (0, b1, b2)):
+ *   Ju = (a2 P1, a0 P2 - a2 P0, -(a0 P1), a0, 0, a2),  Jv = (b2 P1 - b1 P2, -(b2 P0), b1 P0, 0, b1, b2)      = [-D [R X]x | D]
+ *   H_ij = Ju_i Ju_j + Jv_i Jv_j (i <= j),  g_i = Ju_i du + Jv_i dv,  cost = s2;  a row that is not an inlier of the current mask
+ *   contributes zero.  Summed through the project's one tree (one lane per valid row, 256 rows per workgroup, lane -> wave by shuffles,
+ *   wave -> workgroup through LDS in wave order, one partial per workgroup, one wave folds the partials): no floating-point atomics,
+ *   two calls on the same input give the same bytes.  The host takes the step: (H + lam diag H) delta = -g by a dense Cholesky (row by
+ *   row, sums left to right); Rodrigues with a = sin th / th, b = (1 - cos th) / th^2 (th < 1e-8: a = 1 - th^2 / 6, b = 1/2 - th^2 / 24),
+ *   G = a [w]x + b [w]x^2, E = I + G, R' = E R.  lam_0 = 1e-3 per round.  A trial is ACCEPTED iff the factor exists, its cost is finite
+ *   and strictly lower, and every inlier of the mask is still in front of the camera (x2 finite and > 0): lam <- max(lam / 10,
+ *   1e-12); otherwise lam <- 10 lam.  STRICTLY LOWER is decided on the cost's change taken from the increment, not on two rounded
+ *   sums (which agree to fifteen digits near the minimum: their comparison there is noise, and where the loop stops would be luck).
+ *   Per inlier row, at the base pose:  dx_i = ((G_i0 P0 + G_i1 P1) + G_i2 P2) + dt_i;  x2' = x2 + dx2;  dxn = (dx0 - xn dx2) / x2',
+ *   dyn = (dx1 - yn dx2) / x2';  ddu = fx dxn, ddv = fy dyn;  delta = ddu (2 du + ddu) + ddv (2 dv + ddv)  (= s2' - s2 exactly);
+ *   summed through the same tree:  lower iff the sum is < 0.  A round ends after max_iter accepted steps, after a trial whose step has |w|_inf <= 1e-12 and
+ *   |dt|_inf <= 1e-12 (1 + |t|_inf) (taken first if accepted), when lam > 1e12, or at once on an empty mask.
+ * Schedule.  Round 1: mask = the classification at the winner, refine.  Round 2: mask = the classification at the refined pose,
+ *   refine again.  The mask that comes back is the classification at the FINAL pose.
+ * Evaluate only.  max_iter = 0 refines nothing; n_hyp = 0 (which needs a prior) searches nothing.  Both: the prior comes back bit
+ *   for bit with its mask, inliers and rms -- the health check of a calibrated rig (a camera against points built without it).
+ *
+ * mocap_resect_camera: R [9], t [3] out; mask [N] (may be NULL) 1 = inlier at the returned pose, 0 otherwise (skipped rows too);
+ *   info [MOCAP_RESECT_INFO] (may be NULL):  [0] valid rows  [1] the winner's inliers  [2] its hypothesis  [3] its solution (-1, -1: no
+ *   candidate)  [4] hypotheses without a solution  [5] final inliers  [6] accepted steps  [7] linearisations  [8] rms over the final
+ *   inliers at the prior pose (NaN without one)  [9] rms at the winner  [10] rms at the final pose  [11] MOCAP_RESECT_* status.
+ *   rms = sqrt(sum s2 / inliers), NaN without an inlier.  min_inliers >= 4, max_iter >= 0, 0 <= n_hyp <= MOCAP_RESECT_MAX_HYP.
+ * mocap_resect_camera_dev: the same with X and obs as device pointers, on the context's stream; R, t, mask, info are host pointers
+ *   and valid on return.
+ * mocap_resect_hypotheses: the candidate table of the same search (n_hyp >= 1), for tests and debugging: sample [H][3] input rows of
+ *   each sample (-1 for the prior and for hypotheses without a sample), n_sol [H], poses [H][4][12] (R | t; NaN where there is no
+ *   solution), counts [H][4].
+ * MOCAP_E_ARG, every output untouched, for: N or n_hyp out of range; min_inliers < 4; max_iter < 0; a K that is not plain; a
+ *   threshold that is not finite or not > 0; n_hyp = 0 without a prior; one of prior_R, prior_t without the other; a null X, obs, K,
+ *   R or t (or a null output of mocap_resect_hypotheses).
+ * Out of scope: a live-loop stage; re-seating from unlabelled multi-marker frames; lens distortion or intrinsics as unknowns;
+ *   several cameras jointly (mocap_ba_joint_solve afterwards does that); any change to mocap_initial_poses. */
+#define MOCAP_RESECT_MAX_POINTS 131072
+#define MOCAP_RESECT_MAX_HYP 4096
+#define MOCAP_RESECT_INFO 12 /* doubles */
+enum {
+  MOCAP_RESECT_OK = 0,
+  MOCAP_RESECT_TOO_FEW = 1,  /* fewer than 4 valid rows */
+  MOCAP_RESECT_NO_MODEL = 2  /* no candidate pose reaches min_inliers */
+};
+int mocap_resect_camera(mocap_ctx* ctx, int64_t N, const double* X, const double* obs, const double* K, const double* prior_R,
+                        const double* prior_t, double threshold_px, int n_hyp, uint64_t seed, int min_inliers, int max_iter,
+                        double* R, double* t, uint8_t* mask, double* info);
+int mocap_resect_camera_dev(mocap_ctx* ctx, int64_t N, const double* d_X, const double* d_obs, const double* K,
+                            const double* prior_R, const double* prior_t, double threshold_px, int n_hyp, uint64_t seed,
+                            int min_inliers, int max_iter, double* R, double* t, uint8_t* mask, double* info);
+int mocap_resect_hypotheses(mocap_ctx* ctx, int64_t N, const double* X, const double* obs, const double* K, const double* prior_R,
+                            const double* prior_t, double threshold_px, int n_hyp, uint64_t seed, int32_t* sample, int32_t* n_sol,
+                            double* poses, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,9 @@ struct mocap_ctx {
   // pinned: G and the camera blocks down, the poses and delta up
   DevBuf baj_ws;
   PinBuf baj_pin;
+  // camera resection (csrc/resect_capi.hip): rows, candidate table, mask and slab; pinned: the record of a linearisation, poses up
+  DevBuf rs_ws;
+  PinBuf rs_pin;
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);

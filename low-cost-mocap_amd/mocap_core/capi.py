@@ -66,10 +66,15 @@ BAJ_ST_POINT_SINGULAR = 8 # ... some point's 3 x 3 block had no Cholesky factor 
 BAJ_ST_LAMBDA = 16        # ... stopped because the damping passed 1e12
 BAJ_ST_MAX_ITER = 32      # ... stopped after max_iter passes
 BAJ_ST_BAD_DEPTH = 64     # ... ba_joint_normal_eq: a view was not used (depth not finite or <= 0)
+RESECT_MAX_POINTS = 131072  # mocap_resect_*: rows at most
+RESECT_MAX_HYP = 4096     # ... hypotheses at most
+RESECT_INFO = 12          # ... doubles of `info`
+RESECT_OK, RESECT_TOO_FEW, RESECT_NO_MODEL = 0, 1, 2   # ... status: fewer than 4 valid rows / no candidate reaches min_inliers
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
 _vp, _i32, _i64, _dbl, _u32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_uint32
+_u64 = ctypes.c_uint64
 
 # name -> (restype, argtypes); must list every symbol include/mocap_core.h declares
 SIGNATURES = {
@@ -181,6 +186,9 @@ SIGNATURES = {
     "mocap_ba_solve_ex": (_i32, [_vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _i32, _i32, _i32, _vp, _i32]),
     "mocap_ba_joint_normal_eq": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
     "mocap_ba_joint_solve": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _i32, _vp]),
+    "mocap_resect_camera": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mocap_resect_camera_dev": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mocap_resect_hypotheses": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _u64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -1295,3 +1303,78 @@ class MocapCore:
         info = dict(zip(self._BAJ_INFO_KEYS, info.tolist()))
         info["status"] = int(info["status"])
         return R.reshape(-1, 3, 3), t, s, X, info
+
+    # ------------------------------------------------------------------ camera resection
+    RESECT_INFO_KEYS = ("valid", "winner_inliers", "winner_hypothesis", "winner_solution", "no_solution", "inliers", "accepted",
+                        "linearisations", "rms_prior", "rms_winner", "rms_final", "status")
+
+    def _resect_inputs(self, X, obs, K, prior, threshold_px, n_hyp, n_hyp_min):
+        """The checks that need no device, as the library makes them (MOCAP_E_ARG), and the arrays in the C layout."""
+        def refuse(why):
+            e = MocapError(f"mocap_core error {MOCAP_E_ARG}: camera resection: {why}")
+            e.code = MOCAP_E_ARG
+            raise e
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 2)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        if X.shape[0] != obs.shape[0] or not 1 <= X.shape[0] <= RESECT_MAX_POINTS:
+            refuse(f"X [N][3] and obs [N][2] with 1 <= N <= {RESECT_MAX_POINTS}")
+        if not n_hyp_min <= int(n_hyp) <= RESECT_MAX_HYP:
+            refuse(f"n_hyp must be {n_hyp_min} .. {RESECT_MAX_HYP}")
+        if int(n_hyp) == 0 and prior is None:
+            refuse("n_hyp = 0 needs a prior pose")
+        if not (np.isfinite(threshold_px) and threshold_px > 0):
+            refuse("threshold_px must be finite and > 0")
+        if (K[[1, 3, 6, 7]] != 0).any() or K[8] != 1 or not (np.isfinite(K[[0, 4, 2, 5]]).all() and K[0] > 0 and K[4] > 0):
+            refuse("the intrinsic matrix is not [[fx,0,cx],[0,fy,cy],[0,0,1]] with finite fx, fy > 0")
+        pR = pt = None
+        if prior is not None:
+            pR = np.ascontiguousarray(prior[0], dtype=np.float64).reshape(9)
+            pt = np.ascontiguousarray(prior[1], dtype=np.float64).reshape(3)
+        return X, obs, K, pR, pt
+
+    def _resect_info(self, info):
+        out = dict(zip(self.RESECT_INFO_KEYS, info.tolist()))
+        for k in ("valid", "winner_inliers", "winner_hypothesis", "winner_solution", "no_solution", "inliers", "accepted",
+                  "linearisations", "status"):
+            out[k] = int(out[k])
+        return out
+
+    def resect_camera(self, X, obs, K, prior=None, threshold_px=2.0, n_hyp=256, seed=0, min_inliers=6, max_iter=20):
+        """mocap_resect_camera: one camera's pose from 3-D points X [N][3] and its pixels obs [N][2] (rows with a NaN are skipped),
+        with the camera's own plain K -> (R [3][3], t [3], mask [N] bool, info dict).  prior: (R, t) or None; with one, hypothesis 0
+        is the prior.  max_iter = 0 refines nothing, n_hyp = 0 searches nothing: both evaluate the prior only."""
+        X, obs, K, pR, pt = self._resect_inputs(X, obs, K, prior, threshold_px, n_hyp, 0)
+        if int(min_inliers) < 4 or int(max_iter) < 0:
+            e = MocapError(f"mocap_core error {MOCAP_E_ARG}: camera resection: min_inliers must be at least 4, max_iter >= 0")
+            e.code = MOCAP_E_ARG
+            raise e
+        N = X.shape[0]
+        R, t, mask, info = np.zeros(9), np.zeros(3), np.zeros(N, dtype=np.uint8), np.zeros(RESECT_INFO)
+        self._check(self.lib.mocap_resect_camera(self._h, N, _p(X), _p(obs), _p(K), _p(pR), _p(pt), float(threshold_px), int(n_hyp),
+                                                 int(seed), int(min_inliers), int(max_iter), _p(R), _p(t), _p(mask), _p(info)))
+        return R.reshape(3, 3), t, mask.astype(bool), self._resect_info(info)
+
+    def resect_camera_dev(self, N, d_X, d_obs, K, prior=None, threshold_px=2.0, n_hyp=256, seed=0, min_inliers=6, max_iter=20):
+        """mocap_resect_camera_dev: resect_camera with X [N][3] and obs [N][2] as device pointers, on the context's stream."""
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        pR = pt = None
+        if prior is not None:
+            pR = np.ascontiguousarray(prior[0], dtype=np.float64).reshape(9)
+            pt = np.ascontiguousarray(prior[1], dtype=np.float64).reshape(3)
+        R, t, mask, info = np.zeros(9), np.zeros(3), np.zeros(int(N), dtype=np.uint8), np.zeros(RESECT_INFO)
+        self._check(self.lib.mocap_resect_camera_dev(self._h, int(N), _vp(d_X), _vp(d_obs), _p(K), _p(pR), _p(pt), float(threshold_px),
+                                                     int(n_hyp), int(seed), int(min_inliers), int(max_iter), _p(R), _p(t), _p(mask),
+                                                     _p(info)))
+        return R.reshape(3, 3), t, mask.astype(bool), self._resect_info(info)
+
+    def resect_hypotheses(self, X, obs, K, prior=None, threshold_px=2.0, n_hyp=256, seed=0):
+        """mocap_resect_hypotheses: the candidate table of resect_camera's search -> {"sample" [H][3] input rows (-1: none), "n_sol"
+        [H], "poses" [H][4][12] (R | t, NaN where there is no solution), "counts" [H][4]}."""
+        X, obs, K, pR, pt = self._resect_inputs(X, obs, K, prior, threshold_px, n_hyp, 1)
+        H = int(n_hyp)
+        sample, n_sol = np.zeros((H, 3), dtype=np.int32), np.zeros(H, dtype=np.int32)
+        poses, counts = np.zeros((H, 4, 12)), np.zeros((H, 4), dtype=np.int32)
+        self._check(self.lib.mocap_resect_hypotheses(self._h, X.shape[0], _p(X), _p(obs), _p(K), _p(pR), _p(pt), float(threshold_px), H,
+                                                     int(seed), _p(sample), _p(n_sol), _p(poses), _p(counts)))
+        return {"sample": sample, "n_sol": n_sol, "poses": poses, "counts": counts}

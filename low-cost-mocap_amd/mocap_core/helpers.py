@@ -924,6 +924,88 @@ def calculate_camera_pose(data, socketio):
     return camera_poses, error
 
 
+# ----------------------------------------------------------------------------- camera resection (one camera re-seated)
+def _resection_inputs(image_points, camera_poses, camera):
+    """One camera against the rig's own points: the capture's points triangulated and refined WITHOUT that camera (its column
+    blanked: every point needs two other cameras), and where the camera saw them -> (core, X [N][3] NaN for no point, obs [N][2],
+    K [3][3], prior (R, t) or None).  Caller holds the lock."""
+    C = len(camera_poses)
+    if C < 3:
+        raise ValueError("camera resection needs at least 3 cameras: the points must come from two others")
+    if not 0 <= int(camera) < C:
+        raise IndexError("camera index out of range")
+    camera = int(camera)
+    has_pose = camera_poses[camera] is not None
+    poses = list(camera_poses)
+    if not has_pose:
+        poses[camera] = {"R": np.eye(3), "t": np.zeros(3)}    # its column is blanked: the placeholder is never used
+    obs = _obs_array(image_points, C)
+    if obs.shape[0] == 0:
+        raise ValueError("camera resection needs a capture: image_points is empty")
+    blanked = obs.copy()
+    blanked[:, camera] = np.nan
+    core = _upload_cameras(poses)
+    X, _, _ = core.triangulate_refined(blanked, iters=_state["refine"] or 4)
+    R, t = _pose_arrays(poses)
+    return core, X, obs[:, camera].copy(), _intrinsics(C)[camera], ((R[camera], t[camera]) if has_pose else None)
+
+
+def reseat_camera(image_points, camera_poses, camera, threshold_px=2.0, n_hyp=256, seed=0, min_inliers=6, max_iter=20):
+    """Re-seat ONE camera of a calibrated rig -- it was knocked, or it is new -- from a capture (`capture-points` payload,
+    [N][C][2] with None for unseen), keeping the rig's scale, frame and world transform (mocap_resect_camera, include/mocap_core.h
+    "camera resection"): the 3-D points are the capture's points built WITHOUT that camera (triangulate_points_refined with its
+    column blanked, so C >= 3), its pose in camera_poses -- None for a new camera -- is the prior, its intrinsic matrix the one from
+    set_camera_params.
+
+    Returns (camera_poses, report): the pose list with that camera replaced, and the solver's info fields by name plus "camera" and
+    "R", "t" (the resected pose in the frame the poses came in).
+    When the status is not capi.RESECT_OK the poses come back as they were.  Camera 0 defines the rig's frame: the result is
+    re-gauged so that it stays (I, 0) -- with (R0, t0) its resected pose in the old frame every camera becomes R_c R0^T,
+    t_c - R_c R0^T t0 -- and report["to_world_right"] is the 4 x 4 matrix to right-multiply onto to_world_coords_matrix so that
+    world coordinates do not move (D R0^T D | -D R0^T t0 with D = diag(-1, -1, 1) of set_to_world_coords_matrix's convention)."""
+    with _state["lock"]:
+        core, X, obs, K, prior = _resection_inputs(image_points, camera_poses, camera)
+        R, t, _, info = core.resect_camera(X, obs, K, prior=prior, threshold_px=threshold_px, n_hyp=n_hyp, seed=seed,
+                                           min_inliers=min_inliers, max_iter=max_iter)
+    camera = int(camera)
+    report = dict(info, camera=camera, R=R, t=t)        # the resected pose in the frame the poses came in
+    poses =[None if p is None else {"R": np.array(p["R"], dtype=np.float64).reshape(3, 3), "t": np.array(p["t"], dtype=np.float64).reshape(3)}
+             for p in camera_poses]
+    if info["status"] != capi.RESECT_OK:
+        return poses, report
+    if camera != 0:
+        poses[camera] = {"R": R, "t": t}
+        return poses, report
+    for c in range(1, len(poses)):
+        Rc = poses[c]["R"] @ R.T
+        poses[c] = {"R": Rc, "t": poses[c]["t"] - Rc @ t}
+    poses[0] = {"R": np.eye(3), "t": np.zeros(3)}
+    D = np.diag([-1.0, -1.0, 1.0])
+    M = np.eye(4)
+    M[:3, :3] = D @ R.T @ D
+    M[:3, 3] = -D @ R.T @ t
+    report["to_world_right"] = M
+    return poses, report
+
+
+def camera_health(image_points, camera_poses, threshold_px=2.0):
+    """Which camera was knocked?  Every camera's reprojection error against points built WITHOUT it (the evaluate-only mode of
+    mocap_resect_camera: nothing is searched or refined).  Returns one dict per camera: "rms" (pixels, over all its views of such
+    points that lie in front of it), "inlier_share" (views within threshold_px) and "views".  The camera with the largest rms is
+    the one to hand to reseat_camera."""
+    out = []
+    with _state["lock"]:
+        for c in range(len(camera_poses)):
+            core, X, obs, K, prior = _resection_inputs(image_points, camera_poses, c)
+            if prior is None:
+                raise ValueError("camera_health needs a pose for every camera")
+            _, _, _, near = core.resect_camera(X, obs, K, prior=prior, threshold_px=threshold_px, n_hyp=0, min_inliers=4, max_iter=0)
+            _, _, _, wide = core.resect_camera(X, obs, K, prior=prior, threshold_px=1e9, n_hyp=0, min_inliers=4, max_iter=0)
+            out.append({"rms": wide["rms_final"], "inlier_share": near["inliers"] / near["valid"] if near["valid"] else 0.0,
+                        "views": near["valid"]})
+    return out
+
+
 # ----------------------------------------------------------------------------- calibration tail (scale, floor, origin)
 def _pack_object_points(object_points):
     """The UI's ragged objectPoints (per frame a list of [x, y, z]) -> (xyz [F][K_max][3] NaN-padded, n_pts [F])."""
