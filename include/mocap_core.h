@@ -1102,8 +1102,11 @@ int mocap_ba_solve(mocap_ctx* ctx, double* x, int64_t N, const double* obs, doub
 /* mocap_ba_solve_ex: the same solve; `info_len` = doubles the caller's `info` holds, min(info_len,
  * MOCAP_BA_INFO_DOUBLES) are written: the 8 above, then [8] njev (= 1 + accepted steps, scipy's count), [9] number of
  * linearisations that had to be launched a second time because the kernel launched ahead of the host's decision had
- * abandoned itself (device watchdog, 2 s: the host was held up between two iterations; 0 in normal operation). */
-#define MOCAP_BA_INFO_DOUBLES 10
+ * abandoned itself (device watchdog, 2 s: the host was held up between two iterations; 0 in normal operation), [10] base
+ * points handed over to a kernel that was launched ahead of them (0: every linearisation got its point by value -- a
+ * rig or point count outside the launch-ahead's range, MOCAP_BA_NO_PREARM, or the chain schedule), [11] 1 when the
+ * one-launch linearisation kernel ran, 0 for the chain of five launches. */
+#define MOCAP_BA_INFO_DOUBLES 12
 int mocap_ba_solve_ex(mocap_ctx* ctx, double* x, int64_t N, const double* obs, double ftol, double xtol,
                       double gtol, int max_iter, int f32_residuals, int use_cauchy, double* info, int info_len);
 

@@ -42,6 +42,7 @@ constexpr double kEps = 2.220446049250313e-16;
 void sym_eig(int n, std::vector<double>& A, std::vector<double>& V, std::vector<double>& d) {
   V = A;
   d.assign(n, 0.0);
+  if (n == 0) return;  // no live parameter (J^T J all zero): the code below writes V[n-1][n-1] and e[0]
   std::vector<double> e(n, 0.0);
   auto v = [&](int i, int j) -> double& { return V[(size_t)i * n + j]; };
   // ---- tridiagonalisation
@@ -1094,6 +1095,8 @@ static int ba_solve_impl(mocap_ctx* ctx, double* x, int64_t N, const double* obs
     info[7] = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
     info[8] = njev;
     info[9] = w.prof_relaunches;
+    info[10] = w.handovers;
+    info[11] = w.fused ? 1.0 : 0.0;
   }
   return termination ? MOCAP_OK : MOCAP_E_NOCONV;
 }

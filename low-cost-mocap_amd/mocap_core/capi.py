@@ -1237,11 +1237,12 @@ class MocapCore:
                  use_cauchy=True):
         x = np.array(x0, dtype=np.float64)
         obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, self.C, 2)
-        info = np.zeros(10)
+        info = np.zeros(12)
         rc = self._check(self.lib.mocap_ba_solve_ex(self._h, _p(x), obs.shape[0], _p(obs), float(ftol), float(xtol),
                                                     float(gtol), int(max_iter), int(f32_residuals), int(use_cauchy),
                                                     _p(info), info.size), allow=(MOCAP_E_NOCONV,))
-        keys = ("iterations", "nfev", "status", "cost0", "cost", "optimality", "m", "elapsed_ms", "njev", "relaunches")
+        keys = ("iterations", "nfev", "status", "cost0", "cost", "optimality", "m", "elapsed_ms", "njev", "relaunches",
+                "handovers", "fused")
         return x, dict(zip(keys, info.tolist()), converged=(rc == MOCAP_OK))
 
     # ------------------------------------------------------------------ joint bundle adjustment (poses and points together)
