@@ -774,6 +774,78 @@ int mocap_learn_rigid_body_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, cons
                                const int32_t* d_id, const int32_t* d_status, int N, const int32_t* sel, int64_t ref_frame,
                                int iters, double max_rms, double* d_result);
 
+/* ---------------------------------------------------------------- trajectories (the core's own contract)
+ * A recorded session as one time series per marker: the frame-major cloud xyz [F][K_max][3] with the marker tracker's id [F][K_max]
+ * gathered into rows, then each row smoothed, short occlusions filled, and velocity and acceleration given beside the position.  Two
+ * stages, each with a host and a "_dev" form.  Not a stage of the live loop: with nothing called nothing changes.
+ *
+ * mocap_gather_tracks[_dev]: traj [R][F][3], time contiguous within a row.
+ *   relabel [n_ids] i32: the row of id i; a value outside 0 .. R-1 (-1 by convention) = the id has no row.  Two ids may share a row.
+ *   traj[r][f] = xyz[f][j] of the LOWEST slot j < n_pts[f] with 0 <= id[f][j] < n_ids, relabel[id[f][j]] == r,
+ *   hits[f][j] >= min_hits (when hits is not NULL) and three finite coordinates; no such slot: three NaN.  n_pts[f] outside
+ *   0 .. K_max counts as 0 (the "no valid slot" rule).  Every byte of traj is written.  One lane per frame, no atomics.
+ *   MOCAP_E_ARG, traj untouched, for: n_frames < 1; K_max outside 1 .. 64; R outside 1 .. MOCAP_TS_MAX_ROWS; R * n_frames > 2^31;
+ *   n_ids < 1; a null buffer (hits may be NULL).  In the "_dev" form every array, relabel included, is device-accessible.
+ *
+ * mocap_smooth_tracks[_dev]: t [F], traj [R][F][3] (any such table, e.g. a tracked body's t_pose per body) -> pos, vel, acc
+ * [R][F][3], res [R][F] f64, n_used, flag [R][F] i32: a local polynomial of degree d per output sample, by least squares.
+ *   d        1, 2 or 3                                    W      half window in frames, 1 .. MOCAP_TS_MAX_HALF_WINDOW
+ *   span     seconds, > 0; +inf = none                     n_min  d + 1 .. 2 W + 1: samples a fit needs
+ *   max_gap  0 .. W: the longest run of missing frames that is filled; 0 = fill nothing
+ *   MOCAP_E_ARG, every output untouched, for a value outside these, n_frames < 1, R outside 1 .. MOCAP_TS_MAX_ROWS,
+ *   R * n_frames > 2^31 or a null buffer.  The host form also rejects a t with no finite entry.
+ * All arithmetic is IEEE double, no fused operation, in the order written here; / and sqrt are correctly rounded.
+ *   Good time.  Frame f has a good time iff t_f is finite and t_f > the maximum of the finite t_g, g < f (the maximum of nothing is
+ *     -inf): a function of t alone.  The good times increase strictly.
+ *   Present.  (r, f) is present iff f has a good time and traj[r][f] is three finite values.
+ *   Samples of (r, f), f with a good time: the present frames g of row r with |g - f| <= W and |s_g| <= span, s_g = t_g - t_f;
+ *     n is their number.
+ *   Fillable.  (r, f) is fillable iff it is not present, max_gap > 0, the nearest present frames a < f < b of the row both exist,
+ *     b - a - 1 <= max_gap, and a and b are both samples of (r, f).  (max_gap <= W puts both inside the frame window: a fill is
+ *     never an extrapolation.)
+ *   flag and n_used, the first rule that applies:
+ *     f has no good time             flag = MOCAP_TS_BAD_TIME, n_used = 0
+ *     neither present nor fillable   flag = 0, n_used = n
+ *     n < n_min                      flag = MOCAP_TS_FEW, n_used = n
+ *     a pivot of the fit fails       flag = MOCAP_TS_SINGULAR, n_used = n
+ *     otherwise                      flag = MOCAP_TS_SMOOTHED (present) or MOCAP_TS_FILLED (fillable), n_used = n
+ *     Only the last rule makes an output; under every other pos, vel, acc and res are NaN.  Every byte of every output is written.
+ *   Fit.  h = max |s_g| over the samples (> 0: n >= 2 and good times differ); u_g = s_g / h; p_0 = 1, p_i = p_(i-1) * u_g;
+ *     S_i = sum_g p_i for i <= 2 d; B_i[k] = sum_g (p_i * x_g[k]) for i <= d, x_g = traj[r][g]; every sum starts from 0 and takes
+ *     the samples in ascending g.  A_ij = S_(i+j), i, j <= d.  Cholesky A = L L^T row by row: for i = 0 .. d, for j = 0 .. i:
+ *     s = A_ij, then s = s - L_ik * L_jk for k = 0 .. j-1 in turn; j < i: L_ij = s / L_jj; j = i: the pivot s fails unless it is
+ *     finite and > 0, L_ii = sqrt(s).  Per coordinate k: forwards y_i = (B_i[k] - L_i0 * y_0 - ... - L_i,i-1 * y_(i-1)) / L_ii, the
+ *     products subtracted in turn, i = 0 .. d; backwards c_i = (y_i - L_(i+1)i * c_(i+1) - ... - L_di * c_d) / L_ii, likewise,
+ *     i = d .. 0.
+ *   Results.  pos = c_0; vel = c_1 / h; acc = ((2 * c_2) / h) / h for d >= 2, NaN for d = 1;
+ *     res = sqrt(ss / (3 n)), ss = the sum from 0, over the samples in ascending g and then k = 0, 1, 2, of e * e,
+ *     e = x_g[k] - q, q = c_d, then q = q * u_g + c_i for i = d-1 .. 0 (Horner; product, then sum).
+ * Two calls on the same input give the same bytes; the host form and the "_dev" form give the same bytes.  One workgroup of 256
+ * lanes per 256 consecutive frames of a row (grid ceil(F / 256) x R) stages its tile and a halo of W frames in LDS; the good-time
+ * bits come from a prefix maximum over t in three small launches.  No atomics.  The "_dev" forms enqueue on the context's stream;
+ * the host forms upload, run and download.
+ * Out of scope: stitching the fragments of one marker that got several ids (relabel is its seam: give them one row), smoothing of
+ * rotations, a fixed-lag or streaming form, weighted windows, outlier rejection, more than 1024 rows or a half window above 32. */
+#define MOCAP_TS_MAX_ROWS 1024
+#define MOCAP_TS_MAX_HALF_WINDOW 32
+enum {
+  MOCAP_TS_SMOOTHED = 1,  /* the sample was present and is the fit's value at its own time */
+  MOCAP_TS_FILLED = 2,    /* the sample was missing inside a gap of at most max_gap frames: the fit's value */
+  MOCAP_TS_FEW = 4,       /* fewer than n_min samples in the window: no output */
+  MOCAP_TS_SINGULAR = 8,  /* a Cholesky pivot was not finite or not > 0: no output */
+  MOCAP_TS_BAD_TIME = 16  /* the frame's time stamp is not finite or does not exceed every earlier one: no output */
+};
+int mocap_gather_tracks(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int32_t* n_pts, const int32_t* id,
+                        const int32_t* hits, int min_hits, int n_ids, const int32_t* relabel, int R, double* traj);
+int mocap_gather_tracks_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int32_t* d_n_pts,
+                            const int32_t* d_id, const int32_t* d_hits, int min_hits, int n_ids, const int32_t* d_relabel, int R,
+                            double* d_traj);
+int mocap_smooth_tracks(mocap_ctx* ctx, int64_t n_frames, int R, const double* t, const double* traj, int degree, int W, double span,
+                        int n_min, int max_gap, double* pos, double* vel, double* acc, double* res, int32_t* n_used, int32_t* flag);
+int mocap_smooth_tracks_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_t, const double* d_traj, int degree, int W,
+                            double span, int n_min, int max_gap, double* d_pos, double* d_vel, double* d_acc, double* d_res,
+                            int32_t* d_n_used, int32_t* d_flag);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

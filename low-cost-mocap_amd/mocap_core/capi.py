@@ -55,6 +55,8 @@ RF_STEPS_SHIFT = 8        # ... and the accepted steps, info >> 8
 LB_RESULT = 129           # mocap_learn_rigid_body: doubles of its `result`
 LB_ST_NO_REF = 1          # ... status flags: no valid frame shows every selected marker (or the given ref_frame does not)
 LB_ST_MARKER_UNSEEN = 2   # ... a marker had no used frame in some round and kept its previous position
+TS_MAX_ROWS, TS_MAX_HALF_WINDOW = 1024, 32   # mocap_gather_tracks / mocap_smooth_tracks: rows, half window in frames
+TS_SMOOTHED, TS_FILLED, TS_FEW, TS_SINGULAR, TS_BAD_TIME = 1, 2, 4, 8, 16   # ... a sample's flag (include/mocap_core.h)
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -132,6 +134,10 @@ SIGNATURES = {
                                                     _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_learn_rigid_body": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _dbl, _vp]),
     "mocap_learn_rigid_body_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _dbl, _vp]),
+    "mocap_gather_tracks": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "mocap_gather_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "mocap_smooth_tracks": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_smooth_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -826,6 +832,48 @@ class MocapCore:
         self._check(self.lib.mocap_learn_rigid_body_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_n_pts), _vp(d_id),
                                                         _vp(d_status or 0), sel.size, _p(sel), int(ref_frame), int(iters),
                                                         float(max_rms), _vp(d_result)))
+
+    # ------------------------------------------------------------------ trajectories (a session as one time series per marker)
+    def gather_tracks(self, xyz, n_pts, ids, relabel, R, hits=None, min_hits=0):
+        """mocap_gather_tracks over host arrays xyz [F][K_max][3] (K_max <= 64), n_pts [F], ids [F][K_max] (the marker tracker's),
+        hits [F][K_max] or None; relabel [n_ids]: the row of each id, -1 = none -> traj [R][F][3], NaN where a row has no point."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        F, K_max, _ = xyz.shape
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(F, K_max)
+        hits = None if hits is None else np.ascontiguousarray(hits, dtype=np.int32).reshape(F, K_max)
+        relabel = np.ascontiguousarray(relabel, dtype=np.int32).reshape(-1)
+        traj = np.zeros((max(int(R), 0), F, 3))
+        self._check(self.lib.mocap_gather_tracks(self._h, F, K_max, _p(xyz), _p(n_pts), _p(ids), _p(hits), int(min_hits), relabel.size,
+                                                 _p(relabel), int(R), _p(traj)))
+        return traj
+
+    def gather_tracks_dev(self, n_frames, K_max, d_xyz, d_n_pts, d_id, d_hits, min_hits, n_ids, d_relabel, R, d_traj):
+        """Device pointers (ints; d_hits may be 0); d_relabel: device-accessible int32[n_ids]; d_traj: double[R][F][3]."""
+        self._check(self.lib.mocap_gather_tracks_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_n_pts), _vp(d_id),
+                                                     _vp(d_hits or 0), int(min_hits), int(n_ids), _vp(d_relabel), int(R), _vp(d_traj)))
+
+    def smooth_tracks(self, t, traj, degree=2, W=8, span=float("inf"), n_min=None, max_gap=0):
+        """mocap_smooth_tracks over host arrays t [F], traj [R][F][3] -> {"pos", "vel", "acc" [R][F][3], "res" [R][F], "n_used",
+        "flag" int32 [R][F] (TS_* values)}: a local polynomial of `degree` over the present samples within W frames and `span`
+        seconds of each sample; gaps of at most max_gap frames are filled.  n_min: samples a fit needs, default degree + 2
+        (capped at 2 W + 1)."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        R, F, _ = traj.shape
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+        o = {"pos": np.zeros((R, F, 3)), "vel": np.zeros((R, F, 3)), "acc": np.zeros((R, F, 3)), "res": np.zeros((R, F)),
+             "n_used": np.zeros((R, F), dtype=np.int32), "flag": np.zeros((R, F), dtype=np.int32)}
+        self._check(self.lib.mocap_smooth_tracks(self._h, F, R, _p(t), _p(traj), int(degree), int(W), float(span), n_min, int(max_gap),
+                                                 *[_p(o[k]) for k in ("pos", "vel", "acc", "res", "n_used", "flag")]))
+        return o
+
+    def smooth_tracks_dev(self, n_frames, R, d_t, d_traj, degree, W, span, n_min, max_gap, d_pos, d_vel, d_acc, d_res, d_n_used,
+                          d_flag):
+        """Device pointers (ints), shapes as smooth_tracks."""
+        self._check(self.lib.mocap_smooth_tracks_dev(self._h, int(n_frames), int(R), _vp(d_t), _vp(d_traj), int(degree), int(W),
+                                                     float(span), int(n_min), int(max_gap), _vp(d_pos), _vp(d_vel), _vp(d_acc),
+                                                     _vp(d_res), _vp(d_n_used), _vp(d_flag)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

@@ -587,6 +587,68 @@ def learn_rigid_body(capture, sel=None, name="body", **kw):
     return learned
 
 
+def track_table(ids, hits=None, min_len=10, min_hits=0):
+    """Which track ids of a session get a trajectory row (plain NumPy, on the host).  ids [F][K_max] as the marker tracker writes
+    them (-1 = no track), hits [F][K_max] or None: a sighting counts when its id is >= 0 and, with hits given, its hits >= min_hits.
+    Returns (relabel int32 [n_ids], rows int32 [R]): the ids with at least min_len sightings in ascending order, rows[r] = the id of
+    row r, relabel[i] = the row of id i or -1 -- what mocap_gather_tracks takes.  n_ids = the largest id seen + 1 (1 for none)."""
+    ids = np.asarray(ids)
+    seen = ids >= 0
+    if hits is not None:
+        seen &= np.asarray(hits) >= min_hits
+    counts = np.bincount(ids[seen].astype(np.int64).ravel(), minlength=1)
+    rows = np.nonzero(counts >= max(int(min_len), 1))[0].astype(np.int32)
+    relabel = np.full(counts.size, -1, dtype=np.int32)
+    relabel[rows] = np.arange(rows.size, dtype=np.int32)
+    return relabel, rows
+
+
+def session_trajectories(t, xyz, n_pts, ids, hits=None, min_hits=0, min_len=10, degree=2, W=8, span=float("inf"), n_min=None,
+                         max_gap=0):
+    """A recorded session as one smoothed, gap-filled time series per marker ("trajectories", include/mocap_core.h): track_table ->
+    mocap_gather_tracks -> mocap_smooth_tracks.  t [F], xyz [F][K_max][3], n_pts [F] (the frame path's), ids, hits [F][K_max] (the
+    marker tracker's), as NumPy arrays or as torch tensors on the core's GPU (those are read in place: only ids and hits are copied to
+    the host, for the table, and the results stay resident as torch tensors).  Returns {"ids" [R] the track id of each row, "relabel",
+    "traj", "pos", "vel", "acc" [R][F][3], "res", "n_used", "flag" [R][F]}.  No id with min_len sightings raises ValueError; more than
+    capi.TS_MAX_ROWS of them is the core's MOCAP_E_ARG."""
+    resident = getattr(xyz, "is_cuda", False)
+    host = (lambda a: None if a is None else a.cpu().numpy()) if resident else (lambda a: None if a is None else np.asarray(a))
+    relabel, rows = track_table(host(ids), host(hits), min_len=min_len, min_hits=min_hits)
+    R = int(rows.size)
+    if R == 0:
+        raise ValueError(f"session_trajectories: no track id has {min_len} sightings in this session")
+    n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            traj = core.gather_tracks(xyz, n_pts, ids, relabel, R, hits=hits, min_hits=min_hits)
+            out = core.smooth_tracks(t, traj, degree=degree, W=W, span=span, n_min=n_min, max_gap=max_gap)
+        else:
+            import torch
+            F, K_max = xyz.shape[0], xyz.shape[1]
+            assert xyz.dtype == torch.float64 and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.is_cuda and t.numel() == F
+            assert n_pts.dtype == torch.int32 and n_pts.is_contiguous() and n_pts.is_cuda and n_pts.numel() == F
+            for a in (ids, hits):
+                assert a is None or (a.dtype == torch.int32 and a.is_contiguous() and a.is_cuda and tuple(a.shape) == (F, K_max))
+            if xyz.device.index != core.device_id:
+                raise ValueError(f"the session lives on {xyz.device}, the core on GPU {core.device_id}: a resident session is read in place")
+            dev = xyz.device
+            d_relabel = torch.from_numpy(relabel).to(dev)
+            traj = torch.empty((R, F, 3), dtype=torch.float64, device=dev)
+            out = {k: torch.empty((R, F, 3), dtype=torch.float64, device=dev) for k in ("pos", "vel", "acc")}
+            out["res"] = torch.empty((R, F), dtype=torch.float64, device=dev)
+            out["n_used"], out["flag"] = (torch.empty((R, F), dtype=torch.int32, device=dev) for _ in range(2))
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.gather_tracks_dev(F, K_max, xyz.data_ptr(), n_pts.data_ptr(), ids.data_ptr(), 0 if hits is None else hits.data_ptr(),
+                                   min_hits, relabel.size, d_relabel.data_ptr(), R, traj.data_ptr())
+            core.smooth_tracks_dev(F, R, t.data_ptr(), traj.data_ptr(), degree, W, span, n_min, max_gap,
+                                   *[out[k].data_ptr() for k in ("pos", "vel", "acc", "res", "n_used", "flag")])
+            core.synchronize()
+    out.update(ids=rows, relabel=relabel, traj=traj)
+    return out
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
