@@ -824,8 +824,9 @@ int mocap_learn_rigid_body_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, cons
  * lanes per 256 consecutive frames of a row (grid ceil(F / 256) x R) stages its tile and a halo of W frames in LDS; the good-time
  * bits come from a prefix maximum over t in three small launches.  No atomics.  The "_dev" forms enqueue on the context's stream;
  * the host forms upload, run and download.
- * Out of scope: stitching the fragments of one marker that got several ids (relabel is its seam: give them one row), smoothing of
- * rotations, a fixed-lag or streaming form, weighted windows, outlier rejection, more than 1024 rows or a half window above 32. */
+ * The fragments of one marker that got several ids are found by the next section, "track stitching" (relabel is its seam: it gives
+ * them one row).  Out of scope: smoothing of rotations, a fixed-lag or streaming form, weighted windows, outlier rejection, more
+ * than 1024 rows or a half window above 32. */
 #define MOCAP_TS_MAX_ROWS 1024
 #define MOCAP_TS_MAX_HALF_WINDOW 32
 enum {
@@ -845,6 +846,62 @@ int mocap_smooth_tracks(mocap_ctx* ctx, int64_t n_frames, int R, const double* t
 int mocap_smooth_tracks_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_t, const double* d_traj, int degree, int W,
                             double span, int n_min, int max_gap, double* d_pos, double* d_vel, double* d_acc, double* d_res,
                             int32_t* d_n_used, int32_t* d_flag);
+
+/* ---------------------------------------------------------------- track stitching (the core's own contract)
+ * Which rows of a gathered session are the same marker.  The marker tracker retires a track after max_missed unseen frames (marker
+ * tracker, step 5), so a marker hidden for longer comes back under a new id and mocap_gather_tracks gives it a second row, NaN where
+ * the first one lives.  This stage links such fragments into chains and numbers the chains; helpers.stitch_table turns that into
+ * the relabel of a second mocap_gather_tracks, which then writes one row per marker.  Opt-in: with nothing called nothing changes.
+ *
+ * mocap_stitch_tracks[_dev]: n_frames, R, t [F], traj [R][F][3] as mocap_gather_tracks writes and mocap_smooth_tracks reads them.
+ *   fit_frames  1 .. MOCAP_ST_MAX_FIT: frames at a fragment's end that feed its end model
+ *   max_dt      seconds, > 0; +inf allowed: the longest hidden time that is bridged
+ *   gate        metres, finite and > 0                  gate_rate  metres per second, finite and >= 0
+ *   MOCAP_E_ARG, every output untouched, for a value outside these, n_frames < 1, R outside 1 .. MOCAP_TS_MAX_ROWS,
+ *   R * n_frames > 2^31 or a null buffer.  The host form also rejects a t with no finite entry.
+ * Outputs, every byte written:
+ *   ext [R][3] i32   a_r, b_r, n_r: the first and the last present frame of row r and the number of present ones; -1, -1, 0 for an
+ *                    empty row
+ *   next, prev [R] i32   the linked successor and predecessor row, -1 = none
+ *   cost [R] f64     the cost of the link r -> next[r], NaN where none
+ *   chain [R] i32    the row at the head of r's chain (follow prev until it is -1); a row without links, an empty one included, is
+ *                    its own head.  An empty row is never linked.
+ *   row_of [R] i32   the number of r's chain, chains counted 0, 1, ... in ascending order of their head row; -1 for an empty row
+ *   n_chains i32     (one value) the number of chains of non-empty rows
+ * All arithmetic is IEEE double, no fused operation, in the order written here; / is correctly rounded; there is no sqrt.
+ *   Good time, present.  As in "trajectories": a function of t, and of t and traj[r][f].
+ *   Extent.  a_r = the smallest, b_r = the largest present frame of row r, n_r their number.
+ *   End models.  Row r, n_r > 0, has a tail model at frame e = b_r over the window lo = max(b_r - fit_frames, 0) .. b_r, and a head
+ *     model at e = a_r over a_r .. min(a_r + fit_frames, n_frames - 1).  Samples: the present frames g of the row inside the window
+ *     (e is one); m their number; s_g = t_g - t_e; h = the largest |s_g|, found in ascending g from 0.  With m >= 2: u_g = s_g / h;
+ *     S0 = sum 1, S1 = sum u_g, S2 = sum (u_g * u_g), B0[k] = sum x_g[k], B1[k] = sum (u_g * x_g[k]), x_g = traj[r][g], every sum from
+ *     0 in ascending g; det = S0 * S2 - S1 * S1 (two products, then the difference).  If det is finite and > 0:
+ *       pos[k] = (S2 * B0[k] - S1 * B1[k]) / det         (the line's value at t_e, where u = 0)
+ *       vel[k] = ((S0 * B1[k] - S1 * B0[k]) / det) / h
+ *     With m < 2, or a det that is not finite or not > 0: pos = x_e, vel = 0.  The model's time is t_e.
+ *   Pair (p -> q), p != q, n_p > 0, n_q > 0, T = the tail model of p, H = the head model of q.  dt = t_(a_q) - t_(b_p);
+ *     g = gate + gate_rate * dt; g2 = g * g; for k = 0, 1, 2:
+ *       d_k = H.pos[k] - (T.pos[k] + T.vel[k] * dt)      (where the tail expects the head)
+ *       e_k = T.pos[k] - (H.pos[k] - H.vel[k] * dt)      (where the head expects the tail)
+ *     d2 = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2, e2 likewise; c = 0.5 * (d2 + e2).  The pair is admissible iff b_p < a_q (strictly
+ *     later, never overlapping), dt <= max_dt and c < g2 (false for a NaN on either side).
+ *   Association.  The admissible pairs are taken in ascending lexicographic order of (c, p, q); a pair is committed iff p has no
+ *     successor yet and q has no predecessor yet: next[p] = q, prev[q] = p, cost[p] = c.  This is the marker tracker's greedy
+ *     global nearest neighbour over fragments, and a function of the input alone (the device commits mutually best pairs in
+ *     rounds, which gives the same links under this total order).  Links run forward in frames: no chain closes into a cycle.
+ *   Chains.  chain[r]: follow prev from r until it is -1.  row_of and n_chains as above.
+ * Two calls on the same input give the same bytes; the host form and the "_dev" form give the same bytes.  Extents are combined
+ * with 32-bit integer atomics (order-independent); there are no floating-point atomics.  The "_dev" form enqueues on the context's
+ * stream (every pointer device-accessible); the host form uploads, runs and downloads.
+ * Out of scope: a minimum-cost (Hungarian or min-cost-flow) assignment instead of the greedy one; splitting a track that swapped
+ * markers; rigid-body geometry as a cue; overlapping fragments (twins: point consolidation handles those); a streaming form. */
+#define MOCAP_ST_MAX_FIT 64
+int mocap_stitch_tracks(mocap_ctx* ctx, int64_t n_frames, int R, const double* t, const double* traj, int fit_frames, double max_dt,
+                        double gate, double gate_rate, int32_t* ext, int32_t* next, int32_t* prev, double* cost, int32_t* chain,
+                        int32_t* row_of, int32_t* n_chains);
+int mocap_stitch_tracks_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_t, const double* d_traj, int fit_frames,
+                            double max_dt, double gate, double gate_rate, int32_t* d_ext, int32_t* d_next, int32_t* d_prev,
+                            double* d_cost, int32_t* d_chain, int32_t* d_row_of, int32_t* d_n_chains);
 
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,

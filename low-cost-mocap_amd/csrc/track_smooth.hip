@@ -283,16 +283,21 @@ hipError_t launch_gather_tracks(const GatherTracksArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_smooth_tracks(const SmoothTracksArgs& a, hipStream_t stream) {
+hipError_t launch_good_times(const SmoothTracksArgs& a, hipStream_t stream) {
   const int64_t P = ts_tiles(a.n_frames);
-  const dim3 tiles((unsigned)P), block(kT), one(1), grid((unsigned)P, (unsigned)a.R);
+  const dim3 tiles((unsigned)P), block(kT), one(1);
   hipError_t e;
   hipLaunchKernelGGL(ts_tile_max_kernel, tiles, block, 0, stream, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(ts_tile_scan_kernel, one, block, 0, stream, a, P);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(ts_good_kernel, tiles, block, 0, stream, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+hipError_t launch_smooth_tracks(const SmoothTracksArgs& a, hipStream_t stream) {
+  const dim3 block(kT), grid((unsigned)ts_tiles(a.n_frames), (unsigned)a.R);
+  if (hipError_t e = launch_good_times(a, stream)) return e;
   if (a.degree == 1) hipLaunchKernelGGL(ts_smooth_kernel<1>, grid, block, 0, stream, a);
   else if (a.degree == 2) hipLaunchKernelGGL(ts_smooth_kernel<2>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(ts_smooth_kernel<3>, grid, block, 0, stream, a);

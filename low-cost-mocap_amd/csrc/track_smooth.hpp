@@ -38,7 +38,9 @@ struct SmoothTracksArgs {
 
 // one launch: a lane per frame, every row of traj written
 hipError_t launch_gather_tracks(const GatherTracksArgs& a, hipStream_t stream);
-// four launches: the good-time bits of t (tile maxima, their prefix, the bits), then the fit
+// three launches: the good-time bits of t (tile maxima, their prefix, the bits); reads n_frames and t, writes tile_max and good
+hipError_t launch_good_times(const SmoothTracksArgs& a, hipStream_t stream);
+// four launches: the good-time bits, then the fit
 hipError_t launch_smooth_tracks(const SmoothTracksArgs& a, hipStream_t stream);
 
 }  // namespace mocap

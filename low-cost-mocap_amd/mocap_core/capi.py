@@ -57,6 +57,7 @@ LB_ST_NO_REF = 1          # ... status flags: no valid frame shows every selecte
 LB_ST_MARKER_UNSEEN = 2   # ... a marker had no used frame in some round and kept its previous position
 TS_MAX_ROWS, TS_MAX_HALF_WINDOW = 1024, 32   # mocap_gather_tracks / mocap_smooth_tracks: rows, half window in frames
 TS_SMOOTHED, TS_FILLED, TS_FEW, TS_SINGULAR, TS_BAD_TIME = 1, 2, 4, 8, 16   # ... a sample's flag (include/mocap_core.h)
+ST_MAX_FIT = 64           # mocap_stitch_tracks: frames of an end model's window at most
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -138,6 +139,8 @@ SIGNATURES = {
     "mocap_gather_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "mocap_smooth_tracks": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_smooth_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_stitch_tracks": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_stitch_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -874,6 +877,33 @@ class MocapCore:
         self._check(self.lib.mocap_smooth_tracks_dev(self._h, int(n_frames), int(R), _vp(d_t), _vp(d_traj), int(degree), int(W),
                                                      float(span), int(n_min), int(max_gap), _vp(d_pos), _vp(d_vel), _vp(d_acc),
                                                      _vp(d_res), _vp(d_n_used), _vp(d_flag)))
+
+    # ------------------------------------------------------------------ track stitching (the rows of one marker linked into a chain)
+    STITCH_OUT = ("ext", "next", "prev", "cost", "chain", "row_of", "n_chains")
+
+    def stitch_tracks(self, t, traj, fit_frames=8, max_dt=float("inf"), gate=0.05, gate_rate=0.0):
+        """mocap_stitch_tracks over host arrays t [F], traj [R][F][3] (gather_tracks') -> {"ext" int32 [R][3]: first and last present
+        frame and the number present (-1, -1, 0 for an empty row), "next", "prev" int32 [R]: the linked rows, -1 = none, "cost" [R]:
+        the cost of the link to next, NaN where none, "chain" int32 [R]: the head row of each row's chain, "row_of" int32 [R]: the
+        number of its chain, -1 for an empty row, "n_chains" int}.  A fragment's end is a line through the present samples of its
+        last (first) fit_frames + 1 frames; p -> q is linked when q starts after p ends, at most max_dt seconds later, and the two
+        extrapolations miss by less than gate + gate_rate * dt (symmetric mean square), cheapest pairs first."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        R, F, _ = traj.shape
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        o = {"ext": np.zeros((R, 3), dtype=np.int32), "cost": np.zeros(R), "n_chains": np.zeros(1, dtype=np.int32)}
+        o.update({k: np.zeros(R, dtype=np.int32) for k in ("next", "prev", "chain", "row_of")})
+        self._check(self.lib.mocap_stitch_tracks(self._h, F, R, _p(t), _p(traj), int(fit_frames), float(max_dt), float(gate),
+                                                 float(gate_rate), *[_p(o[k]) for k in self.STITCH_OUT]))
+        o["n_chains"] = int(o["n_chains"][0])
+        return o
+
+    def stitch_tracks_dev(self, n_frames, R, d_t, d_traj, fit_frames, max_dt, gate, gate_rate, d_ext, d_next, d_prev, d_cost, d_chain,
+                          d_row_of, d_n_chains):
+        """Device pointers (ints), shapes as stitch_tracks; d_n_chains: int32[1]."""
+        self._check(self.lib.mocap_stitch_tracks_dev(self._h, int(n_frames), int(R), _vp(d_t), _vp(d_traj), int(fit_frames),
+                                                     float(max_dt), float(gate), float(gate_rate), _vp(d_ext), _vp(d_next), _vp(d_prev),
+                                                     _vp(d_cost), _vp(d_chain), _vp(d_row_of), _vp(d_n_chains)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

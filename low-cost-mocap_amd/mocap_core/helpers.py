@@ -603,14 +603,49 @@ def track_table(ids, hits=None, min_len=10, min_hits=0):
     return relabel, rows
 
 
+def stitch_table(relabel, row_of):
+    """The relabel of the second gather (plain NumPy, on the host): relabel [n_ids] as track_table gives it, row_of [R] as
+    mocap_stitch_tracks gives it -> relabel2 int32 [n_ids], relabel2[i] = row_of[relabel[i]] where relabel[i] >= 0, else -1: every id
+    of a chain lands on the chain's one row, an id whose row was empty on none."""
+    relabel, row_of = np.asarray(relabel, dtype=np.int32), np.asarray(row_of, dtype=np.int32)
+    out = np.full(relabel.shape, -1, dtype=np.int32)
+    has = relabel >= 0
+    out[has] = row_of[relabel[has]]
+    return out
+
+
+def _stitch_report(rows, st, t_at):
+    """ids, links, fragments of a stitched session from the [R] outputs of mocap_stitch_tracks (host arrays); t_at(frames) -> the
+    time stamps of those frames."""
+    heads = [r for r in range(rows.size) if st["row_of"][r] >= 0 and st["chain"][r] == r]      # ascending: the order of row_of
+    ids, links = [], []
+    for r in heads:
+        chain = [r]
+        while st["next"][chain[-1]] >= 0:
+            chain.append(int(st["next"][chain[-1]]))
+        ids.append(rows[chain])
+        links += [(p, q) for p, q in zip(chain[:-1], chain[1:])]
+    if links:
+        p, q = np.array(links).T
+        dt = t_at(st["ext"][q, 0]) - t_at(st["ext"][p, 1])
+        links = [(int(rows[a]), int(rows[b]), float(st["cost"][a]), float(d)) for a, b, d in zip(p, q, dt)]
+    return ids, links, st["ext"]
+
+
 def session_trajectories(t, xyz, n_pts, ids, hits=None, min_hits=0, min_len=10, degree=2, W=8, span=float("inf"), n_min=None,
-                         max_gap=0):
+                         max_gap=0, stitch=None):
     """A recorded session as one smoothed, gap-filled time series per marker ("trajectories", include/mocap_core.h): track_table ->
     mocap_gather_tracks -> mocap_smooth_tracks.  t [F], xyz [F][K_max][3], n_pts [F] (the frame path's), ids, hits [F][K_max] (the
     marker tracker's), as NumPy arrays or as torch tensors on the core's GPU (those are read in place: only ids and hits are copied to
     the host, for the table, and the results stay resident as torch tensors).  Returns {"ids" [R] the track id of each row, "relabel",
     "traj", "pos", "vel", "acc" [R][F][3], "res", "n_used", "flag" [R][F]}.  No id with min_len sightings raises ValueError; more than
-    capi.TS_MAX_ROWS of them is the core's MOCAP_E_ARG."""
+    capi.TS_MAX_ROWS of them is the core's MOCAP_E_ARG.
+    stitch = {"fit_frames", "max_dt", "gate", "gate_rate"} ("track stitching", include/mocap_core.h): a marker that was hidden for
+    longer than the tracker's max_missed came back under a new id; the gathered rows go through mocap_stitch_tracks, stitch_table
+    maps every id of a chain to the chain's row, and a second gather with R = n_chains feeds the smoother: one row per marker.  Only
+    the [R] outputs of the stitching come to the host.  Then "ids" is a list of arrays, the track ids of each row in time order,
+    "relabel" the second gather's, and the dict gains "links": [(from id, to id, cost, dt seconds)] and "fragments": ext int32
+    [fragments][3] of the first gather's rows (first and last present frame, number present), in the order of track_table's rows."""
     resident = getattr(xyz, "is_cuda", False)
     host = (lambda a: None if a is None else a.cpu().numpy()) if resident else (lambda a: None if a is None else np.asarray(a))
     relabel, rows = track_table(host(ids), host(hits), min_len=min_len, min_hits=min_hits)
@@ -618,10 +653,25 @@ def session_trajectories(t, xyz, n_pts, ids, hits=None, min_hits=0, min_len=10, 
     if R == 0:
         raise ValueError(f"session_trajectories: no track id has {min_len} sightings in this session")
     n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+    report = None
+
+    def restitch(st, t_at):
+        """-> (the second gather's relabel, its R)"""
+        nonlocal report
+        if st["n_chains"] < 1:
+            raise ValueError("session_trajectories: no row of this session has a sample with a good time stamp")
+        report = _stitch_report(rows, st, t_at)
+        return stitch_table(relabel, st["row_of"]), int(st["n_chains"])
+
     with _state["lock"]:
         core = get_core()
         if not resident:
             traj = core.gather_tracks(xyz, n_pts, ids, relabel, R, hits=hits, min_hits=min_hits)
+            if stitch is not None:
+                t_host = np.asarray(t, dtype=np.float64).reshape(-1)
+                st = core.stitch_tracks(t, traj, stitch["fit_frames"], stitch["max_dt"], stitch["gate"], stitch["gate_rate"])
+                relabel, R = restitch(st, lambda f: t_host[f])
+                traj = core.gather_tracks(xyz, n_pts, ids, relabel, R, hits=hits, min_hits=min_hits)
             out = core.smooth_tracks(t, traj, degree=degree, W=W, span=span, n_min=n_min, max_gap=max_gap)
         else:
             import torch
@@ -634,18 +684,39 @@ def session_trajectories(t, xyz, n_pts, ids, hits=None, min_hits=0, min_len=10, 
             if xyz.device.index != core.device_id:
                 raise ValueError(f"the session lives on {xyz.device}, the core on GPU {core.device_id}: a resident session is read in place")
             dev = xyz.device
-            d_relabel = torch.from_numpy(relabel).to(dev)
-            traj = torch.empty((R, F, 3), dtype=torch.float64, device=dev)
+            tables = []                                           # device copies of relabel: alive until the last synchronize
+
+            def gather():
+                tables.append(torch.from_numpy(relabel).to(dev))
+                rows_dev = torch.empty((R, F, 3), dtype=torch.float64, device=dev)
+                torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+                core.gather_tracks_dev(F, K_max, xyz.data_ptr(), n_pts.data_ptr(), ids.data_ptr(), 0 if hits is None else hits.data_ptr(),
+                                       min_hits, relabel.size, tables[-1].data_ptr(), R, rows_dev.data_ptr())
+                return rows_dev
+
+            if stitch is not None:
+                traj = gather()
+                d = {"ext": torch.empty((R, 3), dtype=torch.int32, device=dev), "cost": torch.empty(R, dtype=torch.float64, device=dev),
+                     "n_chains": torch.empty(1, dtype=torch.int32, device=dev)}
+                d.update({k: torch.empty(R, dtype=torch.int32, device=dev) for k in ("next", "prev", "chain", "row_of")})
+                torch.cuda.current_stream(dev).synchronize()
+                core.stitch_tracks_dev(F, R, t.data_ptr(), traj.data_ptr(), stitch["fit_frames"], stitch["max_dt"], stitch["gate"],
+                                       stitch["gate_rate"], *[d[k].data_ptr() for k in core.STITCH_OUT])
+                core.synchronize()
+                st = {k: v.cpu().numpy() for k, v in d.items()}
+                st["n_chains"] = int(st["n_chains"][0])
+                relabel, R = restitch(st, lambda f: t[torch.from_numpy(np.asarray(f, dtype=np.int64)).to(dev)].cpu().numpy())
+            traj = gather()
             out = {k: torch.empty((R, F, 3), dtype=torch.float64, device=dev) for k in ("pos", "vel", "acc")}
             out["res"] = torch.empty((R, F), dtype=torch.float64, device=dev)
             out["n_used"], out["flag"] = (torch.empty((R, F), dtype=torch.int32, device=dev) for _ in range(2))
             torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
-            core.gather_tracks_dev(F, K_max, xyz.data_ptr(), n_pts.data_ptr(), ids.data_ptr(), 0 if hits is None else hits.data_ptr(),
-                                   min_hits, relabel.size, d_relabel.data_ptr(), R, traj.data_ptr())
             core.smooth_tracks_dev(F, R, t.data_ptr(), traj.data_ptr(), degree, W, span, n_min, max_gap,
                                    *[out[k].data_ptr() for k in ("pos", "vel", "acc", "res", "n_used", "flag")])
             core.synchronize()
     out.update(ids=rows, relabel=relabel, traj=traj)
+    if report is not None:
+        out.update(ids=report[0], links=report[1], fragments=report[2])
     return out
 
 
