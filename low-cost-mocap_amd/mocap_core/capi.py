@@ -1222,6 +1222,14 @@ class MocapCore:
                                                       _vp(d_corr), _vp(d_offsets), _vp(d_records or 0), int(capacity),
                                                       _vp(d_total or 0)))
 
+    def locate_objects_dev(self, n_frames, K_max, d_xyz, d_err, d_n_pts, O_max, d_pos, d_heading, d_error, d_drone, d_n_obj,
+                           d_lead=0):
+        """mocap_locate_objects_dev: device pointers in, device pointers out, enqueued on the core's stream.  Only the first
+        min(n_obj, O_max) object slots of a frame are written."""
+        self._check(self.lib.mocap_locate_objects_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_err), _vp(d_n_pts),
+                                                      int(O_max), _vp(d_pos), _vp(d_heading), _vp(d_error), _vp(d_drone),
+                                                      _vp(d_lead or 0), _vp(d_n_obj)))
+
     def triangulate_dev(self, N, d_obs, d_xyz, d_err):
         self._check(self.lib.mocap_triangulate_dev(self._h, int(N), _vp(d_obs), _vp(d_xyz), _vp(d_err or 0)))
 

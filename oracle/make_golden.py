@@ -305,6 +305,36 @@ def golden_post(name, n_frames, k_max, seed):
     print(name, "frames", n_frames, "objects", int(ref_nobj.sum()))
 
 
+def golden_locate_edges(name="locate_edges"):
+    """locate_objects (helpers.py:424-480) on the constructed frames of tests/locate_cases.py: frames on the function's decision
+    edges, shared and skipped points, members across the 64-point chunk edges, non-finite points, out-of-range counts (no valid
+    slot: the function sees an empty frame) and 12 dense-clutter frames.  Per family: the inputs and the reference's n_obj,
+    pos, heading, error and droneIndex (as many object slots as the family's fullest frame needs)."""
+    sys.path.insert(0, os.path.join(_ROOT, "tests"))
+    import locate_cases as lc
+    H = ref_harness.load_reference(4)
+    arrays, report = {}, []
+    for fam, cs, idx in lc.recorded():
+        xyz, err, n_pts = cs["xyz"][idx], cs["err"][idx], cs["n_pts"][idx]
+        n_eff = lc.effective_n(n_pts, err.shape[1])
+        with np.errstate(invalid="ignore"):      # inf - inf among the non-finite points
+            objs = [H.locate_objects(xyz[f, :n_eff[f]].copy(), err[f, :n_eff[f]].copy()) for f in range(len(idx))]
+        o_max = max(1, max(len(o) for o in objs))
+        ref_pos = np.full((len(idx), o_max, 3), np.nan)
+        ref_heading = np.full((len(idx), o_max), np.nan)
+        ref_error = np.full((len(idx), o_max), np.nan)
+        ref_drone = np.full((len(idx), o_max), -1, dtype=np.int32)
+        for f, fo in enumerate(objs):
+            for j, o in enumerate(fo):
+                ref_pos[f, j], ref_heading[f, j], ref_error[f, j], ref_drone[f, j] = o["pos"], o["heading"], o["error"], o["droneIndex"]
+        arrays.update({fam + "_frames": idx.astype(np.int32), fam + "_xyz": xyz, fam + "_err": err, fam + "_n_pts": n_pts,
+                       fam + "_ref_nobj": np.array([len(o) for o in objs], dtype=np.int32), fam + "_ref_pos": ref_pos,
+                       fam + "_ref_heading": ref_heading, fam + "_ref_error": ref_error, fam + "_ref_drone": ref_drone})
+        report.append(f"{fam} {len(idx)}/{sum(len(o) for o in objs)}")
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **arrays)
+    print(name, "frames/objects:", ", ".join(report))
+
+
 def golden_track(name, n_frames, seed):
     """The live loop's body after _find_dot, end to end through the reference's own code (helpers.py:94-108):
     find_point_correspondance_and_object_points -> the world-coordinate loop (exec'd from the file) -> locate_objects,
@@ -420,6 +450,8 @@ def main():
         return main_ba()
     if "--track-only" in sys.argv:
         return golden_track("track_apptsx_chain", 60, seed=19)
+    if "--locate-only" in sys.argv:
+        return golden_locate_edges()
     if "--with-cv2" in sys.argv:       # pin the OpenCV restatements against a REAL cv2, where one exists
         from oracle import make_cv2_golden
         return make_cv2_golden.main()
@@ -447,6 +479,8 @@ def main():
     main_ba()
     # the rows right after the path: world-coordinate epilogue + object locator
     golden_post("post_world_locate", 300, 24, seed=10)
+    # ... the locator again where its decisions flip and its searches change chunk
+    golden_locate_edges()
     # ... and the live loop's body end to end (match -> world -> locate) on the reference UI's own rig
     golden_track("track_apptsx_chain", 60, seed=19)
 

@@ -256,7 +256,8 @@ def locate_objects(object_points, errors):
     """helpers.py:424-480 restated with explicit loops: 3-LED patterns (two points 0.095 m from a lead
     point and 0.15 m from each other, +-0.025), first valid pair in row-major order wins
     (cartesian_product, helpers.py:532-533); only the lead point is checked against
-    `already_matched_points` (helpers.py:437).  Returns a list of dicts like the reference plus "lead"."""
+    `already_matched_points` (helpers.py:437).  Returns a list of dicts like the reference plus "lead" and "pair"
+    (the indices of the lead point and of the winning pair, in the pair's own order)."""
     P = np.asarray(object_points, dtype=np.float64).reshape(-1, 3)
     E = np.asarray(errors, dtype=np.float64).reshape(-1)
     K = P.shape[0]
@@ -288,7 +289,7 @@ def locate_objects(object_points, errors):
                 heading = heading + np.pi if heading < -np.pi / 2 else heading
                 drone_index = 0 if (P[i] - location)[1] > 0 else 1
                 objects.append({"pos": location, "heading": -heading, "error": error,
-                                "droneIndex": drone_index, "lead": i})
+                                "droneIndex": drone_index, "lead": i, "pair": (a, b)})
                 found = True
                 break
             if found:
