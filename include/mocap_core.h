@@ -903,6 +903,68 @@ int mocap_stitch_tracks_dev(mocap_ctx* ctx, int64_t n_frames, int R, const doubl
                             double max_dt, double gate, double gate_rate, int32_t* d_ext, int32_t* d_next, int32_t* d_prev,
                             double* d_cost, int32_t* d_chain, int32_t* d_row_of, int32_t* d_n_chains);
 
+/* ---------------------------------------------------------------- rigid groups (the core's own contract)
+ * Which rows of a gathered session keep their mutual distances: those rows are the markers of one rigid body.  The stage between
+ * the session pipeline (track markers, gather, stitch: one row per marker) and the rigid-body pipeline (learn, register, track),
+ * which so far started from a hand-typed list of track ids; helpers.find_rigid_groups and helpers.learn_session_bodies are the
+ * glue.  Opt-in: with nothing called nothing changes.
+ *
+ * mocap_rigid_groups[_dev]: n_frames, R, traj [R][F][3] as mocap_gather_tracks writes it.  No time stamps: rigidity does not depend
+ * on time.  A sample (r, f) is present iff traj[r][f] is three finite values.
+ *   min_common  >= 2: frames two rows must share (and a row must have) to be judged
+ *   tol         metres, finite and > 0: the largest standard deviation of a pair's distance that still counts as rigid
+ *   max_dist    metres, > 0; +inf allowed: the largest mean distance of an edge
+ *   min_travel  metres, finite and >= 0: the smallest bounding-box diagonal of a row that takes part
+ *   MOCAP_E_ARG, every output untouched, for a value outside these, n_frames outside 1 .. MOCAP_RG_MAX_FRAMES, R outside
+ *   1 .. MOCAP_RG_MAX_ROWS or a null buffer.
+ * Outputs, every byte written:
+ *   cnt [R][R] i32, dist, spread [R][R] f64   per pair, symmetric, the diagonal included: frames in common, mean and standard
+ *                                             deviation of the distance; NaN, NaN where cnt is 0
+ *   travel [R] f64                            the diagonal of the row's bounding box; NaN for an empty row
+ *   group_of [R] i32                          the row's group, -1 = none
+ *   gsize, ghead, gconf [R] i32, gspread [R] f64   per group g < n_groups: rows, lowest row, conflicts, largest spread over its
+ *                                             edges; -1, -1, -1, NaN for g >= n_groups
+ *   n_groups i32                              (one value)
+ * All arithmetic is IEEE double, no fused operation, in the order written here; / and sqrt are correctly rounded.
+ *   1. Pair statistics, for p <= q ([q][p] is the copy of [p][q]; the diagonal follows the same rule and gives dist = spread = 0):
+ *      over the frames f at which both rows are present, with dx = x_p - x_q, dy, dz likewise:
+ *        D_f = sqrt((dx * dx + dy * dy) + dz * dz)
+ *        cnt = the number of such frames;  dist = SUM(D) / cnt;  spread = sqrt(SUM((D - dist) * (D - dist)) / cnt), a second pass
+ *        over the same frames with the rounded dist; cnt = 0: dist = spread = NaN.
+ *   2. SUM is the project's reduction tree (csrc/tree_fold.hpp) over frames in tiles of 256: lane l of tile T carries frame
+ *      256 T + l; a frame that is absent for the pair or beyond n_frames carries +0.0.  Within each wave of 64 lanes, for
+ *      off = 32, 16, 8, 4, 2, 1 in turn: v[l] = v[l] + v[l + off] for l < off.  The tile's sum is ((w0 + w1) + w2) + w3 over the
+ *      v[0] of its four waves.  The P = ceil(n_frames / 256) tile sums are folded by 64 lanes: with c = ceil(P / 64), lane l starts
+ *      from 0.0 and adds the tile sums c l, c l + 1, ... below min(c l + c, P) in turn; then the same six halving steps; v[0] is SUM.
+ *      (How the device arrives at this association order is its own business -- it folds 64 pairs at once, transposed, and counts
+ *      from presence bits -- the bits are not.)
+ *   3. Travel.  Over the present samples of row r: e_k = max_k - min_k per axis (exact in any order);
+ *      travel = sqrt((e_0 * e_0 + e_1 * e_1) + e_2 * e_2); no present sample: NaN.
+ *   4. Row r is eligible iff cnt[r][r] >= min_common and travel[r] >= min_travel.  There is an edge p - q, p != q, iff both rows are
+ *      eligible, cnt[p][q] >= min_common, spread[p][q] <= tol and dist[p][q] <= max_dist.  A NaN fails every test.
+ *   5. Groups are the connected components of the edge graph with at least two rows, numbered 0, 1, ... by ascending lowest row.
+ *      gsize = its rows, ghead = its lowest row, gconf = the pairs p < q inside it with cnt[p][q] >= min_common and NOT
+ *      spread[p][q] <= tol (a conflict: the component is a linkage, or two bodies bridged by a marker, not one body),
+ *      gspread = the largest spread over its edges.
+ * Two calls on the same input give the same bytes; the host form and the "_dev" form give the same bytes.  The bounding boxes are
+ * combined with 64-bit integer atomics on an order-preserving key (order-independent); there are no floating-point atomics.  The
+ * "_dev" form enqueues on the context's stream (every pointer device-accessible), with no host round trip; the host form uploads,
+ * runs and downloads.  The workspace of one call stays under 256 MB: the pairs go through it in rounds.
+ * What the stage cannot know: two bodies that never move relative to each other during the capture are one group, and so are
+ * markers that lie still (on the floor, on a tripod) -- any two of them keep their distance.  min_travel is the handle for those;
+ * a capture in which every body moves on its own is the user's part.
+ * Out of scope: robust (median or inlier-fraction) spreads; splitting a linkage at its conflicts; cliques instead of components;
+ * more than 256 rows or 2^22 frames; a streaming form; rigid-body geometry as a cue for the stitcher. */
+#define MOCAP_RG_MAX_ROWS 256
+#define MOCAP_RG_MAX_FRAMES 4194304
+int mocap_rigid_groups(mocap_ctx* ctx, int64_t n_frames, int R, const double* traj, int min_common, double tol, double max_dist,
+                       double min_travel, int32_t* cnt, double* dist, double* spread, double* travel, int32_t* group_of,
+                       int32_t* gsize, int32_t* ghead, int32_t* gconf, double* gspread, int32_t* n_groups);
+int mocap_rigid_groups_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_traj, int min_common, double tol, double max_dist,
+                           double min_travel, int32_t* d_cnt, double* d_dist, double* d_spread, double* d_travel,
+                           int32_t* d_group_of, int32_t* d_gsize, int32_t* d_ghead, int32_t* d_gconf, double* d_gspread,
+                           int32_t* d_n_groups);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

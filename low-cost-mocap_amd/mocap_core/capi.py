@@ -58,6 +58,7 @@ LB_ST_MARKER_UNSEEN = 2   # ... a marker had no used frame in some round and kep
 TS_MAX_ROWS, TS_MAX_HALF_WINDOW = 1024, 32   # mocap_gather_tracks / mocap_smooth_tracks: rows, half window in frames
 TS_SMOOTHED, TS_FILLED, TS_FEW, TS_SINGULAR, TS_BAD_TIME = 1, 2, 4, 8, 16   # ... a sample's flag (include/mocap_core.h)
 ST_MAX_FIT = 64           # mocap_stitch_tracks: frames of an end model's window at most
+RG_MAX_ROWS, RG_MAX_FRAMES = 256, 1 << 22    # mocap_rigid_groups: rows and frames at most
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -141,6 +142,8 @@ SIGNATURES = {
     "mocap_smooth_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_stitch_tracks": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_stitch_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_rigid_groups": (_i32, [_vp, _i64, _i32, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_rigid_groups_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -904,6 +907,34 @@ class MocapCore:
         self._check(self.lib.mocap_stitch_tracks_dev(self._h, int(n_frames), int(R), _vp(d_t), _vp(d_traj), int(fit_frames),
                                                      float(max_dt), float(gate), float(gate_rate), _vp(d_ext), _vp(d_next), _vp(d_prev),
                                                      _vp(d_cost), _vp(d_chain), _vp(d_row_of), _vp(d_n_chains)))
+
+    # ------------------------------------------------------------------ rigid groups (the rows that keep their mutual distances)
+    RIGID_OUT = ("cnt", "dist", "spread", "travel", "group_of", "gsize", "ghead", "gconf", "gspread", "n_groups")
+
+    def rigid_groups(self, traj, min_common, tol, max_dist=float("inf"), min_travel=0.0):
+        """mocap_rigid_groups over the host array traj [R][F][3] (gather_tracks') -> {"cnt" int32, "dist", "spread" [R][R]: frames
+        in common, mean and standard deviation of every pair's distance (NaN where cnt is 0), "travel" [R]: the diagonal of each
+        row's bounding box, "group_of" int32 [R]: the row's group or -1, "gsize", "ghead", "gconf" int32 [R], "gspread" [R]: per
+        group its rows, lowest row, conflicts and largest edge spread (-1, -1, -1, NaN beyond n_groups), "n_groups" int}.  Two rows
+        are linked when both have min_common samples and min_travel of travel, share min_common frames, and their distance has a
+        standard deviation <= tol and a mean <= max_dist; the groups are the connected components of at least two rows."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        R, F, _ = traj.shape
+        o = {"cnt": np.zeros((R, R), dtype=np.int32), "dist": np.zeros((R, R)), "spread": np.zeros((R, R)), "travel": np.zeros(R),
+             "gspread": np.zeros(R), "n_groups": np.zeros(1, dtype=np.int32)}
+        o.update({k: np.zeros(R, dtype=np.int32) for k in ("group_of", "gsize", "ghead", "gconf")})
+        self._check(self.lib.mocap_rigid_groups(self._h, F, R, _p(traj), int(min_common), float(tol), float(max_dist),
+                                                float(min_travel), *[_p(o[k]) for k in self.RIGID_OUT]))
+        o["n_groups"] = int(o["n_groups"][0])
+        return o
+
+    def rigid_groups_dev(self, n_frames, R, d_traj, min_common, tol, max_dist, min_travel, d_cnt, d_dist, d_spread, d_travel,
+                         d_group_of, d_gsize, d_ghead, d_gconf, d_gspread, d_n_groups):
+        """Device pointers (ints), shapes as rigid_groups; d_n_groups: int32[1]."""
+        self._check(self.lib.mocap_rigid_groups_dev(self._h, int(n_frames), int(R), _vp(d_traj), int(min_common), float(tol),
+                                                    float(max_dist), float(min_travel), _vp(d_cnt), _vp(d_dist), _vp(d_spread),
+                                                    _vp(d_travel), _vp(d_group_of), _vp(d_gsize), _vp(d_ghead), _vp(d_gconf),
+                                                    _vp(d_gspread), _vp(d_n_groups)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

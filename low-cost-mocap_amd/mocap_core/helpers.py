@@ -720,6 +720,86 @@ def session_trajectories(t, xyz, n_pts, ids, hits=None, min_hits=0, min_len=10, 
     return out
 
 
+def find_rigid_groups(session, tol=0.003, min_common=30, max_dist=float("inf"), min_travel=0.0):
+    """The rigid bodies of a recorded session ("rigid groups", include/mocap_core.h): the rows of session["traj"] -- the gathered
+    samples, not the smoothed or filled ones -- whose mutual distances stay put.  session = what session_trajectories returns, NumPy
+    or resident (a resident traj is read in place; only the [R] and [R][R] outputs come to the host).  Two rows are linked when they
+    share min_common frames over which their distance has a standard deviation <= tol and a mean <= max_dist; min_travel (the
+    diagonal of a row's bounding box) keeps markers that lie still out.  Returns a list of {"rows": the group's rows ascending,
+    "ids": the track id of each row (with a stitched session: the array of ids each row went through), "size", "conflicts": pairs
+    inside the group that share min_common frames and are NOT rigid -- a linkage, or two bodies bridged --, "max_spread": the largest
+    standard deviation over its links, "dist" [size][size]: the mean distances}, ordered by lowest row."""
+    traj = session["traj"]
+    resident = getattr(traj, "is_cuda", False)
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            res = core.rigid_groups(traj, min_common, tol, max_dist=max_dist, min_travel=min_travel)
+        else:
+            import torch
+            R, F = traj.shape[0], traj.shape[1]
+            assert traj.dtype == torch.float64 and traj.is_contiguous() and traj.dim() == 3 and traj.shape[2] == 3
+            if traj.device.index != core.device_id:
+                raise ValueError(f"the session lives on {traj.device}, the core on GPU {core.device_id}: a resident session is read in place")
+            dev = traj.device
+            d = {"cnt": torch.empty((R, R), dtype=torch.int32, device=dev), "n_groups": torch.empty(1, dtype=torch.int32, device=dev)}
+            d.update({k: torch.empty((R, R), dtype=torch.float64, device=dev) for k in ("dist", "spread")})
+            d.update({k: torch.empty(R, dtype=torch.float64, device=dev) for k in ("travel", "gspread")})
+            d.update({k: torch.empty(R, dtype=torch.int32, device=dev) for k in ("group_of", "gsize", "ghead", "gconf")})
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.rigid_groups_dev(F, R, traj.data_ptr(), min_common, tol, max_dist, min_travel, *[d[k].data_ptr() for k in core.RIGID_OUT])
+            core.synchronize()
+            res = {k: v.cpu().numpy() for k, v in d.items()}
+            res["n_groups"] = int(res["n_groups"][0])
+    ids = session["ids"]
+    groups = []
+    for g in range(res["n_groups"]):
+        rows = np.flatnonzero(res["group_of"] == g)
+        groups.append({"rows": rows.tolist(), "ids": [ids[r].tolist() if np.ndim(ids[r]) else int(ids[r]) for r in rows],
+                       "size": int(res["gsize"][g]), "conflicts": int(res["gconf"][g]), "max_spread": float(res["gspread"][g]),
+                       "dist": res["dist"][np.ix_(rows, rows)].copy()})
+    return groups
+
+
+def learn_session_bodies(capture, session, groups=None, names=None, **learn_kw):
+    """From a session's rigid groups to registered bodies: every group with 3 .. capi.RB_MAX_MARKERS rows and no conflict goes
+    through learn_rigid_body.  capture = learn_rigid_body's (the same frames the session was made of, NumPy or resident), session =
+    session_trajectories' dict, groups = find_rigid_groups' list (None: found with its defaults), names = one per group (default
+    "body<g>").  The capture's ids are relabelled through session["relabel"] -- an id >= 0 inside the table becomes its row,
+    everything else -1; plain indexing, on the device for a resident capture -- and the learner is called with sel = the group's
+    rows, so a stitched marker with several ids is one marker.  Returns (learned, skipped): learned = learn_rigid_body's dicts
+    (plus "rows"), ready for set_rigid_bodies(learned, tol=...); skipped = [(group, reason)]."""
+    if groups is None:
+        groups = find_rigid_groups(session)
+    relabel = np.ascontiguousarray(session["relabel"], dtype=np.int32)
+    ids = capture["id"]
+    if getattr(ids, "is_cuda", False):
+        import torch
+        table = torch.from_numpy(relabel).to(ids.device)
+        inside = (ids >= 0) & (ids < relabel.size)
+        rows_of = torch.where(inside, table[ids.clamp(0, relabel.size - 1).long()], torch.full_like(ids, -1)).contiguous()
+    else:
+        ids = np.asarray(ids)
+        inside = (ids >= 0) & (ids < relabel.size)
+        rows_of = np.where(inside, relabel[np.clip(ids, 0, relabel.size - 1)], -1).astype(np.int32)
+    relabelled = {**capture, "id": rows_of}
+    learned, skipped = [], []
+    for g, group in enumerate(groups):
+        if not 3 <= group["size"] <= capi.RB_MAX_MARKERS:
+            skipped.append((group, f"{group['size']} rows: a body has 3 .. {capi.RB_MAX_MARKERS} markers"))
+        elif group["conflicts"]:
+            skipped.append((group, f"{group['conflicts']} pairs inside the group are not rigid: a linkage, or bodies bridged by a marker"))
+        else:
+            try:
+                body = learn_rigid_body(relabelled, sel=group["rows"], name=names[g] if names is not None else f"body{g}", **learn_kw)
+            except capi.MocapError as e:
+                skipped.append((group, str(e)))
+                continue
+            body["rows"] = list(group["rows"])
+            learned.append(body)
+    return learned, skipped
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
