@@ -3,6 +3,7 @@ the plain-C restatement of the reference hot path (see oracle/c/mocap_oracle.c).
 Used by tests/ (parity at sizes the Python restatement cannot reach), by
 __graft_entry__.smoke() and as bench.py's `cpu_baseline` ("port") leg."""
 import ctypes
+import fcntl
 import os
 import subprocess
 
@@ -14,10 +15,18 @@ _lib = None
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, "c", f) for f in ("mocap_oracle.c", "blob_oracle.c")]
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in srcs):
-        subprocess.check_call(["make", "-C", os.path.join(_HERE, "c"), "-B", "libmocap_oracle.so"],
-                              stdout=subprocess.DEVNULL)
+    """Rebuilds the library when it is missing or older than its sources.  Several processes may come here at once (the
+    ranks of a spawned test, bench.py's workers) and the linker writes the file in place: the check and the build are
+    taken under a lock on the directory, so that nobody builds twice or loads a file another process is still writing."""
+    cdir = os.path.join(_HERE, "c")
+    srcs = [os.path.join(cdir, f) for f in ("mocap_oracle.c", "blob_oracle.c")]
+    fd = os.open(cdir, os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in srcs):
+            subprocess.check_call(["make", "-C", cdir, "-B", "libmocap_oracle.so"], stdout=subprocess.DEVNULL)
+    finally:
+        os.close(fd)        # releases the lock
     return _SO
 
 

@@ -10,19 +10,25 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import jpeg_cases as jc  # noqa: E402
 import jpeg_reference as jr  # noqa: E402
 
-# name -> (content, tiles, H, W, qualities)
+# name -> (content, tiles, H, W, qualities), or -> a builder of tests/jpeg_cases.py (constructed images: long zero runs
+# in either table, DC category 11), which brings its qualities along
 CASES = {
     "jpeg_t2_16x16_noise": ("noise", 2, 16, 16, (95, 50)),
     "jpeg_t3_32x48_noise": ("noise", 3, 32, 48, (95, 100)),
     "jpeg_t2_64x64_dots": ("dots", 2, 64, 64, (95, 30)),
+    **jc.GOLDEN,
 }
 
 
 def case_tiles(name):
-    content, T, H, W, _ = CASES[name]
-    return np.stack([jr.content(content, H, W, seed=17 + t) for t in range(T)])
+    """-> tiles [T][H][W][3], qualities"""
+    if callable(CASES[name]):
+        return CASES[name]()
+    content, T, H, W, qualities = CASES[name]
+    return np.stack([jr.content(content, H, W, seed=17 + t) for t in range(T)]), qualities
 
 
 def pil_encode(bgr, quality):
@@ -33,8 +39,8 @@ def pil_encode(bgr, quality):
 
 
 def main():
-    for name, (_, T, H, W, qualities) in CASES.items():
-        tiles = case_tiles(name)
+    for name in CASES:
+        tiles, qualities = case_tiles(name)
         out = {"tiles": tiles, "qualities": np.array(qualities, dtype=np.int32)}
         for i, q in enumerate(qualities):
             ours, pil = jr.encode_tiles(tiles, q), pil_encode(np.hstack(list(tiles)), q)

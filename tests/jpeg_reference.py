@@ -231,6 +231,117 @@ def pack_scan(codes, lens):
     return out[keep].tobytes()
 
 
+STUFF_ROUND_BYTES = 1024 * 16     # scan bytes one round of the device's stuff pass takes: 1 024 lanes, a 16-byte piece each
+
+
+def lane_codes(coef):
+    """The scan of [MCUs][6][64] cut the way the device cuts it: one "lane code" per zigzag position that codes anything.
+    Position 0 is the DC code plus its value bits; a non-zero AC position is its ZRL symbols, its run/size symbol and its
+    value bits; position 63, when zero, is the EOB.  Written from the coefficients on its own, not from scan_symbols():
+    tests/test_jpeg_cases_cpu.py requires that the lane codes, concatenated, are pack_scan()'s bytes.
+    -> list of (bits, length, table, position, run, zrls, size); run and zrls are -1 for DC codes and EOBs."""
+    out = []
+    last_dc = [0, 0, 0]
+    for mcu in np.asarray(coef).tolist():
+        for b, blk in enumerate(mcu):
+            comp = (0, 0, 0, 0, 1, 2)[b]
+            tbl = min(comp, 1)
+            diff = blk[0] - last_dc[comp]
+            last_dc[comp] = blk[0]
+            size = abs(diff).bit_length()
+            code, n = _DC[tbl][size]
+            out.append((code << size | ((diff if diff >= 0 else diff - 1) & ((1 << size) - 1)), n + size, tbl, 0, -1, -1, size))
+            prev = 0
+            for k in range(1, 64):
+                v = blk[k]
+                if v == 0:
+                    continue
+                run = k - prev - 1
+                prev = k
+                bits, n = 0, 0
+                zc, zn = _AC[tbl][0xF0]
+                for _ in range(run // 16):
+                    bits, n = bits << zn | zc, n + zn
+                size = abs(v).bit_length()
+                c, cn = _AC[tbl][(run % 16) << 4 | size]
+                bits = (bits << cn | c) << size | ((v if v >= 0 else v - 1) & ((1 << size) - 1))
+                out.append((bits, n + cn + size, tbl, k, run, run // 16, size))
+            if blk[63] == 0:
+                c, cn = _AC[tbl][0]
+                out.append((c, cn, tbl, 63, -1, -1, 0))
+    return out
+
+
+def scan_profile(coef):
+    """Which paths of the device's entropy coder the scan of [MCUs][6][64] reaches (csrc/jpeg_kernels.hip: the emit pass
+    writes a lane code into up to three 32-bit words, ac_code loops once per ZRL, the stuff pass takes STUFF_ROUND_BYTES per
+    round in 16-byte pieces).  Per-table entries are indexed 0 = luminance, 1 = chrominance."""
+    lanes = lane_codes(coef)
+    length = np.array([c[1] for c in lanes], np.int64)
+    offset = np.cumsum(length) - length
+    table = np.array([c[2] for c in lanes], np.int64)
+    zrls = np.array([c[5] for c in lanes], np.int64)
+    is_dc = np.array([c[3] == 0 for c in lanes])
+    total = int(length.sum())
+    span = (offset & 31) + length
+    raw = np.frombuffer(unstuffed_scan(lanes), np.uint8)
+    coef = np.asarray(coef)
+    prof = {
+        "lanes": lanes, "length": length, "offset": offset, "table": table,
+        "zrl_codes": [[int(((table == t) & (zrls == z)).sum()) for z in range(4)] for t in range(2)],
+        "runs": [{c[4] for c in lanes if c[2] == t and c[4] >= 0} for t in range(2)],
+        "longest": [int(length[table == t].max()) if (table == t).any() else 0 for t in range(2)],
+        "three_word": [int(((table == t) & (span > 64)).sum()) for t in range(2)],
+        "two_word": [int(((table == t) & (span > 32)).sum()) for t in range(2)],
+        "dc_categories": [{c[6] for c in lanes if c[2] == t and c[3] == 0} for t in range(2)],
+        "ac_sizes": [{c[6] for c in lanes if c[2] == t and c[4] >= 0} for t in range(2)],
+        "blocks": int(is_dc.sum()),
+        "blocks_without_eob": int((coef[:, :, 63] != 0).sum()),
+        "total_bits": total, "nb": (total + 7) // 8, "pad_bits": (-total) % 8,
+        "ff_positions": np.nonzero(raw == 0xFF)[0],
+    }
+    assert prof["nb"] == len(raw)
+    return prof
+
+
+def unstuffed_scan(lanes):
+    """The lane codes as one MSB-first bit string, its last byte padded with 1 bits; no 0x00s inserted."""
+    text = "".join(format(c[0], "0%db" % c[1]) for c in lanes)
+    text += "1" * ((-len(text)) % 8)
+    return int(text, 2).to_bytes(len(text) // 8, "big")
+
+
+def stuffed(raw):
+    return bytes(raw).replace(b"\xff", b"\xff\x00")
+
+
+def ff_per_round(prof):
+    """0xFF bytes each round of the stuff pass meets (the later rounds start from the carried count of the earlier ones)."""
+    rounds = max(1, -(-prof["nb"] // STUFF_ROUND_BYTES))
+    return np.bincount(prof["ff_positions"] // STUFF_ROUND_BYTES, minlength=rounds)
+
+
+def ff_at_piece_offset(prof, at, first_round=0):
+    """0xFF bytes at byte `at` of their 16-byte piece, in rounds first_round and later."""
+    p = prof["ff_positions"]
+    return int(((p % 16 == at) & (p // STUFF_ROUND_BYTES >= first_round)).sum())
+
+
+def last_byte_is_ff(prof):
+    return len(prof["ff_positions"]) > 0 and int(prof["ff_positions"][-1]) == prof["nb"] - 1
+
+
+def profile_line(prof):
+    """One line for a test to print before it asserts on the device."""
+    t = ("Y", "C")
+    return " ".join(
+        [f"blocks={prof['blocks']} no_eob={prof['blocks_without_eob']} nb={prof['nb']} pad={prof['pad_bits']}"]
+        + [f"{t[i]}:zrl0123={prof['zrl_codes'][i]} longest={prof['longest'][i]} w3={prof['three_word'][i]} w2={prof['two_word'][i]} "
+           f"dc<={max(prof['dc_categories'][i])} ac<={max(prof['ac_sizes'][i], default=0)}" for i in range(2)]
+        + [f"ff/round={ff_per_round(prof).tolist()} ff@15={ff_at_piece_offset(prof, 15)} ff@0={ff_at_piece_offset(prof, 0)} "
+           f"last_ff={last_byte_is_ff(prof)}"])
+
+
 def encode(bgr, quality=95):
     """The whole file for one BGR image [H][W][3] uint8."""
     bgr = np.asarray(bgr)

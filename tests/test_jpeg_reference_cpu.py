@@ -6,6 +6,7 @@ import io
 import numpy as np
 import pytest
 
+import jpeg_cases as jc
 import jpeg_reference as jr
 from conftest import golden_names, load_golden
 
@@ -39,6 +40,18 @@ def test_grid_reaches_stuffing_zrl_and_blocks_without_eob():
     assert (coef[:, :, 63] != 0).any(), "no block without EOB"
     _, _, syms = jr.scan_symbols(jr.coefficients(jr.content("dots", 320, 640), 95))
     assert 0xF0 in syms, "no ZRL in the dark frame"
+    # ... and how deep the ZRLs go: the dark frame's stay in luminance and never reach three; the constructed images
+    # (tests/jpeg_cases.py) reach one, two and three in a row in both tables, which scan_symbols' symbols state as well
+    dark = jr.scan_profile(jr.coefficients(jr.content("dots", 320, 640), 95))
+    assert dark["zrl_codes"][0][1] >= 1 and dark["zrl_codes"][0][3] == 0 and dark["zrl_codes"][1][1:] == [0, 0, 0]
+    for t, name in ((0, "single_coefficient_luma/q95"), (1, "single_coefficient_chroma/q95")):
+        frames, q = jc.CASES[name]
+        prof, = jc.profiles(name)
+        assert all(n >= 3 for n in prof["zrl_codes"][t][1:]), (name, prof["zrl_codes"][t])
+        _, _, syms = jr.scan_symbols(jr.coefficients(np.hstack(list(frames[0])), q))
+        text = bytes(syms)
+        assert text.count(b"\xf0") == sum(z * n for tbl in prof["zrl_codes"] for z, n in enumerate(tbl))
+        assert b"\xf0\xf0\xf0" in text and b"\xf0\xf0\xf0\xf0" not in text      # three in a row, never four (run <= 62)
 
 
 def test_quality_outside_1_100_is_refused():
