@@ -965,6 +965,130 @@ int mocap_rigid_groups_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double
                            int32_t* d_group_of, int32_t* d_gsize, int32_t* d_ghead, int32_t* d_gconf, double* d_gspread,
                            int32_t* d_n_groups);
 
+/* ---------------------------------------------------------------- body trajectories (the core's own contract)
+ * A session's rigid bodies as 6-DoF time series.  Behind "rigid groups" and the learner the rows of a body are known and so are
+ * its marker coordinates: the assignment the live body tracker searches for per frame is given.  Three stages, each with a host and
+ * a "_dev" form: the pose per (body, frame) from the labelled rows with a sign-continuous quaternion; the orientation smoothed,
+ * with angular velocity; the session's rows with hidden markers filled from the body's pose.  The body origin is smoothed by
+ * mocap_smooth_tracks itself (t_pose [B][F][3] is a table it accepts).  Offline and opt-in: with nothing called nothing changes;
+ * the context's registration (mocap_set_rigid_bodies) is neither read nor changed.
+ *
+ * The bodies of a call: B in 1 .. MOCAP_BP_MAX_BODIES; n_markers [B] i32, each 3 .. MOCAP_RB_MAX_MARKERS; rows [B][8] i32, the
+ * session row of each marker; markers [B][8][3] f64, body coordinates as mocap_learn_rigid_body returns them.  Entries at or beyond
+ * n_markers[b] are not read.  The three arrays are HOST memory in both forms (as mocap_set_rigid_bodies' are): the host checks
+ * them, tabulates each body's 256-bit posable mask by the rigid-body section's rule, and hands the table to the device inside
+ * kernel arguments -- a "_dev" call neither waits nor keeps a pointer to them.
+ *   MOCAP_E_ARG, every output untouched, for: B outside 1 .. 64; n_markers[b] outside 3 .. 8; a row outside 0 .. R-1; a row used
+ *   twice, within one body or across bodies; a non-finite coordinate; a body whose full marker set is not POSABLE (rigid bodies);
+ *   R outside 1 .. MOCAP_TS_MAX_ROWS; R * n_frames > 2^31; n_frames < 1; a null buffer; and what each stage names below.
+ * All arithmetic is IEEE double, no fused operation, in the order written here; / and sqrt are correctly rounded.  Every byte of
+ * every output is written.  Two calls on the same input give the same bytes; the host form and the "_dev" form give the same
+ * bytes.  No floating-point atomics (one 32-bit integer maximum in LDS, exact in any order).
+ *
+ * 1. mocap_pose_rows[_dev]: traj [R][F][3] as mocap_gather_tracks writes it, the bodies, max_rms (> 0, +inf allowed, else
+ *    MOCAP_E_ARG) -> all [B][F]: n_used i32, present i32, quat [4] (w, x, y, z), Rm [9] row-major, t_pose [3], rms f64, flag i32.
+ *      present  bit m: traj[rows[b][m]][f] is three finite values (m < n_markers[b]);  n_used = the number of set bits
+ *      flag, the first rule that applies:
+ *        n_used < 3                                   MOCAP_BP_FEW
+ *        the present subset is not posable            MOCAP_BP_DEGENERATE   (the body's table at index `present`)
+ *        the fit's rms > max_rms                      MOCAP_BP_RMS
+ *        otherwise                                    MOCAP_BP_POSED
+ *      The fit (made under RMS and POSED) is the rigid-body section's pose of the present markers, operation for operation, the
+ *      markers in ascending m (csrc/rb_pose.hpp): c = n_used, inv = 1 / c; qb, pb = the sums from 0 of the model points and of the
+ *      samples, each * inv; per marker mq = q_m - qb, wp = p_m - pb, S_ij = S_ij + mq_i * wp_j from 0; Horn's matrix
+ *        A00 = (S00 + S11) + S22, A11 = (S00 - S11) - S22, A22 = (S11 - S00) - S22, A33 = (S22 - S00) - S11, A01 = S12 - S21,
+ *        A02 = S20 - S02, A03 = S01 - S10, A12 = S01 + S10, A13 = S20 + S02, A23 = S12 + S21;
+ *      cyclic Jacobi, at most 40 sweeps, a sweep begins with off = the sum of |A01|, |A02|, |A03|, |A12|, |A13|, |A23| in that
+ *      order and ends the iteration when off == 0; the pairs (p, q) in the order 01, 02, 03, 12, 13, 23; a pair with A_pq == 0
+ *      is skipped; with g = 100 |A_pq|, from the fifth sweep on, |A_pp| + g == |A_pp| and |A_qq| + g == |A_qq| set A_pq = 0
+ *      instead; else theta = (A_qq - A_pp) / (2 A_pq), t = 1 / (|theta| + sqrt(theta theta + 1)), negated for theta < 0,
+ *      cs = 1 / sqrt(t t + 1), sn = t cs, A_pp = A_pp - t A_pq, A_qq = A_qq + t A_pq, A_pq = 0, and for k = 0 .. 3: (k not p, q)
+ *      A_kp = cs A_kp - sn A_kq, A_kq = sn A_kp + cs A_kq from the old values, mirrored; V_kp = cs V_kp - sn V_kq,
+ *      V_kq = sn V_kp + cs V_kq, V from the identity.  The column of the largest diagonal entry (the first among equals) is
+ *      (w, x, y, z); qn = sqrt(((w w + x x) + y y) + z z); each / qn;
+ *        R00 = ((w w + x x) - y y) - z z   R01 = 2 (x y - w z)               R02 = 2 (x z + w y)
+ *        R10 = 2 (x y + w z)               R11 = ((w w - x x) + y y) - z z   R12 = 2 (y z - w x)
+ *        R20 = 2 (x z - w y)               R21 = 2 (y z + w x)               R22 = ((w w - x x) - y y) + z z
+ *      t_i = pb_i - ((R_i0 qb_0 + R_i1 qb_1) + R_i2 qb_2); ss = the sum from 0 over the markers and then i = 0, 1, 2 of r r,
+ *      r = ((R_i0 mq_0 + R_i1 mq_1) + R_i2 mq_2) - wp_i; rms = sqrt(ss * inv).
+ *      Under every flag but POSED quat, Rm and t_pose are NaN; rms is NaN under FEW and DEGENERATE (no fit was made).
+ *    Sign continuity.  An eigenvector's sign is arbitrary; a smoother needs one hemisphere.  Over the POSED frames of a body in
+ *    ascending f, s = the sign state (0 = as computed, 1 = negated), out = the quaternion written:
+ *      the first:   s = 1 iff its first non-zero component in (w, x, y, z) order is negative;
+ *      every later: d = ((w w' + x x') + y y') + z z' of the frame's computed quaternion against the previous POSED frame's `out`;
+ *                   d < 0: s = 1; d > 0: s = 0; d zero or NaN: s stays what it was (no flip);
+ *      out = the computed quaternion, all four components negated iff s = 1.  Rm does not depend on the sign.
+ *    Negation is exact, so s is the prefix parity of the flips [d_raw < 0] between consecutive computed quaternions (and the
+ *    first frame's bit): the device finds the previous POSED frame by a prefix maximum and the parity by a prefix XOR, in tiles
+ *    of 256 frames -- four small launches behind the pose kernel, no walk over frames.
+ *
+ * 2. mocap_smooth_rotations[_dev]: t [F], quat [B][F][4] (stage 1's), degree, W, span, n_min, max_gap with the ranges and refusals
+ *    of mocap_smooth_tracks (B in the place of R: 1 .. MOCAP_BP_MAX_BODIES; the host form also rejects a t with no finite entry)
+ *    -> quat_s [B][F][4], omega [B][F][3] (rad/s, world axes), res [B][F] f64, n_used, flag [B][F] i32 (MOCAP_TS_* values).
+ *      Good time, samples, fillable, the flag rules and the fit are those of "trajectories", word for word, with four coordinates
+ *      k = 0 .. 3 instead of three, and: (b, f) is present iff f has a good time and quat[b][f] is four finite values.
+ *      With p = c_0 and p' = c_1 / h (four components each, / per component):
+ *        n2 = ((p_w p_w + p_x p_x) + p_y p_y) + p_z p_z; not finite or not > 0: flag = MOCAP_TS_SINGULAR (n_used = n)
+ *        quat_s = p / sqrt(n2) per component
+ *        omega_x = (2 * ((p_w * p'_x - p'_w * p_x) - (p'_y * p_z - p'_z * p_y))) / n2
+ *        omega_y = (2 * ((p_w * p'_y - p'_w * p_y) - (p'_z * p_x - p'_x * p_z))) / n2
+ *        omega_z = (2 * ((p_w * p'_z - p'_w * p_z) - (p'_x * p_y - p'_y * p_x))) / n2
+ *        res = sqrt(ss / (4 n)), ss over the samples in ascending g and then k = 0 .. 3, Horner as in "trajectories".
+ *      omega = 2 vec(p' (x) conj(p)) / |p|^2 is the exact angular velocity of the normalised polynomial; with world = R body it is
+ *      expressed in world axes.  Only SMOOTHED and FILLED make an output; under every other flag quat_s, omega and res are NaN.
+ *      mocap_smooth_tracks over t_pose with the same parameters gives the same flag and n_used: the presence pattern is the same
+ *      (POSED) and the pivots depend on the times alone -- save where this stage's n2 rule fires.
+ *
+ * 3. mocap_fill_rows[_dev]: traj [R][F][3], the bodies, stage 1's flag, Rm, t_pose [B][F], and optionally -- all three or none
+ *    (NULL), anything else is MOCAP_E_ARG -- flag_s [B][F] i32, quat_s [B][F][4] (stage 2's) and pos_s [B][F][3]
+ *    (mocap_smooth_tracks' pos over t_pose) -> filled [R][F][3] f64, src [R][F] i32, per (row, frame) by the first rule that applies:
+ *      traj[r][f] is three finite values                          those bytes, MOCAP_BP_SRC_MEASURED
+ *      r is marker m of body b and flag[b][f] is POSED            x_i = ((Rm_i0 * q_0 + Rm_i1 * q_1) + Rm_i2 * q_2) + t_pose_i,
+ *                                                                 q = markers[b][m], MOCAP_BP_SRC_RIGID
+ *      ... the optional arrays are given and flag_s[b][f] is      R from quat_s[b][f] by the formula of stage 1,
+ *          MOCAP_TS_FILLED                                        x_i = ((R_i0 * q_0 + R_i1 * q_1) + R_i2 * q_2) + pos_s_i,
+ *                                                                 MOCAP_BP_SRC_RIGID_FILLED
+ *      otherwise                                                  three NaN, MOCAP_BP_SRC_NONE
+ *    A row of no body falls under the first and the last rule only.  filled is a table mocap_smooth_tracks, mocap_stitch_tracks
+ *    and mocap_rigid_groups read unchanged.  A marker hidden for seconds is there as long as three others of its body that span
+ *    a plane are seen.
+ * One lane per (body, frame) for the poses and per (row, frame) for the fill, frames along the lanes; the rotation smoother stages
+ * 256 frames and a halo of W in LDS as "trajectories" does.  The "_dev" forms enqueue on the context's stream (every pointer but
+ * the body description device-accessible), with no host round trip; the host forms upload, run and download.
+ * Out of scope: angular acceleration; a geodesic (SO(3)) fit instead of the component-wise polynomial; re-learning the template
+ * from the filled rows; body geometry as a cue for the stitcher; a pose from fewer than three markers; weighted or robust fits; a
+ * streaming form; more than 64 bodies or 8 markers per body; writing C3D or TRC files. */
+#define MOCAP_BP_MAX_BODIES 64
+enum {
+  MOCAP_BP_POSED = 1,       /* a pose was fitted to the present markers and its rms is within max_rms */
+  MOCAP_BP_FEW = 2,         /* fewer than three markers of the body are present: no fit */
+  MOCAP_BP_DEGENERATE = 4,  /* the present markers are not a posable subset (collinear): no fit */
+  MOCAP_BP_RMS = 8          /* the fit's rms exceeds max_rms: rms is written, the pose is not */
+};
+enum {
+  MOCAP_BP_SRC_NONE = 0,         /* no sample and nothing to fill it from: NaN */
+  MOCAP_BP_SRC_MEASURED = 1,     /* the row's own sample */
+  MOCAP_BP_SRC_RIGID = 2,        /* the frame's pose applied to the marker's body coordinates */
+  MOCAP_BP_SRC_RIGID_FILLED = 3  /* the smoothers' gap-filled pose applied to them */
+};
+int mocap_pose_rows(mocap_ctx* ctx, int64_t n_frames, int R, const double* traj, int B, const int32_t* n_markers, const int32_t* rows,
+                    const double* markers, double max_rms, int32_t* n_used, int32_t* present, double* quat, double* Rm, double* t_pose,
+                    double* rms, int32_t* flag);
+int mocap_pose_rows_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_traj, int B, const int32_t* n_markers,
+                        const int32_t* rows, const double* markers, double max_rms, int32_t* d_n_used, int32_t* d_present,
+                        double* d_quat, double* d_Rm, double* d_t_pose, double* d_rms, int32_t* d_flag);
+int mocap_smooth_rotations(mocap_ctx* ctx, int64_t n_frames, int B, const double* t, const double* quat, int degree, int W, double span,
+                           int n_min, int max_gap, double* quat_s, double* omega, double* res, int32_t* n_used, int32_t* flag);
+int mocap_smooth_rotations_dev(mocap_ctx* ctx, int64_t n_frames, int B, const double* d_t, const double* d_quat, int degree, int W,
+                               double span, int n_min, int max_gap, double* d_quat_s, double* d_omega, double* d_res,
+                               int32_t* d_n_used, int32_t* d_flag);
+int mocap_fill_rows(mocap_ctx* ctx, int64_t n_frames, int R, const double* traj, int B, const int32_t* n_markers, const int32_t* rows,
+                    const double* markers, const int32_t* flag, const double* Rm, const double* t_pose, const int32_t* flag_s,
+                    const double* quat_s, const double* pos_s, double* filled, int32_t* src);
+int mocap_fill_rows_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_traj, int B, const int32_t* n_markers,
+                        const int32_t* rows, const double* markers, const int32_t* d_flag, const double* d_Rm, const double* d_t_pose,
+                        const int32_t* d_flag_s, const double* d_quat_s, const double* d_pos_s, double* d_filled, int32_t* d_src);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

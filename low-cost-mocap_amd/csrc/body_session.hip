@@ -1,0 +1,547 @@
+// body_session.hip -- a session's rigid bodies as 6-DoF series (include/mocap_core.h, "body trajectories").
+//   put      the host's body table into device memory: a chunk of 8 bodies per launch travels as a kernel argument, so a "_dev" call
+//            needs neither a host buffer that outlives it nor a wait.
+//   pose     one lane per (body, frame), grid ceil(F / 256) x B, frames along the lanes: the 24-byte samples of a row lie side by
+//            side.  The body -- rows, model, posable mask -- is the same for the whole workgroup: scalar loads.  The present markers'
+//            points are read three times (centroid, cross-covariance, residual) instead of being kept: 48 doubles less beside the
+//            64 of A and V, which is what keeps the kernel out of scratch.  The arithmetic is rb_pose.hpp's,
+//            operation for operation, with the points taken from the rows; the Jacobi sweep is that header's own function.
+//   sign     the previous POSED frame of every frame as a prefix maximum (the tile's last POSED frame from the pose kernel, one
+//            workgroup per body over the tiles, then within the tile), the flip against it, and the flips' prefix parity the same
+//            way: four small launches behind the pose kernel, no walk over frames.  Maximum and XOR are exact in any order.
+//   smooth   track_smooth.hip's layout with four doubles per sample: 256 frames and a halo of W on either side in LDS (t, four
+//            planes, one byte of bits: 13.1 KB), each lane walks its window three times.  The fit is that kernel's text with 3 -> 4
+//            (it lives in that file's unnamed namespace; moving it would change what the existing kernel compiles from).
+//   fill     one lane per (row, frame), grid ceil(F / 256) x R; the row's (body, marker) comes from a table built on the device.
+// FP64 throughout, nothing fused (-ffp-contract=off is the build's rule), / and sqrt correctly rounded.
+#include "body_session.hpp"
+#include "mocap_device.hpp"
+#include "rb_pose.hpp"
+
+namespace mocap {
+
+namespace {
+
+constexpr int kT = kTsTile;
+constexpr int kStage = kTsTile + 2 * kTsMaxHalfWindow;
+constexpr int kTsSmoothed = 1, kTsFilled = 2, kTsFew = 4, kTsSingular = 8, kTsBadTime = 16;  // mirrored from include/mocap_core.h (MOCAP_TS_*)
+constexpr int kGood = 1, kPresent = 2;  // bits of a staged frame
+
+__device__ __forceinline__ bool finite1(double v) { return fabs(v) < __builtin_inf(); }  // false for NaN
+
+// ------------------------------------------------------------------------------------------------------------------ body table
+__global__ __launch_bounds__(64) void bp_put_kernel(BpBodyChunk c, int count, BpBody* dst) {
+  constexpr int kWords = (int)(sizeof(BpBody) / sizeof(unsigned long long));
+  static_assert(sizeof(BpBody) % sizeof(unsigned long long) == 0, "copied as 64-bit words");
+  const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&c);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(dst);
+  for (int i = threadIdx.x; i < count * kWords; i += 64) out[i] = src[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------------ poses
+__global__ __launch_bounds__(kT) void bp_pose_kernel(PoseRowsArgs a) {
+  __shared__ int s_last;
+  const int b = blockIdx.y, lane = threadIdx.x;
+  const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + lane;
+  if (lane == 0) s_last = -1;
+  __syncthreads();
+  const BpBody* __restrict__ body = a.bodies + b;
+  const int N = body->n;
+  bool posed = false;
+  if (f < F) {
+    const double nan = __builtin_nan("");
+    const double* __restrict__ P = a.traj + (size_t)f * 3;
+    const size_t rs = (size_t)F * 3;  // doubles per row
+    double qb[3] = {0, 0, 0}, pb[3] = {0, 0, 0};
+    unsigned pres = 0;
+    int count = 0;
+#pragma unroll
+    for (int m = 0; m < kBpMaxMarkers; m++)
+      if (m < N) {
+        const double* p = P + (size_t)body->rows[m] * rs;
+        const double x = p[0], y = p[1], z = p[2];
+        if (finite1(x) && finite1(y) && finite1(z)) {
+          pres |= 1u << m;
+          count++;
+          qb[0] = qb[0] + body->q[m][0];
+          qb[1] = qb[1] + body->q[m][1];
+          qb[2] = qb[2] + body->q[m][2];
+          pb[0] = pb[0] + x;
+          pb[1] = pb[1] + y;
+          pb[2] = pb[2] + z;
+        }
+      }
+    int flag;
+    double quat[4] = {nan, nan, nan, nan}, R[9], t[3] = {nan, nan, nan}, rms = nan;
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = nan;
+    if (count < 3) {
+      flag = kBpFew;
+    } else if (!((body->posable[pres >> 6] >> (pres & 63)) & 1ull)) {
+      flag = kBpDegenerate;
+    } else {
+      const double inv_c = 1.0 / (double)count;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        qb[k] = qb[k] * inv_c;
+        pb[k] = pb[k] * inv_c;
+      }
+      double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // S[i][j] = sum (q - qb)_i (p - pb)_j
+#pragma unroll
+      for (int m = 0; m < kBpMaxMarkers; m++)
+        if (m < N && (pres >> m & 1u)) {
+          const double* p = P + (size_t)body->rows[m] * rs;
+          double mq[3], wp[3];
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+            mq[k] = body->q[m][k] - qb[k];
+            wp[k] = p[k] - pb[k];
+          }
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) S[i][j] = S[i][j] + mq[i] * wp[j];
+        }
+      double A[4][4], V[4][4];
+      A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
+      A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
+      A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
+      A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+      A[0][1] = A[1][0] = S[1][2] - S[2][1];
+      A[0][2] = A[2][0] = S[2][0] - S[0][2];
+      A[0][3] = A[3][0] = S[0][1] - S[1][0];
+      A[1][2] = A[2][1] = S[0][1] + S[1][0];
+      A[1][3] = A[3][1] = S[2][0] + S[0][2];
+      A[2][3] = A[3][2] = S[1][2] + S[2][1];
+      rb_jacobi4(A, V);
+      double lam = A[0][0], qw = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
+#pragma unroll
+      for (int k = 1; k < 4; k++)
+        if (A[k][k] > lam) {
+          lam = A[k][k];
+          qw = V[0][k];
+          qx = V[1][k];
+          qy = V[2][k];
+          qz = V[3][k];
+        }
+      const double qn = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
+      qw = qw / qn;
+      qx = qx / qn;
+      qy = qy / qn;
+      qz = qz / qn;
+      R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
+      R[1] = 2.0 * (qx * qy - qw * qz);
+      R[2] = 2.0 * (qx * qz + qw * qy);
+      R[3] = 2.0 * (qx * qy + qw * qz);
+      R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
+      R[5] = 2.0 * (qy * qz - qw * qx);
+      R[6] = 2.0 * (qx * qz - qw * qy);
+      R[7] = 2.0 * (qy * qz + qw * qx);
+      R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+#pragma unroll
+      for (int i = 0; i < 3; i++) t[i] = pb[i] - ((R[3 * i] * qb[0] + R[3 * i + 1] * qb[1]) + R[3 * i + 2] * qb[2]);
+      // residuals in centred coordinates: R q_i + t - p_i = R (q_i - qb) - (p_i - pb)
+      double ss = 0.0;
+#pragma unroll
+      for (int m = 0; m < kBpMaxMarkers; m++)
+        if (m < N && (pres >> m & 1u)) {
+          const double* p = P + (size_t)body->rows[m] * rs;
+          double mq[3];
+#pragma unroll
+          for (int k = 0; k < 3; k++) mq[k] = body->q[m][k] - qb[k];
+#pragma unroll
+          for (int i = 0; i < 3; i++) {
+            const double r = ((R[3 * i] * mq[0] + R[3 * i + 1] * mq[1]) + R[3 * i + 2] * mq[2]) - (p[i] - pb[i]);
+            ss = ss + r * r;
+          }
+        }
+      rms = sqrt(ss * inv_c);
+      if (rms > a.max_rms) {
+        flag = kBpRms;
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = nan;
+        t[0] = t[1] = t[2] = nan;
+      } else {
+        flag = kBpPosed;
+        posed = true;
+        quat[0] = qw;
+        quat[1] = qx;
+        quat[2] = qy;
+        quat[3] = qz;
+      }
+    }
+    const size_t o = (size_t)b * F + f;
+    a.n_used[o] = count;
+    a.present[o] = (int32_t)pres;
+    a.flag[o] = flag;
+    a.rms[o] = rms;
+#pragma unroll
+    for (int i = 0; i < 4; i++) a.quat[4 * o + i] = quat[i];
+#pragma unroll
+    for (int i = 0; i < 9; i++) a.Rm[9 * o + i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) a.t_pose[3 * o + i] = t[i];
+  }
+  if (posed) atomicMax(&s_last, lane);  // (an integer maximum in LDS: exact in any order)
+  __syncthreads();
+  if (lane == 0) a.tile_i32[(size_t)b * gridDim.x + blockIdx.x] = s_last < 0 ? -1 : (int32_t)(blockIdx.x * kT + s_last);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ sign continuity
+struct OpMax {
+  static constexpr int32_t kNone = -1;
+  __device__ static int32_t op(int32_t x, int32_t y) { return x > y ? x : y; }
+};
+struct OpXor {
+  static constexpr int32_t kNone = 0;
+  __device__ static int32_t op(int32_t x, int32_t y) { return x ^ y; }
+};
+
+// inclusive prefix over the workgroup's 256 values (Hillis-Steele through LDS); every lane calls it
+template <class Op>
+__device__ __forceinline__ int32_t block_prefix(int32_t v, int32_t* s) {
+  const int l = threadIdx.x;
+  s[l] = v;
+  __syncthreads();
+  for (int d = 1; d < kT; d <<= 1) {
+    const int32_t o = l >= d ? s[l - d] : Op::kNone;
+    __syncthreads();
+    v = Op::op(o, v);
+    s[l] = v;
+    __syncthreads();
+  }
+  return v;
+}
+
+// one workgroup per body: tile[p] becomes the fold of the tiles before p.  Lane l owns the entries [l * per, (l + 1) * per).
+template <class Op>
+__global__ __launch_bounds__(kT) void bp_tile_scan_kernel(int32_t* tile_i32, int64_t P) {
+  __shared__ int32_t s[kT];
+  int32_t* tile = tile_i32 + (size_t)blockIdx.x * P;
+  const int64_t per = (P + kT - 1) / kT, lo = threadIdx.x * per, hi = lo + per < P ? lo + per : P;
+  int32_t m = Op::kNone;
+  for (int64_t p = lo; p < hi; p++) m = Op::op(m, tile[p]);
+  block_prefix<Op>(m, s);
+  int32_t run = threadIdx.x > 0 ? s[threadIdx.x - 1] : Op::kNone;
+  for (int64_t p = lo; p < hi; p++) {
+    const int32_t own = tile[p];
+    tile[p] = run;
+    run = Op::op(run, own);
+  }
+}
+
+// the flip of every POSED frame against the POSED frame before it, and the flips' parity within the tile
+__global__ __launch_bounds__(kT) void bp_flip_kernel(PoseRowsArgs a) {
+  __shared__ int32_t s[kT];
+  const int b = blockIdx.y, lane = threadIdx.x;
+  const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + lane;
+  const size_t o = (size_t)b * F + (f < F ? f : 0), tp = (size_t)b * gridDim.x + blockIdx.x;
+  const bool posed = f < F && a.flag[o] == kBpPosed;
+  block_prefix<OpMax>(posed ? (int32_t)f : -1, s);
+  const int32_t in_tile = lane > 0 ? s[lane - 1] : -1, before_tile = a.tile_i32[tp];
+  const int32_t prev = in_tile > before_tile ? in_tile : before_tile;
+  int32_t flip = 0;
+  if (posed) {
+    const double* q = a.quat + 4 * o;
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    if (prev < 0) {
+      const double lead = w != 0.0 ? w : x != 0.0 ? x : y != 0.0 ? y : z;
+      flip = lead < 0.0;
+    } else {
+      const double* u = a.quat + 4 * ((size_t)b * F + prev);
+      const double d = ((u[0] * w + u[1] * x) + u[2] * y) + u[3] * z;
+      flip = d < 0.0;
+    }
+  }
+  __syncthreads();  // (s is read above and rewritten below)
+  const int32_t par = block_prefix<OpXor>(flip, s);
+  if (f < F) a.parity[o] = (uint8_t)par;
+  __syncthreads();  // every lane has read tile_i32[tp]
+  if (lane == kT - 1) a.tile_i32[tp] = par;
+}
+
+__global__ __launch_bounds__(kT) void bp_sign_kernel(PoseRowsArgs a) {
+  const int b = blockIdx.y;
+  const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (f >= F) return;
+  const size_t o = (size_t)b * F + f;
+  if (a.flag[o] != kBpPosed) return;
+  if (!((a.parity[o] ^ a.tile_i32[(size_t)b * gridDim.x + blockIdx.x]) & 1)) return;
+  double* q = a.quat + 4 * o;
+#pragma unroll
+  for (int i = 0; i < 4; i++) q[i] = -q[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------------ rotations
+template <int D>
+__global__ __launch_bounds__(kT) void bp_smooth_kernel(SmoothRotationsArgs a) {
+  __shared__ double s_t[kStage];
+  __shared__ double s_x[4][kStage];
+  __shared__ uint8_t s_ok[kStage];
+  const int W = a.W, lane = threadIdx.x, r = blockIdx.y;
+  const int64_t F = a.n_frames, f0 = (int64_t)blockIdx.x * kT;
+  const double* row = a.quat + (size_t)r * F * 4;
+  for (int i = lane; i < kT + 2 * W; i += kT) {  // staged index i = frame f0 - W + i
+    const int64_t g = f0 - W + i;
+    double tv = 0.0, x[4] = {0.0, 0.0, 0.0, 0.0};
+    int bits = 0;
+    if (g >= 0 && g < F) {
+      tv = a.t[g];
+#pragma unroll
+      for (int k = 0; k < 4; k++) x[k] = row[4 * g + k];
+      if (a.good[g]) bits = finite1(x[0]) && finite1(x[1]) && finite1(x[2]) && finite1(x[3]) ? kGood | kPresent : kGood;
+    }
+    s_t[i] = tv;
+#pragma unroll
+    for (int k = 0; k < 4; k++) s_x[k][i] = x[k];
+    s_ok[i] = (uint8_t)bits;
+  }
+  __syncthreads();
+  const int64_t f = f0 + lane;
+  if (f >= F) return;
+
+  const double nan = __builtin_nan("");
+  const int c = lane + W;  // this lane's frame among the staged ones; its window is the staged frames lane .. lane + 2 W
+  const double tf = s_t[c];
+  int n = 0, flag = 0;
+  double out[8];           // quat_s, omega, res
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[i] = nan;
+  double h = 0.0;
+  if (!(s_ok[c] & kGood)) {
+    flag = kTsBadTime;
+  } else {
+    int ja = 0, jb = 0;    // offsets of the nearest present frames below and above, 0 = none in the window
+    bool sa = false, sb = false;
+    for (int j = -W; j <= W; j++) {
+      if (!(s_ok[c + j] & kPresent)) continue;
+      const double as = fabs(s_t[c + j] - tf);
+      const bool in = as <= a.span;
+      if (in) {
+        n++;
+        h = as > h ? as : h;
+      }
+      if (j < 0) {
+        ja = j;
+        sa = in;
+      } else if (j > 0 && jb == 0) {
+        jb = j;
+        sb = in;
+      }
+    }
+    const bool present = s_ok[c] & kPresent;
+    const bool fillable = !present && a.max_gap > 0 && ja != 0 && jb != 0 && jb - ja - 1 <= a.max_gap && sa && sb;
+    if (!present && !fillable) {
+      flag = 0;
+    } else if (n < a.n_min) {
+      flag = kTsFew;
+    } else {
+      double S[2 * D + 1], B[D + 1][4];
+#pragma unroll
+      for (int i = 0; i <= 2 * D; i++) S[i] = 0.0;
+#pragma unroll
+      for (int i = 0; i <= D; i++) B[i][0] = B[i][1] = B[i][2] = B[i][3] = 0.0;
+      for (int j = -W; j <= W; j++) {
+        if (!(s_ok[c + j] & kPresent)) continue;
+        const double s = s_t[c + j] - tf;
+        if (!(fabs(s) <= a.span)) continue;
+        const double u = s / h, x0 = s_x[0][c + j], x1 = s_x[1][c + j], x2 = s_x[2][c + j], x3 = s_x[3][c + j];
+        double p = 1.0;
+#pragma unroll
+        for (int i = 0; i <= 2 * D; i++) {
+          S[i] = S[i] + p;
+          if (i <= D) {
+            B[i][0] = B[i][0] + p * x0;
+            B[i][1] = B[i][1] + p * x1;
+            B[i][2] = B[i][2] + p * x2;
+            B[i][3] = B[i][3] + p * x3;
+          }
+          p = p * u;
+        }
+      }
+      // A_ij = S_{i+j} = L L^T, row by row
+      double L[D + 1][D + 1];
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i <= D; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+          double s = S[i + j];
+#pragma unroll
+          for (int k = 0; k < j; k++) s = s - L[i][k] * L[j][k];
+          if (j == i) {
+            if (!(s > 0.0 && s < __builtin_inf())) ok = false;
+            L[i][i] = sqrt(s);
+          } else {
+            L[i][j] = s / L[j][j];
+          }
+        }
+      if (!ok) {
+        flag = kTsSingular;
+      } else {
+        double cf[D + 1][4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          double y[D + 1];
+#pragma unroll
+          for (int i = 0; i <= D; i++) {
+            double s = B[i][k];
+#pragma unroll
+            for (int m = 0; m < i; m++) s = s - L[i][m] * y[m];
+            y[i] = s / L[i][i];
+          }
+#pragma unroll
+          for (int i = D; i >= 0; i--) {
+            double s = y[i];
+#pragma unroll
+            for (int m = i + 1; m <= D; m++) s = s - L[m][i] * cf[m][k];
+            cf[i][k] = s / L[i][i];
+          }
+        }
+        const double pw = cf[0][0], px = cf[0][1], py = cf[0][2], pz = cf[0][3];
+        const double n2 = ((pw * pw + px * px) + py * py) + pz * pz;
+        if (!(n2 > 0.0 && n2 < __builtin_inf())) {
+          flag = kTsSingular;
+        } else {
+          flag = present ? kTsSmoothed : kTsFilled;
+          double ss = 0.0;
+          for (int j = -W; j <= W; j++) {
+            if (!(s_ok[c + j] & kPresent)) continue;
+            const double s = s_t[c + j] - tf;
+            if (!(fabs(s) <= a.span)) continue;
+            const double u = s / h;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              double q = cf[D][k];
+#pragma unroll
+              for (int i = D - 1; i >= 0; i--) q = q * u + cf[i][k];
+              const double e = s_x[k][c + j] - q;
+              ss = ss + e * e;
+            }
+          }
+          const double nq = sqrt(n2);
+          const double dw = cf[1][0] / h, dx = cf[1][1] / h, dy = cf[1][2] / h, dz = cf[1][3] / h;
+          out[0] = pw / nq;
+          out[1] = px / nq;
+          out[2] = py / nq;
+          out[3] = pz / nq;
+          out[4] = (2.0 * ((pw * dx - dw * px) - (dy * pz - dz * py))) / n2;
+          out[5] = (2.0 * ((pw * dy - dw * py) - (dz * px - dx * pz))) / n2;
+          out[6] = (2.0 * ((pw * dz - dw * pz) - (dx * py - dy * px))) / n2;
+          out[7] = sqrt(ss / (double)(4 * n));
+        }
+      }
+    }
+  }
+  const size_t o = (size_t)r * F + f;
+#pragma unroll
+  for (int k = 0; k < 4; k++) a.quat_s[4 * o + k] = out[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) a.omega[3 * o + k] = out[4 + k];
+  a.res[o] = out[7];
+  a.n_used[o] = n;
+  a.flag[o] = flag;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ fill
+__global__ __launch_bounds__(kT) void bp_row_table_kernel(FillRowsArgs a) {  // one workgroup
+  for (int r = threadIdx.x; r < a.R; r += kT) a.row_of[r] = -1;
+  __syncthreads();
+  for (int i = threadIdx.x; i < a.B * kBpMaxMarkers; i += kT) {
+    const int b = i / kBpMaxMarkers, m = i % kBpMaxMarkers;
+    if (m >= a.bodies[b].n) continue;
+    const int r = a.bodies[b].rows[m];
+    if (r >= 0 && r < a.R) a.row_of[r] = i;  // (the host has checked the range and that no row appears twice)
+  }
+}
+
+__global__ __launch_bounds__(kT) void bp_fill_kernel(FillRowsArgs a) {
+  const int r = blockIdx.y;
+  const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (f >= F) return;
+  const size_t o = (size_t)r * F + f;
+  const double nan = __builtin_nan("");
+  double x[3] = {a.traj[3 * o], a.traj[3 * o + 1], a.traj[3 * o + 2]};
+  int src = kBpSrcMeasured;
+  if (!(finite1(x[0]) && finite1(x[1]) && finite1(x[2]))) {
+    x[0] = x[1] = x[2] = nan;
+    src = kBpSrcNone;
+    const int bm = a.row_of[r];
+    if (bm >= 0) {
+      const int b = bm / kBpMaxMarkers, m = bm % kBpMaxMarkers;
+      const double* q = a.bodies[b].q[m];
+      const size_t p = (size_t)b * F + f;
+      if (a.flag[p] == kBpPosed) {
+        const double* R = a.Rm + 9 * p;
+#pragma unroll
+        for (int i = 0; i < 3; i++) x[i] = ((R[3 * i] * q[0] + R[3 * i + 1] * q[1]) + R[3 * i + 2] * q[2]) + a.t_pose[3 * p + i];
+        src = kBpSrcRigid;
+      } else if (a.flag_s && a.flag_s[p] == kTsFilled) {
+        const double qw = a.quat_s[4 * p], qx = a.quat_s[4 * p + 1], qy = a.quat_s[4 * p + 2], qz = a.quat_s[4 * p + 3];
+        double R[9];
+        R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
+        R[1] = 2.0 * (qx * qy - qw * qz);
+        R[2] = 2.0 * (qx * qz + qw * qy);
+        R[3] = 2.0 * (qx * qy + qw * qz);
+        R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
+        R[5] = 2.0 * (qy * qz - qw * qx);
+        R[6] = 2.0 * (qx * qz - qw * qy);
+        R[7] = 2.0 * (qy * qz + qw * qx);
+        R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+#pragma unroll
+        for (int i = 0; i < 3; i++) x[i] = ((R[3 * i] * q[0] + R[3 * i + 1] * q[1]) + R[3 * i + 2] * q[2]) + a.pos_s[3 * p + i];
+        src = kBpSrcRigidFilled;
+      }
+    }
+  }
+  a.filled[3 * o] = x[0];
+  a.filled[3 * o + 1] = x[1];
+  a.filled[3 * o + 2] = x[2];
+  a.src[o] = src;
+}
+
+}  // namespace
+
+hipError_t launch_put_bodies(const BpBody* host, int B, BpBody* dev, hipStream_t stream) {
+  for (int b0 = 0; b0 < B; b0 += kBpPutBodies) {
+    BpBodyChunk c{};
+    const int count = B - b0 < kBpPutBodies ? B - b0 : kBpPutBodies;
+    for (int i = 0; i < count; i++) c.b[i] = host[b0 + i];
+    hipLaunchKernelGGL(bp_put_kernel, dim3(1), dim3(64), 0, stream, c, count, dev + b0);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_pose_rows(const PoseRowsArgs& a, hipStream_t stream) {
+  const int64_t P = ts_tiles(a.n_frames);
+  const dim3 block(kT), grid((unsigned)P, (unsigned)a.B), per_body((unsigned)a.B);
+  hipError_t e;
+  hipLaunchKernelGGL(bp_pose_kernel, grid, block, 0, stream, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bp_tile_scan_kernel<OpMax>, per_body, block, 0, stream, a.tile_i32, P);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bp_flip_kernel, grid, block, 0, stream, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bp_tile_scan_kernel<OpXor>, per_body, block, 0, stream, a.tile_i32, P);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bp_sign_kernel, grid, block, 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_smooth_rotations(const SmoothRotationsArgs& a, hipStream_t stream) {
+  const dim3 block(kT), grid((unsigned)ts_tiles(a.n_frames), (unsigned)a.B);
+  if (a.degree == 1) hipLaunchKernelGGL(bp_smooth_kernel<1>, grid, block, 0, stream, a);
+  else if (a.degree == 2) hipLaunchKernelGGL(bp_smooth_kernel<2>, grid, block, 0, stream, a);
+  else hipLaunchKernelGGL(bp_smooth_kernel<3>, grid, block, 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_rows(const FillRowsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(bp_row_table_kernel, dim3(1), dim3(kT), 0, stream, a);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(bp_fill_kernel, dim3((unsigned)ts_tiles(a.n_frames), (unsigned)a.R), dim3(kT), 0, stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace mocap

@@ -59,6 +59,9 @@ TS_MAX_ROWS, TS_MAX_HALF_WINDOW = 1024, 32   # mocap_gather_tracks / mocap_smoot
 TS_SMOOTHED, TS_FILLED, TS_FEW, TS_SINGULAR, TS_BAD_TIME = 1, 2, 4, 8, 16   # ... a sample's flag (include/mocap_core.h)
 ST_MAX_FIT = 64           # mocap_stitch_tracks: frames of an end model's window at most
 RG_MAX_ROWS, RG_MAX_FRAMES = 256, 1 << 22    # mocap_rigid_groups: rows and frames at most
+BP_MAX_BODIES = 64        # mocap_pose_rows / mocap_smooth_rotations / mocap_fill_rows: bodies of a call at most
+BP_POSED, BP_FEW, BP_DEGENERATE, BP_RMS = 1, 2, 4, 8   # ... a (body, frame)'s flag (include/mocap_core.h)
+BP_SRC_NONE, BP_SRC_MEASURED, BP_SRC_RIGID, BP_SRC_RIGID_FILLED = 0, 1, 2, 3   # ... where a filled sample comes from
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -144,6 +147,12 @@ SIGNATURES = {
     "mocap_stitch_tracks_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_rigid_groups": (_i32, [_vp, _i64, _i32, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_rigid_groups_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_pose_rows": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_pose_rows_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_smooth_rotations": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_smooth_rotations_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_fill_rows": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_fill_rows_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
     "mocap_consolidate_points": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_consolidate_points_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -935,6 +944,96 @@ class MocapCore:
                                                     float(max_dist), float(min_travel), _vp(d_cnt), _vp(d_dist), _vp(d_spread),
                                                     _vp(d_travel), _vp(d_group_of), _vp(d_gsize), _vp(d_ghead), _vp(d_gconf),
                                                     _vp(d_gspread), _vp(d_n_groups)))
+
+    # ------------------------------------------------------------------ body trajectories (a session's bodies as 6-DoF series)
+    POSE_OUT = ("n_used", "present", "quat", "R", "t_pose", "rms", "flag")
+    ROT_OUT = ("quat_s", "omega", "res", "n_used", "flag")
+
+    @staticmethod
+    def _session_bodies(bodies):
+        """bodies = [{"rows": [N] session rows, "markers": [N][3]}] (learn_session_bodies' list) or [(rows, markers)]
+        -> (B, n_markers int32 [B], rows int32 [B][8], markers [B][8][3]): the layout of the C entry points.  A body with more than 8
+        markers keeps its count (the core refuses it); the core does every other check."""
+        B = len(bodies)
+        n = np.zeros(max(B, 1), dtype=np.int32)
+        rows = np.full((max(B, 1), RB_MAX_MARKERS), -1, dtype=np.int32)
+        q = np.zeros((max(B, 1), RB_MAX_MARKERS, 3))
+        for b, body in enumerate(bodies):
+            r, m = (body["rows"], body["markers"]) if isinstance(body, dict) else body
+            r = np.asarray(r, dtype=np.int32).reshape(-1)
+            m = np.asarray(m, dtype=np.float64).reshape(-1, 3)
+            if r.size != m.shape[0]:
+                raise ValueError(f"body {b}: {r.size} rows for {m.shape[0]} markers")
+            n[b] = r.size
+            rows[b, :min(r.size, RB_MAX_MARKERS)] = r[:RB_MAX_MARKERS]
+            q[b, :min(r.size, RB_MAX_MARKERS)] = m[:RB_MAX_MARKERS]
+        return B, n, rows, q
+
+    def pose_rows(self, traj, bodies, max_rms=float("inf")):
+        """mocap_pose_rows over the host array traj [R][F][3] (gather_tracks') and bodies (see _session_bodies) -> {"n_used",
+        "present", "flag" int32 [B][F] (BP_* values), "quat" [B][F][4] (w, x, y, z; sign-continuous along f), "R" [B][F][3][3],
+        "t_pose" [B][F][3], "rms" [B][F]}: the pose of each body at each frame from the markers present in its rows."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        R, F, _ = traj.shape
+        B, n, rows, q = self._session_bodies(bodies)
+        Bz = max(B, 1)
+        o = {"quat": np.zeros((Bz, F, 4)), "R": np.zeros((Bz, F, 3, 3)), "t_pose": np.zeros((Bz, F, 3)), "rms": np.zeros((Bz, F))}
+        o.update({k: np.zeros((Bz, F), dtype=np.int32) for k in ("n_used", "present", "flag")})
+        self._check(self.lib.mocap_pose_rows(self._h, F, R, _p(traj), B, _p(n), _p(rows), _p(q), float(max_rms),
+                                             *[_p(o[k]) for k in self.POSE_OUT]))
+        return o
+
+    def pose_rows_dev(self, n_frames, R, d_traj, bodies, max_rms, d_n_used, d_present, d_quat, d_Rm, d_t_pose, d_rms, d_flag):
+        """Device pointers (ints), shapes as pose_rows; bodies: host data, as there."""
+        B, n, rows, q = self._session_bodies(bodies)
+        self._check(self.lib.mocap_pose_rows_dev(self._h, int(n_frames), int(R), _vp(d_traj), B, _p(n), _p(rows), _p(q), float(max_rms),
+                                                 _vp(d_n_used), _vp(d_present), _vp(d_quat), _vp(d_Rm), _vp(d_t_pose), _vp(d_rms),
+                                                 _vp(d_flag)))
+
+    def smooth_rotations(self, t, quat, degree=2, W=8, span=float("inf"), n_min=None, max_gap=0):
+        """mocap_smooth_rotations over host arrays t [F], quat [B][F][4] (pose_rows') -> {"quat_s" [B][F][4], "omega" [B][F][3] (rad/s,
+        world axes), "res" [B][F], "n_used", "flag" int32 [B][F] (TS_* values)}; the parameters are smooth_tracks'."""
+        quat = np.ascontiguousarray(quat, dtype=np.float64)
+        B, F, _ = quat.shape
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(F)
+        n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+        o = {"quat_s": np.zeros((B, F, 4)), "omega": np.zeros((B, F, 3)), "res": np.zeros((B, F)),
+             "n_used": np.zeros((B, F), dtype=np.int32), "flag": np.zeros((B, F), dtype=np.int32)}
+        self._check(self.lib.mocap_smooth_rotations(self._h, F, B, _p(t), _p(quat), int(degree), int(W), float(span), n_min,
+                                                    int(max_gap), *[_p(o[k]) for k in self.ROT_OUT]))
+        return o
+
+    def smooth_rotations_dev(self, n_frames, B, d_t, d_quat, degree, W, span, n_min, max_gap, d_quat_s, d_omega, d_res, d_n_used,
+                             d_flag):
+        """Device pointers (ints), shapes as smooth_rotations."""
+        self._check(self.lib.mocap_smooth_rotations_dev(self._h, int(n_frames), int(B), _vp(d_t), _vp(d_quat), int(degree), int(W),
+                                                        float(span), int(n_min), int(max_gap), _vp(d_quat_s), _vp(d_omega),
+                                                        _vp(d_res), _vp(d_n_used), _vp(d_flag)))
+
+    def fill_rows(self, traj, bodies, flag, Rm, t_pose, flag_s=None, quat_s=None, pos_s=None):
+        """mocap_fill_rows over host arrays: traj [R][F][3], bodies, pose_rows' flag, R and t_pose, and optionally (all three or
+        none) the smoothers' flag_s, quat_s and pos_s -> {"filled" [R][F][3], "src" int32 [R][F] (BP_SRC_* values)}."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        R, F, _ = traj.shape
+        B, n, rows, q = self._session_bodies(bodies)
+        Bz = max(B, 1)
+        flag = np.ascontiguousarray(flag, dtype=np.int32).reshape(Bz, F)
+        Rm = np.ascontiguousarray(Rm, dtype=np.float64).reshape(Bz, F, 9)
+        t_pose = np.ascontiguousarray(t_pose, dtype=np.float64).reshape(Bz, F, 3)
+        flag_s = None if flag_s is None else np.ascontiguousarray(flag_s, dtype=np.int32).reshape(Bz, F)
+        quat_s = None if quat_s is None else np.ascontiguousarray(quat_s, dtype=np.float64).reshape(Bz, F, 4)
+        pos_s = None if pos_s is None else np.ascontiguousarray(pos_s, dtype=np.float64).reshape(Bz, F, 3)
+        o = {"filled": np.zeros((R, F, 3)), "src": np.zeros((R, F), dtype=np.int32)}
+        self._check(self.lib.mocap_fill_rows(self._h, F, R, _p(traj), B, _p(n), _p(rows), _p(q), _p(flag), _p(Rm), _p(t_pose),
+                                             _p(flag_s), _p(quat_s), _p(pos_s), _p(o["filled"]), _p(o["src"])))
+        return o
+
+    def fill_rows_dev(self, n_frames, R, d_traj, bodies, d_flag, d_Rm, d_t_pose, d_flag_s, d_quat_s, d_pos_s, d_filled, d_src):
+        """Device pointers (ints; d_flag_s, d_quat_s, d_pos_s all 0 or all given); bodies: host data, as in pose_rows."""
+        B, n, rows, q = self._session_bodies(bodies)
+        self._check(self.lib.mocap_fill_rows_dev(self._h, int(n_frames), int(R), _vp(d_traj), B, _p(n), _p(rows), _p(q), _vp(d_flag),
+                                                 _vp(d_Rm), _vp(d_t_pose), _vp(d_flag_s or 0), _vp(d_quat_s or 0), _vp(d_pos_s or 0),
+                                                 _vp(d_filled), _vp(d_src)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

@@ -800,6 +800,73 @@ def learn_session_bodies(capture, session, groups=None, names=None, **learn_kw):
     return learned, skipped
 
 
+def session_body_poses(t, session, bodies, max_rms=float("inf"), degree=2, W=8, span=float("inf"), n_min=None, max_gap=0, fill=True):
+    """The motion of a session's rigid bodies ("body trajectories", include/mocap_core.h): mocap_pose_rows over session["traj"],
+    mocap_smooth_tracks over the body origins, mocap_smooth_rotations over the quaternions and, with fill, mocap_fill_rows.
+    t [F] = the session's time stamps, session = session_trajectories' dict, bodies = learn_session_bodies' `learned` list (its
+    "rows" and "markers" are used), NumPy or resident: a resident traj (and t) is read in place and every result stays a torch
+    tensor on that GPU.  degree .. max_gap are the smoothers' (both get the same).  Returns {"quat" [B][F][4], "R" [B][F][3][3],
+    "t_pose" [B][F][3], "rms", "n_used", "present", "flag" [B][F] (capi.BP_*): the pose per frame; "pos", "vel", "acc" [B][F][3]: the
+    body origin smoothed; "quat_s" [B][F][4], "omega" [B][F][3] (rad/s, world axes), "res_rot", "flag_s" [B][F] (capi.TS_*): the
+    orientation smoothed; with fill "filled" [R][F][3], "src" [R][F] (capi.BP_SRC_*): the session's rows with hidden markers put
+    where the body's pose says they are}."""
+    for b, body in enumerate(bodies):
+        if not isinstance(body, dict) or "rows" not in body or "markers" not in body:
+            raise ValueError(f"session_body_poses: body {b} has no 'rows': pass learn_session_bodies' list (learn_rigid_body's dict "
+                             "does not say which session rows its markers are)")
+    if not bodies:
+        raise ValueError("session_body_poses: no bodies")
+    traj = session["traj"]
+    resident = getattr(traj, "is_cuda", False)
+    n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+    par = (int(degree), int(W), float(span), n_min, int(max_gap))
+    B = len(bodies)
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            o = core.pose_rows(traj, bodies, max_rms=max_rms)
+            tr = core.smooth_tracks(t, o["t_pose"], *par)
+            rot = core.smooth_rotations(t, o["quat"], *par)
+            out = {**o, "pos": tr["pos"], "vel": tr["vel"], "acc": tr["acc"], "quat_s": rot["quat_s"], "omega": rot["omega"],
+                   "res_rot": rot["res"], "flag_s": rot["flag"]}
+            if fill:
+                out.update(core.fill_rows(traj, bodies, o["flag"], o["R"], o["t_pose"], rot["flag"], rot["quat_s"], tr["pos"]))
+        else:
+            import torch
+            R, F = traj.shape[0], traj.shape[1]
+            assert traj.dtype == torch.float64 and traj.is_contiguous() and traj.dim() == 3 and traj.shape[2] == 3
+            if traj.device.index != core.device_id:
+                raise ValueError(f"the session lives on {traj.device}, the core on GPU {core.device_id}: a resident session is read in place")
+            dev = traj.device
+            t = t if getattr(t, "is_cuda", False) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(dev)
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == F
+
+            def f64(*shape):
+                return torch.empty(shape, dtype=torch.float64, device=dev)
+
+            def i32(*shape):
+                return torch.empty(shape, dtype=torch.int32, device=dev)
+
+            out = {"quat": f64(B, F, 4), "R": f64(B, F, 3, 3), "t_pose": f64(B, F, 3), "rms": f64(B, F), "n_used": i32(B, F),
+                   "present": i32(B, F), "flag": i32(B, F), "pos": f64(B, F, 3), "vel": f64(B, F, 3), "acc": f64(B, F, 3),
+                   "quat_s": f64(B, F, 4), "omega": f64(B, F, 3), "res_rot": f64(B, F), "flag_s": i32(B, F)}
+            ws = {"res": f64(B, F), "n_tr": i32(B, F), "flag_tr": i32(B, F), "n_rot": i32(B, F)}
+            if fill:
+                out.update(filled=f64(R, F, 3), src=i32(R, F))
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.pose_rows_dev(F, R, traj.data_ptr(), bodies, max_rms, *[out[k].data_ptr() for k in core.POSE_OUT])
+            core.smooth_tracks_dev(F, B, t.data_ptr(), out["t_pose"].data_ptr(), *par, out["pos"].data_ptr(), out["vel"].data_ptr(),
+                                   out["acc"].data_ptr(), ws["res"].data_ptr(), ws["n_tr"].data_ptr(), ws["flag_tr"].data_ptr())
+            core.smooth_rotations_dev(F, B, t.data_ptr(), out["quat"].data_ptr(), *par, out["quat_s"].data_ptr(),
+                                      out["omega"].data_ptr(), out["res_rot"].data_ptr(), ws["n_rot"].data_ptr(), out["flag_s"].data_ptr())
+            if fill:
+                core.fill_rows_dev(F, R, traj.data_ptr(), bodies, out["flag"].data_ptr(), out["R"].data_ptr(), out["t_pose"].data_ptr(),
+                                   out["flag_s"].data_ptr(), out["quat_s"].data_ptr(), out["pos"].data_ptr(), out["filled"].data_ptr(),
+                                   out["src"].data_ptr())
+            core.synchronize()
+    return out
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
