@@ -3,8 +3,9 @@
 //   gather   per frame the slot each selected marker is present at (8 bytes per frame, kept for the later passes); the valid
 //            frames, the lowest complete frame, and per marker pair the count and the sum of the distances
 //   spread   the second pass of the pair statistics, sum (D - d_ij)^2 with d_ij known
-//   round    the frame posed against the template on its present subset (the arithmetic of rb_pose, operation for operation, with
-//            one lane per frame instead of one wave), its markers mapped back, summed per marker
+//   round    the frame posed against the template on its present subset (centroids, cross-covariance and residual as rb_pose()
+//            has them, operation for operation, with one lane per frame instead of one wave; Horn's matrix, the Jacobi sweep, the
+//            top eigenvector and quaternion -> R are rb_pose.hpp's functions), its markers mapped back, summed per marker
 // and behind each a final launch of one wave that folds the workgroups' partials and writes what the next launch reads: the
 // template of the next round never visits the host.
 //
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(kT) void lb_round_kernel(BodyLearnArgs a) {
       for (int m = 0; m < kM; m++)
 #pragma unroll
         for (int k = 0; k < 3; k++) Q[m][k] = a.state->Q[m][k];
-      // the pose of rb_pose.hpp on the present subset, operation for operation
+      // the pose of rb_pose() on the present subset, operation for operation
       const double inv_c = 1.0 / (double)count;
       double qb[3] = {0, 0, 0}, pb[3] = {0, 0, 0};
 #pragma unroll
@@ -235,42 +236,12 @@ __global__ __launch_bounds__(kT) void lb_round_kernel(BodyLearnArgs a) {
             for (int j = 0; j < 3; j++) S[i][j] = S[i][j] + mq[i] * wp[j];
         }
       double A[4][4], V[4][4];
-      A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
-      A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
-      A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
-      A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
-      A[0][1] = A[1][0] = S[1][2] - S[2][1];
-      A[0][2] = A[2][0] = S[2][0] - S[0][2];
-      A[0][3] = A[3][0] = S[0][1] - S[1][0];
-      A[1][2] = A[2][1] = S[0][1] + S[1][0];
-      A[1][3] = A[3][1] = S[2][0] + S[0][2];
-      A[2][3] = A[3][2] = S[1][2] + S[2][1];
+      rb_horn_matrix(S, A);
       rb_jacobi4(A, V);
-      double lam = A[0][0], qw = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
-#pragma unroll
-      for (int k = 1; k < 4; k++)
-        if (A[k][k] > lam) {
-          lam = A[k][k];
-          qw = V[0][k];
-          qx = V[1][k];
-          qy = V[2][k];
-          qz = V[3][k];
-        }
-      const double qn = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
-      qw = qw / qn;
-      qx = qx / qn;
-      qy = qy / qn;
-      qz = qz / qn;
+      double qw, qx, qy, qz;
+      rb_top_quat(A, V, qw, qx, qy, qz);
       double R[9], t[3];
-      R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
-      R[1] = 2.0 * (qx * qy - qw * qz);
-      R[2] = 2.0 * (qx * qz + qw * qy);
-      R[3] = 2.0 * (qx * qy + qw * qz);
-      R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
-      R[5] = 2.0 * (qy * qz - qw * qx);
-      R[6] = 2.0 * (qx * qz - qw * qy);
-      R[7] = 2.0 * (qy * qz + qw * qx);
-      R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+      rb_quat_to_R(qw, qx, qy, qz, R);
 #pragma unroll
       for (int i = 0; i < 3; i++) t[i] = pb[i] - ((R[3 * i] * qb[0] + R[3 * i + 1] * qb[1]) + R[3 * i + 2] * qb[2]);
       double ss = 0.0;

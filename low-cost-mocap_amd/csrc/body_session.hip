@@ -4,30 +4,30 @@
 //   pose     one lane per (body, frame), grid ceil(F / 256) x B, frames along the lanes: the 24-byte samples of a row lie side by
 //            side.  The body -- rows, model, posable mask -- is the same for the whole workgroup: scalar loads.  The present markers'
 //            points are read three times (centroid, cross-covariance, residual) instead of being kept: 48 doubles less beside the
-//            64 of A and V, which is what keeps the kernel out of scratch.  The arithmetic is rb_pose.hpp's,
-//            operation for operation, with the points taken from the rows; the Jacobi sweep is that header's own function.
+//            64 of A and V, which is what keeps the kernel out of scratch.  Centroids, cross-covariance and
+//            residual are rb_pose()'s operation for operation, with the points taken from the rows; Horn's matrix, the Jacobi sweep,
+//            the top eigenvector and quaternion -> R are rb_pose.hpp's own functions.
 //   sign     the previous POSED frame of every frame as a prefix maximum (the tile's last POSED frame from the pose kernel, one
 //            workgroup per body over the tiles, then within the tile), the flip against it, and the flips' prefix parity the same
-//            way: four small launches behind the pose kernel, no walk over frames.  Maximum and XOR are exact in any order.
+//            way: four small launches behind the pose kernel, no walk over frames (block_scan.hpp's prefix and tile scan, the
+//            good-time launches' own).  Maximum and XOR are exact in any order.
 //   smooth   track_smooth.hip's layout with four doubles per sample: 256 frames and a halo of W on either side in LDS (t, four
-//            planes, one byte of bits: 13.1 KB), each lane walks its window three times.  The fit is that kernel's text with 3 -> 4
-//            (it lives in that file's unnamed namespace; moving it would change what the existing kernel compiles from).
+//            planes, one byte of bits: 13.1 KB), each lane walks its window three times.  Staging, fit and residual walk are
+//            window_fit.hpp's with four channels, the marker smoother's own; this kernel keeps the n2 test between the solve and
+//            the residual walk, the normalisation and omega.
 //   fill     one lane per (row, frame), grid ceil(F / 256) x R; the row's (body, marker) comes from a table built on the device.
 // FP64 throughout, nothing fused (-ffp-contract=off is the build's rule), / and sqrt correctly rounded.
 #include "body_session.hpp"
+#include "block_scan.hpp"
 #include "mocap_device.hpp"
 #include "rb_pose.hpp"
+#include "window_fit.hpp"
 
 namespace mocap {
 
 namespace {
 
 constexpr int kT = kTsTile;
-constexpr int kStage = kTsTile + 2 * kTsMaxHalfWindow;
-constexpr int kTsSmoothed = 1, kTsFilled = 2, kTsFew = 4, kTsSingular = 8, kTsBadTime = 16;  // mirrored from include/mocap_core.h (MOCAP_TS_*)
-constexpr int kGood = 1, kPresent = 2;  // bits of a staged frame
-
-__device__ __forceinline__ bool finite1(double v) { return fabs(v) < __builtin_inf(); }  // false for NaN
 
 // ------------------------------------------------------------------------------------------------------------------ body table
 __global__ __launch_bounds__(64) void bp_put_kernel(BpBodyChunk c, int count, BpBody* dst) {
@@ -103,41 +103,11 @@ __global__ __launch_bounds__(kT) void bp_pose_kernel(PoseRowsArgs a) {
             for (int j = 0; j < 3; j++) S[i][j] = S[i][j] + mq[i] * wp[j];
         }
       double A[4][4], V[4][4];
-      A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
-      A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
-      A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
-      A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
-      A[0][1] = A[1][0] = S[1][2] - S[2][1];
-      A[0][2] = A[2][0] = S[2][0] - S[0][2];
-      A[0][3] = A[3][0] = S[0][1] - S[1][0];
-      A[1][2] = A[2][1] = S[0][1] + S[1][0];
-      A[1][3] = A[3][1] = S[2][0] + S[0][2];
-      A[2][3] = A[3][2] = S[1][2] + S[2][1];
+      rb_horn_matrix(S, A);
       rb_jacobi4(A, V);
-      double lam = A[0][0], qw = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
-#pragma unroll
-      for (int k = 1; k < 4; k++)
-        if (A[k][k] > lam) {
-          lam = A[k][k];
-          qw = V[0][k];
-          qx = V[1][k];
-          qy = V[2][k];
-          qz = V[3][k];
-        }
-      const double qn = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
-      qw = qw / qn;
-      qx = qx / qn;
-      qy = qy / qn;
-      qz = qz / qn;
-      R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
-      R[1] = 2.0 * (qx * qy - qw * qz);
-      R[2] = 2.0 * (qx * qz + qw * qy);
-      R[3] = 2.0 * (qx * qy + qw * qz);
-      R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
-      R[5] = 2.0 * (qy * qz - qw * qx);
-      R[6] = 2.0 * (qx * qz - qw * qy);
-      R[7] = 2.0 * (qy * qz + qw * qx);
-      R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+      double qw, qx, qy, qz;
+      rb_top_quat(A, V, qw, qx, qy, qz);
+      rb_quat_to_R(qw, qx, qy, qz, R);
 #pragma unroll
       for (int i = 0; i < 3; i++) t[i] = pb[i] - ((R[3 * i] * qb[0] + R[3 * i + 1] * qb[1]) + R[3 * i + 2] * qb[2]);
       // residuals in centred coordinates: R q_i + t - p_i = R (q_i - qb) - (p_i - pb)
@@ -188,48 +158,6 @@ __global__ __launch_bounds__(kT) void bp_pose_kernel(PoseRowsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ sign continuity
-struct OpMax {
-  static constexpr int32_t kNone = -1;
-  __device__ static int32_t op(int32_t x, int32_t y) { return x > y ? x : y; }
-};
-struct OpXor {
-  static constexpr int32_t kNone = 0;
-  __device__ static int32_t op(int32_t x, int32_t y) { return x ^ y; }
-};
-
-// inclusive prefix over the workgroup's 256 values (Hillis-Steele through LDS); every lane calls it
-template <class Op>
-__device__ __forceinline__ int32_t block_prefix(int32_t v, int32_t* s) {
-  const int l = threadIdx.x;
-  s[l] = v;
-  __syncthreads();
-  for (int d = 1; d < kT; d <<= 1) {
-    const int32_t o = l >= d ? s[l - d] : Op::kNone;
-    __syncthreads();
-    v = Op::op(o, v);
-    s[l] = v;
-    __syncthreads();
-  }
-  return v;
-}
-
-// one workgroup per body: tile[p] becomes the fold of the tiles before p.  Lane l owns the entries [l * per, (l + 1) * per).
-template <class Op>
-__global__ __launch_bounds__(kT) void bp_tile_scan_kernel(int32_t* tile_i32, int64_t P) {
-  __shared__ int32_t s[kT];
-  int32_t* tile = tile_i32 + (size_t)blockIdx.x * P;
-  const int64_t per = (P + kT - 1) / kT, lo = threadIdx.x * per, hi = lo + per < P ? lo + per : P;
-  int32_t m = Op::kNone;
-  for (int64_t p = lo; p < hi; p++) m = Op::op(m, tile[p]);
-  block_prefix<Op>(m, s);
-  int32_t run = threadIdx.x > 0 ? s[threadIdx.x - 1] : Op::kNone;
-  for (int64_t p = lo; p < hi; p++) {
-    const int32_t own = tile[p];
-    tile[p] = run;
-    run = Op::op(run, own);
-  }
-}
-
 // the flip of every POSED frame against the POSED frame before it, and the flips' parity within the tile
 __global__ __launch_bounds__(kT) void bp_flip_kernel(PoseRowsArgs a) {
   __shared__ int32_t s[kT];
@@ -237,7 +165,7 @@ __global__ __launch_bounds__(kT) void bp_flip_kernel(PoseRowsArgs a) {
   const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + lane;
   const size_t o = (size_t)b * F + (f < F ? f : 0), tp = (size_t)b * gridDim.x + blockIdx.x;
   const bool posed = f < F && a.flag[o] == kBpPosed;
-  block_prefix<OpMax>(posed ? (int32_t)f : -1, s);
+  block_prefix<OpMaxI32>(posed ? (int32_t)f : -1, s);
   const int32_t in_tile = lane > 0 ? s[lane - 1] : -1, before_tile = a.tile_i32[tp];
   const int32_t prev = in_tile > before_tile ? in_tile : before_tile;
   int32_t flip = 0;
@@ -275,162 +203,37 @@ __global__ __launch_bounds__(kT) void bp_sign_kernel(PoseRowsArgs a) {
 // ------------------------------------------------------------------------------------------------------------------ rotations
 template <int D>
 __global__ __launch_bounds__(kT) void bp_smooth_kernel(SmoothRotationsArgs a) {
-  __shared__ double s_t[kStage];
-  __shared__ double s_x[4][kStage];
-  __shared__ uint8_t s_ok[kStage];
-  const int W = a.W, lane = threadIdx.x, r = blockIdx.y;
-  const int64_t F = a.n_frames, f0 = (int64_t)blockIdx.x * kT;
-  const double* row = a.quat + (size_t)r * F * 4;
-  for (int i = lane; i < kT + 2 * W; i += kT) {  // staged index i = frame f0 - W + i
-    const int64_t g = f0 - W + i;
-    double tv = 0.0, x[4] = {0.0, 0.0, 0.0, 0.0};
-    int bits = 0;
-    if (g >= 0 && g < F) {
-      tv = a.t[g];
-#pragma unroll
-      for (int k = 0; k < 4; k++) x[k] = row[4 * g + k];
-      if (a.good[g]) bits = finite1(x[0]) && finite1(x[1]) && finite1(x[2]) && finite1(x[3]) ? kGood | kPresent : kGood;
-    }
-    s_t[i] = tv;
-#pragma unroll
-    for (int k = 0; k < 4; k++) s_x[k][i] = x[k];
-    s_ok[i] = (uint8_t)bits;
-  }
-  __syncthreads();
-  const int64_t f = f0 + lane;
+  __shared__ WfStage<4> s;
+  const int r = blockIdx.y;
+  const int64_t F = a.n_frames, f0 = (int64_t)blockIdx.x * kT, f = f0 + threadIdx.x;
+  wf_stage<4>(a, a.quat + (size_t)r * F * 4, f0, s);
   if (f >= F) return;
 
   const double nan = __builtin_nan("");
-  const int c = lane + W;  // this lane's frame among the staged ones; its window is the staged frames lane .. lane + 2 W
-  const double tf = s_t[c];
-  int n = 0, flag = 0;
-  double out[8];           // quat_s, omega, res
+  const int c = threadIdx.x + a.W;  // this lane's frame among the staged ones
+  double out[8];                    // quat_s, omega, res
 #pragma unroll
   for (int i = 0; i < 8; i++) out[i] = nan;
-  double h = 0.0;
-  if (!(s_ok[c] & kGood)) {
-    flag = kTsBadTime;
-  } else {
-    int ja = 0, jb = 0;    // offsets of the nearest present frames below and above, 0 = none in the window
-    bool sa = false, sb = false;
-    for (int j = -W; j <= W; j++) {
-      if (!(s_ok[c + j] & kPresent)) continue;
-      const double as = fabs(s_t[c + j] - tf);
-      const bool in = as <= a.span;
-      if (in) {
-        n++;
-        h = as > h ? as : h;
-      }
-      if (j < 0) {
-        ja = j;
-        sa = in;
-      } else if (j > 0 && jb == 0) {
-        jb = j;
-        sb = in;
-      }
-    }
-    const bool present = s_ok[c] & kPresent;
-    const bool fillable = !present && a.max_gap > 0 && ja != 0 && jb != 0 && jb - ja - 1 <= a.max_gap && sa && sb;
-    if (!present && !fillable) {
-      flag = 0;
-    } else if (n < a.n_min) {
-      flag = kTsFew;
+  int n;
+  double h, cf[D + 1][4];
+  int flag = wf_fit<4, D>(a, s, c, n, h, cf);
+  if (flag & (kTsSmoothed | kTsFilled)) {
+    const double pw = cf[0][0], px = cf[0][1], py = cf[0][2], pz = cf[0][3];
+    const double n2 = ((pw * pw + px * px) + py * py) + pz * pz;
+    if (!(n2 > 0.0 && n2 < __builtin_inf())) {
+      flag = kTsSingular;
     } else {
-      double S[2 * D + 1], B[D + 1][4];
-#pragma unroll
-      for (int i = 0; i <= 2 * D; i++) S[i] = 0.0;
-#pragma unroll
-      for (int i = 0; i <= D; i++) B[i][0] = B[i][1] = B[i][2] = B[i][3] = 0.0;
-      for (int j = -W; j <= W; j++) {
-        if (!(s_ok[c + j] & kPresent)) continue;
-        const double s = s_t[c + j] - tf;
-        if (!(fabs(s) <= a.span)) continue;
-        const double u = s / h, x0 = s_x[0][c + j], x1 = s_x[1][c + j], x2 = s_x[2][c + j], x3 = s_x[3][c + j];
-        double p = 1.0;
-#pragma unroll
-        for (int i = 0; i <= 2 * D; i++) {
-          S[i] = S[i] + p;
-          if (i <= D) {
-            B[i][0] = B[i][0] + p * x0;
-            B[i][1] = B[i][1] + p * x1;
-            B[i][2] = B[i][2] + p * x2;
-            B[i][3] = B[i][3] + p * x3;
-          }
-          p = p * u;
-        }
-      }
-      // A_ij = S_{i+j} = L L^T, row by row
-      double L[D + 1][D + 1];
-      bool ok = true;
-#pragma unroll
-      for (int i = 0; i <= D; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-          double s = S[i + j];
-#pragma unroll
-          for (int k = 0; k < j; k++) s = s - L[i][k] * L[j][k];
-          if (j == i) {
-            if (!(s > 0.0 && s < __builtin_inf())) ok = false;
-            L[i][i] = sqrt(s);
-          } else {
-            L[i][j] = s / L[j][j];
-          }
-        }
-      if (!ok) {
-        flag = kTsSingular;
-      } else {
-        double cf[D + 1][4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          double y[D + 1];
-#pragma unroll
-          for (int i = 0; i <= D; i++) {
-            double s = B[i][k];
-#pragma unroll
-            for (int m = 0; m < i; m++) s = s - L[i][m] * y[m];
-            y[i] = s / L[i][i];
-          }
-#pragma unroll
-          for (int i = D; i >= 0; i--) {
-            double s = y[i];
-#pragma unroll
-            for (int m = i + 1; m <= D; m++) s = s - L[m][i] * cf[m][k];
-            cf[i][k] = s / L[i][i];
-          }
-        }
-        const double pw = cf[0][0], px = cf[0][1], py = cf[0][2], pz = cf[0][3];
-        const double n2 = ((pw * pw + px * px) + py * py) + pz * pz;
-        if (!(n2 > 0.0 && n2 < __builtin_inf())) {
-          flag = kTsSingular;
-        } else {
-          flag = present ? kTsSmoothed : kTsFilled;
-          double ss = 0.0;
-          for (int j = -W; j <= W; j++) {
-            if (!(s_ok[c + j] & kPresent)) continue;
-            const double s = s_t[c + j] - tf;
-            if (!(fabs(s) <= a.span)) continue;
-            const double u = s / h;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-              double q = cf[D][k];
-#pragma unroll
-              for (int i = D - 1; i >= 0; i--) q = q * u + cf[i][k];
-              const double e = s_x[k][c + j] - q;
-              ss = ss + e * e;
-            }
-          }
-          const double nq = sqrt(n2);
-          const double dw = cf[1][0] / h, dx = cf[1][1] / h, dy = cf[1][2] / h, dz = cf[1][3] / h;
-          out[0] = pw / nq;
-          out[1] = px / nq;
-          out[2] = py / nq;
-          out[3] = pz / nq;
-          out[4] = (2.0 * ((pw * dx - dw * px) - (dy * pz - dz * py))) / n2;
-          out[5] = (2.0 * ((pw * dy - dw * py) - (dz * px - dx * pz))) / n2;
-          out[6] = (2.0 * ((pw * dz - dw * pz) - (dx * py - dy * px))) / n2;
-          out[7] = sqrt(ss / (double)(4 * n));
-        }
-      }
+      const double ss = wf_residual<4, D>(a, s, c, h, cf);
+      const double nq = sqrt(n2);
+      const double dw = cf[1][0] / h, dx = cf[1][1] / h, dy = cf[1][2] / h, dz = cf[1][3] / h;
+      out[0] = pw / nq;
+      out[1] = px / nq;
+      out[2] = py / nq;
+      out[3] = pz / nq;
+      out[4] = (2.0 * ((pw * dx - dw * px) - (dy * pz - dz * py))) / n2;
+      out[5] = (2.0 * ((pw * dy - dw * py) - (dz * px - dx * pz))) / n2;
+      out[6] = (2.0 * ((pw * dz - dw * pz) - (dx * py - dy * px))) / n2;
+      out[7] = sqrt(ss / (double)(4 * n));
     }
   }
   const size_t o = (size_t)r * F + f;
@@ -479,15 +282,7 @@ __global__ __launch_bounds__(kT) void bp_fill_kernel(FillRowsArgs a) {
       } else if (a.flag_s && a.flag_s[p] == kTsFilled) {
         const double qw = a.quat_s[4 * p], qx = a.quat_s[4 * p + 1], qy = a.quat_s[4 * p + 2], qz = a.quat_s[4 * p + 3];
         double R[9];
-        R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
-        R[1] = 2.0 * (qx * qy - qw * qz);
-        R[2] = 2.0 * (qx * qz + qw * qy);
-        R[3] = 2.0 * (qx * qy + qw * qz);
-        R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
-        R[5] = 2.0 * (qy * qz - qw * qx);
-        R[6] = 2.0 * (qx * qz - qw * qy);
-        R[7] = 2.0 * (qy * qz + qw * qx);
-        R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+        rb_quat_to_R(qw, qx, qy, qz, R);
 #pragma unroll
         for (int i = 0; i < 3; i++) x[i] = ((R[3 * i] * q[0] + R[3 * i + 1] * q[1]) + R[3 * i + 2] * q[2]) + a.pos_s[3 * p + i];
         src = kBpSrcRigidFilled;
@@ -519,11 +314,11 @@ hipError_t launch_pose_rows(const PoseRowsArgs& a, hipStream_t stream) {
   hipError_t e;
   hipLaunchKernelGGL(bp_pose_kernel, grid, block, 0, stream, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bp_tile_scan_kernel<OpMax>, per_body, block, 0, stream, a.tile_i32, P);
+  hipLaunchKernelGGL(tile_scan_kernel<OpMaxI32>, per_body, block, 0, stream, a.tile_i32, P);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(bp_flip_kernel, grid, block, 0, stream, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bp_tile_scan_kernel<OpXor>, per_body, block, 0, stream, a.tile_i32, P);
+  hipLaunchKernelGGL(tile_scan_kernel<OpXor>, per_body, block, 0, stream, a.tile_i32, P);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(bp_sign_kernel, grid, block, 0, stream, a);
   return hipGetLastError();

@@ -48,13 +48,6 @@ void posable_mask(int n, const double (*q)[3], unsigned long long mask[4]) {
   }
 }
 
-int rows_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int R) {
-  if (n_frames < 1) return ctx->fail(MOCAP_E_ARG, "%s: n_frames must be at least 1", who);
-  if (R < 1 || R > MOCAP_TS_MAX_ROWS) return ctx->fail(MOCAP_E_ARG, "%s: R must be 1 .. %d", who, MOCAP_TS_MAX_ROWS);
-  if (n_frames > ((int64_t)1 << 31) / R) return ctx->fail(MOCAP_E_ARG, "%s: R * n_frames must be at most 2^31", who);
-  return MOCAP_OK;
-}
-
 // the common body description, checked and tabulated
 int bodies_table(mocap_ctx* ctx, const char* who, int R, int B, const int32_t* n_markers, const int32_t* rows, const double* markers,
                  std::vector<BpBody>& table) {
@@ -123,29 +116,13 @@ int rot_check(mocap_ctx* ctx, int64_t n_frames, int B, const double* t, const do
   if (n_frames < 1) return ctx->fail(MOCAP_E_ARG, "%s: n_frames must be at least 1", who);
   if (B < 1 || B > kBpMaxBodies) return ctx->fail(MOCAP_E_ARG, "%s: B must be 1 .. %d", who, kBpMaxBodies);
   if (n_frames > ((int64_t)1 << 31) / B) return ctx->fail(MOCAP_E_ARG, "%s: B * n_frames must be at most 2^31", who);
-  if (degree < 1 || degree > 3) return ctx->fail(MOCAP_E_ARG, "%s: degree must be 1, 2 or 3", who);
-  if (W < 1 || W > MOCAP_TS_MAX_HALF_WINDOW) return ctx->fail(MOCAP_E_ARG, "%s: W must be 1 .. %d", who, MOCAP_TS_MAX_HALF_WINDOW);
-  if (!(span > 0.0)) return ctx->fail(MOCAP_E_ARG, "%s: span must be > 0 (+inf = none)", who);
-  if (n_min < degree + 1 || n_min > 2 * W + 1) return ctx->fail(MOCAP_E_ARG, "%s: n_min must be degree + 1 .. 2 W + 1", who);
-  if (max_gap < 0 || max_gap > W) return ctx->fail(MOCAP_E_ARG, "%s: max_gap must be 0 .. W", who);
+  if (int rc = window_check(ctx, who, degree, W, span, n_min, max_gap)) return rc;
   if (!t || !quat || !quat_s || !omega || !res || !n_used || !flag) return ctx->fail(MOCAP_E_ARG, "%s: null buffer", who);
   return MOCAP_OK;
 }
 
 int rot_dev_locked(mocap_ctx* ctx, SmoothRotationsArgs a) {
-  SmoothTracksArgs g{};  // the good-time launches read n_frames and t, and write tile_max and good
-  g.n_frames = a.n_frames;
-  g.t = a.t;
-  auto lay = [&](void* base) {
-    Carver c(base);
-    g.tile_max = c.take<double>((size_t)ts_tiles(a.n_frames));
-    g.good = c.take<uint8_t>((size_t)a.n_frames);
-    return c.off;
-  };
-  if (ctx->calib_ws.reserve(lay(nullptr))) return ctx->fail(MOCAP_E_HIP, "hipMalloc(body trajectories workspace) failed");
-  lay(ctx->calib_ws.ptr);
-  a.good = g.good;
-  HIP_TRY(ctx, launch_good_times(g, ctx->stream));
+  if (int rc = good_times_locked(ctx, "body trajectories workspace", a.n_frames, a.t, &a.good)) return rc;
   HIP_TRY(ctx, launch_smooth_rotations(a, ctx->stream));
   return MOCAP_OK;
 }

@@ -1,11 +1,15 @@
 // rb_pose.hpp -- the pose of an assignment (include/mocap_core.h, "rigid bodies": centroids, cross-covariance, Horn's 4 x 4
-// matrix, cyclic Jacobi, quaternion -> R, t, rms in centred coordinates) as a function, for the body tracker (body_track.hip).
-// The arithmetic, operation for operation, is that of the per-frame search's pose block (rigid_body.hip), which keeps its own
-// text: behind a function boundary that kernel, tuned to 128 registers, spilled 632 instead of 552 B and ran 2 % longer
-// (7.13 against 6.98 ms per 100 000 frames).  The same operands in the same order give the same bits: the tracker's SEARCH poses
-// are compared byte for byte with the search's own outputs (tests/test_gpu_body_track.py).  A few hundred wave-uniform
-// operations evaluated redundantly by every lane.  FP64 throughout, no fused operations (-ffp-contract=off is the build's
-// rule).  Device code only.
+// matrix, cyclic Jacobi, quaternion -> R, t, rms in centred coordinates) as a function, for the body tracker (body_track.hip),
+// and its middle as small functions -- rb_horn_matrix, rb_jacobi4, rb_top_quat, rb_quat_to_R -- for the kernels that pose one
+// lane per frame from points of their own (body_learn.hip, body_session.hip).  They are separate functions on purpose: one
+// function around matrix, sweep, eigenvector and R cost the session's pose kernel 14 registers (120 -> 134, across the 128
+// boundary: 4 -> 3 waves per SIMD); called one after the other they cost none.
+// One copy of this text remains, in the per-frame search's pose block (rigid_body.hip), Jacobi sweep included: behind a function
+// boundary that kernel, tuned to 128 registers, spilled 632 instead of 552 B and ran 2 % longer (7.13 against 6.98 ms per
+// 100 000 frames), and nobody has a cheaper measurement since.  The arithmetic is the same operation for operation, and the same
+// operands in the same order give the same bits: the tracker's SEARCH poses are compared byte for byte with the search's own
+// outputs (tests/test_gpu_body_track.py).  A few hundred wave-uniform operations evaluated redundantly by every lane.  FP64
+// throughout, no fused operations (-ffp-contract=off is the build's rule).  Device code only.
 #pragma once
 #include "kernels.hpp"
 
@@ -64,6 +68,55 @@ __device__ __forceinline__ void rb_jacobi4(double A[4][4], double V[4][4]) {
   }
 }
 
+// Horn's matrix of the cross-covariance S[i][j] = sum (q - qb)_i (p - pb)_j: its top eigenvector is the rotation's quaternion
+__device__ __forceinline__ void rb_horn_matrix(const double S[3][3], double A[4][4]) {
+  A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
+  A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
+  A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
+  A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+  A[0][1] = A[1][0] = S[1][2] - S[2][1];
+  A[0][2] = A[2][0] = S[2][0] - S[0][2];
+  A[0][3] = A[3][0] = S[0][1] - S[1][0];
+  A[1][2] = A[2][1] = S[0][1] + S[1][0];
+  A[1][3] = A[3][1] = S[2][0] + S[0][2];
+  A[2][3] = A[3][2] = S[1][2] + S[2][1];
+}
+
+// the eigenvector of the largest eigenvalue as a unit quaternion: A, V as rb_jacobi4 leaves them (the first of equal eigenvalues)
+__device__ __forceinline__ void rb_top_quat(const double A[4][4], const double V[4][4], double& qw, double& qx, double& qy, double& qz) {
+  double lam = A[0][0];
+  qw = V[0][0];
+  qx = V[1][0];
+  qy = V[2][0];
+  qz = V[3][0];
+#pragma unroll
+  for (int k = 1; k < 4; k++)
+    if (A[k][k] > lam) {
+      lam = A[k][k];
+      qw = V[0][k];
+      qx = V[1][k];
+      qy = V[2][k];
+      qz = V[3][k];
+    }
+  const double qn = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
+  qw = qw / qn;
+  qx = qx / qn;
+  qy = qy / qn;
+  qz = qz / qn;
+}
+
+__device__ __forceinline__ void rb_quat_to_R(const double qw, const double qx, const double qy, const double qz, double R[9]) {
+  R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
+  R[1] = 2.0 * (qx * qy - qw * qz);
+  R[2] = 2.0 * (qx * qz + qw * qy);
+  R[3] = 2.0 * (qx * qy + qw * qz);
+  R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
+  R[5] = 2.0 * (qy * qz - qw * qx);
+  R[6] = 2.0 * (qx * qz - qw * qy);
+  R[7] = 2.0 * (qy * qz + qw * qx);
+  R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+}
+
 // The pose of the assignment `tuple` (one byte per marker, point index + 1, 0 = unassigned, marker 0 in the top byte; `count` of
 // them assigned, >= 3) of body `mdl` among the wave's points (px, py, pz: lane = point).  mq, wp: two rows of [kRbMaxMarkers][3]
 // doubles of the wave's own LDS -- the assigned model points and their world points, indexed by the marker.  -> asg (point index
@@ -114,41 +167,11 @@ __device__ __forceinline__ unsigned long long rb_pose(const RigidBodyModel* mdl,
         for (int j = 0; j < 3; j++) S[i][j] = S[i][j] + mq[m][i] * wp[m][j];
     }
   double A[4][4], V[4][4];
-  A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
-  A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
-  A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
-  A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
-  A[0][1] = A[1][0] = S[1][2] - S[2][1];
-  A[0][2] = A[2][0] = S[2][0] - S[0][2];
-  A[0][3] = A[3][0] = S[0][1] - S[1][0];
-  A[1][2] = A[2][1] = S[0][1] + S[1][0];
-  A[1][3] = A[3][1] = S[2][0] + S[0][2];
-  A[2][3] = A[3][2] = S[1][2] + S[2][1];
+  rb_horn_matrix(S, A);
   rb_jacobi4(A, V);
-  double lam = A[0][0], qw = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
-#pragma unroll
-  for (int k = 1; k < 4; k++)
-    if (A[k][k] > lam) {
-      lam = A[k][k];
-      qw = V[0][k];
-      qx = V[1][k];
-      qy = V[2][k];
-      qz = V[3][k];
-    }
-  const double qn = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
-  qw = qw / qn;
-  qx = qx / qn;
-  qy = qy / qn;
-  qz = qz / qn;
-  R[0] = ((qw * qw + qx * qx) - qy * qy) - qz * qz;
-  R[1] = 2.0 * (qx * qy - qw * qz);
-  R[2] = 2.0 * (qx * qz + qw * qy);
-  R[3] = 2.0 * (qx * qy + qw * qz);
-  R[4] = ((qw * qw - qx * qx) + qy * qy) - qz * qz;
-  R[5] = 2.0 * (qy * qz - qw * qx);
-  R[6] = 2.0 * (qx * qz - qw * qy);
-  R[7] = 2.0 * (qy * qz + qw * qx);
-  R[8] = ((qw * qw - qx * qx) - qy * qy) + qz * qz;
+  double qw, qx, qy, qz;
+  rb_top_quat(A, V, qw, qx, qy, qz);
+  rb_quat_to_R(qw, qx, qy, qz, R);
 #pragma unroll
   for (int i = 0; i < 3; i++) t[i] = pb[i] - ((R[3 * i] * qb[0] + R[3 * i + 1] * qb[1]) + R[3 * i + 2] * qb[2]);
   // residuals in centred coordinates: R q_i + t - p_i = R (q_i - qb) - (p_i - pb)

@@ -22,6 +22,7 @@
 #include "rigid_groups.hpp"
 
 #include "mocap_device.hpp"
+#include "track_smooth.hpp"
 #include "tree_fold.hpp"
 
 namespace mocap {
@@ -32,8 +33,6 @@ constexpr int kT = kRgTile, kB = kRgBlock, kS = kRgSlots;
 constexpr int kWords = kRgMaxRows / 32;  // words of a row of the edge matrix
 constexpr int kJumps = 8;                // 2^8 >= kRgMaxRows
 static_assert(kT == kCalibThreads && kS == 64 && (1 << kJumps) >= kRgMaxRows, "the tile is tree_fold.hpp's, a block pair is one wave wide");
-
-__device__ __forceinline__ bool finite1(double v) { return fabs(v) < __builtin_inf(); }  // false for NaN
 
 // an unsigned key that orders like the double (finite values only reach it)
 __device__ __forceinline__ unsigned long long key_of(double v) {

@@ -15,7 +15,11 @@ using namespace mocap;
 static_assert(kTsMaxRows == MOCAP_TS_MAX_ROWS && kTsMaxHalfWindow == MOCAP_TS_MAX_HALF_WINDOW, "limits");
 static_assert(kTsMaxPoints == MOCAP_MT_MAX_POINTS, "K_max is the marker tracker's");
 
-namespace {
+static_assert(kTsSmoothed == MOCAP_TS_SMOOTHED && kTsFilled == MOCAP_TS_FILLED && kTsFew == MOCAP_TS_FEW &&
+                  kTsSingular == MOCAP_TS_SINGULAR && kTsBadTime == MOCAP_TS_BAD_TIME,
+              "flags");
+
+namespace mocap {
 
 int rows_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int R) {
   if (n_frames < 1) return ctx->fail(MOCAP_E_ARG, "%s: n_frames must be at least 1", who);
@@ -23,6 +27,34 @@ int rows_check(mocap_ctx* ctx, const char* who, int64_t n_frames, int R) {
   if (n_frames > ((int64_t)1 << 31) / R) return ctx->fail(MOCAP_E_ARG, "%s: R * n_frames must be at most 2^31", who);
   return MOCAP_OK;
 }
+
+int window_check(mocap_ctx* ctx, const char* who, int degree, int W, double span, int n_min, int max_gap) {
+  if (degree < 1 || degree > 3) return ctx->fail(MOCAP_E_ARG, "%s: degree must be 1, 2 or 3", who);
+  if (W < 1 || W > MOCAP_TS_MAX_HALF_WINDOW) return ctx->fail(MOCAP_E_ARG, "%s: W must be 1 .. %d", who, MOCAP_TS_MAX_HALF_WINDOW);
+  if (!(span > 0.0)) return ctx->fail(MOCAP_E_ARG, "%s: span must be > 0 (+inf = none)", who);
+  if (n_min < degree + 1 || n_min > 2 * W + 1) return ctx->fail(MOCAP_E_ARG, "%s: n_min must be degree + 1 .. 2 W + 1", who);
+  if (max_gap < 0 || max_gap > W) return ctx->fail(MOCAP_E_ARG, "%s: max_gap must be 0 .. W", who);
+  return MOCAP_OK;
+}
+
+int good_times_locked(mocap_ctx* ctx, const char* ws, int64_t n_frames, const double* t, const uint8_t** good) {
+  GoodTimesArgs g{n_frames, t, nullptr, nullptr};
+  auto lay = [&](void* base) {
+    Carver c(base);
+    g.tile_max = c.take<double>((size_t)ts_tiles(n_frames));
+    g.good = c.take<uint8_t>((size_t)n_frames);
+    return c.off;
+  };
+  if (ctx->calib_ws.reserve(lay(nullptr))) return ctx->fail(MOCAP_E_HIP, "hipMalloc(%s) failed", ws);
+  lay(ctx->calib_ws.ptr);
+  *good = g.good;
+  HIP_TRY(ctx, launch_good_times(g, ctx->stream));
+  return MOCAP_OK;
+}
+
+}  // namespace mocap
+
+namespace {
 
 int gather_check(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int32_t* n_pts, const int32_t* id, int n_ids,
                  const int32_t* relabel, int R, const double* traj) {
@@ -39,25 +71,14 @@ int smooth_check(mocap_ctx* ctx, int64_t n_frames, int R, const double* t, const
                  const int32_t* n_used, const int32_t* flag) {
   const char* who = "mocap_smooth_tracks";
   if (int rc = rows_check(ctx, who, n_frames, R)) return rc;
-  if (degree < 1 || degree > 3) return ctx->fail(MOCAP_E_ARG, "%s: degree must be 1, 2 or 3", who);
-  if (W < 1 || W > MOCAP_TS_MAX_HALF_WINDOW) return ctx->fail(MOCAP_E_ARG, "%s: W must be 1 .. %d", who, MOCAP_TS_MAX_HALF_WINDOW);
-  if (!(span > 0.0)) return ctx->fail(MOCAP_E_ARG, "%s: span must be > 0 (+inf = none)", who);
-  if (n_min < degree + 1 || n_min > 2 * W + 1) return ctx->fail(MOCAP_E_ARG, "%s: n_min must be degree + 1 .. 2 W + 1", who);
-  if (max_gap < 0 || max_gap > W) return ctx->fail(MOCAP_E_ARG, "%s: max_gap must be 0 .. W", who);
+  if (int rc = window_check(ctx, who, degree, W, span, n_min, max_gap)) return rc;
   if (!t || !traj || !pos || !vel || !acc || !res || !n_used || !flag) return ctx->fail(MOCAP_E_ARG, "%s: null buffer", who);
   return MOCAP_OK;
 }
 
 // (arguments checked; context lock held by the caller; every pointer device-accessible)
 int smooth_dev_locked(mocap_ctx* ctx, SmoothTracksArgs a) {
-  auto lay = [&](void* base) {
-    Carver c(base);
-    a.tile_max = c.take<double>((size_t)ts_tiles(a.n_frames));
-    a.good = c.take<uint8_t>((size_t)a.n_frames);
-    return c.off;
-  };
-  if (ctx->calib_ws.reserve(lay(nullptr))) return ctx->fail(MOCAP_E_HIP, "hipMalloc(trajectory workspace) failed");
-  lay(ctx->calib_ws.ptr);
+  if (int rc = good_times_locked(ctx, "trajectory workspace", a.n_frames, a.t, &a.good)) return rc;
   HIP_TRY(ctx, launch_smooth_tracks(a, ctx->stream));
   return MOCAP_OK;
 }
@@ -118,7 +139,7 @@ extern "C" int mocap_smooth_tracks_dev(mocap_ctx* ctx, int64_t n_frames, int R, 
   if (int rc = smooth_check(ctx, n_frames, R, d_t, d_traj, degree, W, span, n_min, max_gap, d_pos, d_vel, d_acc, d_res, d_n_used, d_flag))
     return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const SmoothTracksArgs a{n_frames, R, degree, W, n_min, max_gap, span, d_t, d_traj, nullptr, nullptr,
+  const SmoothTracksArgs a{n_frames, R, degree, W, n_min, max_gap, span, d_t, d_traj, nullptr,
                            d_pos, d_vel, d_acc, d_res, d_n_used, d_flag};
   const int rc = smooth_dev_locked(ctx, a);
   return rc ? rc : ctx->mark_enqueued();

@@ -30,9 +30,6 @@ constexpr int kMaxLanes = kTsMaxRows;
 constexpr int kJumpRounds = 10;      // 2^10 >= kTsMaxRows
 static_assert((1 << kJumpRounds) >= kTsMaxRows, "pointer jumping must reach the head of the longest chain");
 
-__device__ __forceinline__ bool finite1(double v) { return fabs(v) < __builtin_inf(); }  // false for NaN
-__device__ __forceinline__ bool finite3(const double* p) { return finite1(p[0]) && finite1(p[1]) && finite1(p[2]); }
-
 // ------------------------------------------------------------------------------------------------------------------ extents
 __global__ __launch_bounds__(kT) void st_extent_seed_kernel(StitchTracksArgs a) {
   const int r = blockIdx.x * kT + threadIdx.x;
@@ -47,7 +44,7 @@ __global__ __launch_bounds__(kT) void st_extent_kernel(StitchTracksArgs a) {
   const int lane = threadIdx.x, r = blockIdx.y;
   const int64_t f0 = (int64_t)blockIdx.x * kT, f = f0 + lane;
   bool present = false;
-  if (f < a.n_frames && a.good[f]) present = finite3(a.traj + ((size_t)r * a.n_frames + f) * 3);
+  if (f < a.n_frames && a.good[f]) present = finiteN<3>(a.traj + ((size_t)r * a.n_frames + f) * 3);
   const unsigned long long m = __ballot(present);
   if ((lane & 63) == 0) {
     const int w = lane >> 6;
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(64) void st_model_kernel(StitchTracksArgs a) {
     s_x[0][i] = x[0];
     s_x[1][i] = x[1];
     s_x[2][i] = x[2];
-    s_ok[i] = a.good[g] && finite3(x);
+    s_ok[i] = a.good[g] && finiteN<3>(x);
   }
   __syncthreads();
   if (lane != 0) return;
@@ -301,11 +298,7 @@ __global__ __launch_bounds__(kMaxLanes) void st_assoc_kernel(StitchTracksArgs a)
 }  // namespace
 
 hipError_t launch_stitch_tracks(const StitchTracksArgs& a, hipStream_t stream) {
-  SmoothTracksArgs g{};
-  g.n_frames = a.n_frames;
-  g.t = a.t;
-  g.tile_max = a.tile_max;
-  g.good = a.good;
+  const GoodTimesArgs g{a.n_frames, a.t, a.tile_max, a.good};
   hipError_t e;
   if ((e = launch_good_times(g, stream)) != hipSuccess) return e;
   const unsigned R = (unsigned)a.R;
