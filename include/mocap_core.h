@@ -1498,7 +1498,8 @@ int mocap_ba_solve_ex(mocap_ctx* ctx, double* x, int64_t N, const double* obs, d
  * MOCAP_E_NOCAMS without cameras.  MOCAP_E_ARG, every output untouched, for: C or N out of range; a K that is not plain; MOCAP_BAJ_FOCAL
  *   with C = 2; unknown flag bits; huber_px, ftol or lambda negative or not finite; max_iter < 1; a null obs, R, t, X, S or rhs, or a
  *   null fscale with MOCAP_BAJ_FOCAL.
- * Out of scope: lens distortion and the principal point as unknowns, more than 16 cameras, a sparse reduced system. */
+ * Out of scope: lens distortion and the principal point as unknowns (they are unknowns of mocap_ba_lens_solve, "lens calibration"
+ *   below), more than 16 cameras, a sparse reduced system. */
 #define MOCAP_BAJ_MAX_CAMERAS 16
 #define MOCAP_BAJ_MAX_POINTS 131072
 #define MOCAP_BAJ_INFO 12 /* doubles */
@@ -1609,6 +1610,107 @@ int mocap_resect_camera_dev(mocap_ctx* ctx, int64_t N, const double* d_X, const 
 int mocap_resect_hypotheses(mocap_ctx* ctx, int64_t N, const double* X, const double* obs, const double* K, const double* prior_R,
                             const double* prior_t, double threshold_px, int n_hyp, uint64_t seed, int32_t* sample, int32_t* n_sol,
                             double* poses, int32_t* counts);
+
+/* ---------------------------------------------------------------- lens calibration (the core's own contract)
+ * The joint bundle adjustment above with the full lens model: beside the poses and the points, per camera fx, fy, cx, cy, k1, k2, p1,
+ * p2 can be unknowns -- intrinsic_matrix and distortion_coef of camera-params.json from the capture-points wand wave alone, where the
+ * reference's author needed an OpenCV checkerboard session.  Opt-in and beside mocap_ba_joint_*: with nothing called nothing changes.
+ * THE CAPTURE MUST FILL THE IMAGES (markers out to the corners of every camera's picture) and must be taken RAW, with distortion_coef
+ * = 0 in mocap_set_image_params: points that cover only the middle of the pictures do not determine a lens.
+ *
+ * Cameras.  mocap_set_cameras is NOT needed and NOT read: the camera count C, K [C][9] (row-major, plain: [[fx,0,cx],[0,fy,cy],[0,0,1]],
+ *   fx, fy finite and > 0, cx, cy finite) and dist [C][5] (OpenCV's order k1 k2 p1 p2 k3, as camera-params.json has it; finite) are
+ *   arguments, in and out like the poses R [C][9], t [C][3].  Camera 0's pose is fixed and NEVER written.  k3 is part of the model and
+ *   never an unknown.  2 <= C <= MOCAP_BAL_MAX_CAMERAS; obs [N][C][2] with NaN for unseen; 1 <= N <= MOCAP_BAL_MAX_POINTS (the
+ *   workspace, two sets of [3 N][NP] doubles and 256 Gram slices, is 0.8 GB at N = 65 536 and NP = 224: the order of the joint
+ *   bundle adjustment's at its own limits, whose buffers it shares).
+ * Unknowns.  Columns 6 (c - 1) .. + 5 of camera c >= 1 as in the joint bundle adjustment.  flags select pairs of intrinsics, for EVERY
+ *   camera (camera 0 included), in this order:
+ *     MOCAP_BAL_FOCAL       fx, fy    each with its own scale:  f <- f (1 + delta); the column is the derivative at the current value
+ *     MOCAP_BAL_CENTRE      cx, cy    additive, pixels
+ *     MOCAP_BAL_RADIAL      k1, k2    additive
+ *     MOCAP_BAL_TANGENTIAL  p1, p2    additive
+ *   q = 2 x (flags set) <= 8 columns per camera: column 6 (C - 1) + q c + (the parameter's place among the camera's q).  Any flag
+ *   needs C >= 3.  n_c = 6 (C - 1) + q C <= 218;  NP = n_c + 1 rounded up to a multiple of 16 (<= 224).  flags = 0: the joint bundle
+ *   adjustment with a fixed lens in the model.
+ * Points.  Participation is the joint bundle adjustment's, word for word; the DLT start is taken on P_c = K_c [R_c | t_c] of the K as it
+ *   came and IGNORES the lens.
+ * One view of a point at X, camera (R, t, fx, fy, cx, cy, k1, k2, p1, p2, k3), observation (u, v), huber_px = d:
+ *   P_i = (R_i0 X0 + R_i1 X1) + R_i2 X2;  Y_i = P_i + t_i;  USED iff Y2 is finite and > 0.  x = Y0 / Y2, y = Y1 / Y2.
+ *   The lens (OpenCV's forward model, operation by operation as mocap_core.synth.distort_pixels):
+ *     r2 = x x + y y;  kr = 1 + ((k3 r2 + k2) r2 + k1) r2;
+ *     xd = (x kr + ((2 p1) x) y) + p2 (r2 + (2 x) x);   yd = (y kr + p1 (r2 + (2 y) y)) + ((2 p2) x) y
+ *   and its Jacobian in (x, y), which is symmetric:  dk = ((3 k3) r2 + 2 k2) r2 + k1,  dk2 = 2 dk,
+ *     Jxx = (kr + (dk2 x) x) + ((2 p1) y + (6 p2) x);  Jxy = (dk2 x) y + ((2 p1) x + (2 p2) y);  Jyy = (kr + (dk2 y) y) + ((6 p1) y + (2 p2) x)
+ *   ru = (fx xd + cx) - u, rv = (fy yd + cy) - v;  s2, s, the Huber weight w, rho and sw = sqrt(w) as in the joint bundle adjustment.
+ *   r = (sw ru, sw rv).  gu = sw (fx / Y2), gv = sw (fy / Y2);  the rows of sw dr/dY, no longer sparse:
+ *     du0 = gu Jxx, du1 = gu Jxy, du2 = -(du0 x + du1 y);     dv0 = gv Jxy, dv1 = gv Jyy, dv2 = -(dv0 x + dv1 y)
+ *   B = dr/dX:      Bu[j] = (du0 R_0j + du1 R_1j) + du2 R_2j,   Bv[j] likewise from dv
+ *   A = dr/d(w, t): Au = (du2 P1 - du1 P2,  du0 P2 - du2 P0,  du1 P0 - du0 P1,  du0, du1, du2),   Av likewise from dv
+ *   intrinsics, sfx = sw fx, sfy = sw fy, xr = x r2, yr = y r2, xy2 = (2 x) y   (Au, Av):
+ *     fx (sfx xd, 0)   fy (0, sfy yd)   cx (sw, 0)   cy (0, sw)   k1 (sfx xr, sfy yr)   k2 (sfx (xr r2), sfy (yr r2))
+ *     p1 (sfx xy2, sfy (r2 + (2 y) y))   p2 (sfx (r2 + (2 x) x), sfy xy2)
+ *   A camera's 14 parameters in this order: w 3, t 3, fx, fy, cx, cy, k1, k2, p1, p2.
+ * One linearisation, one iteration, the Marquardt rule, the trial linearised at lam' = max(lam / 10, 1e-12), ACCEPTED / REJECTED,
+ *   lam_0 = 1e-3, the stops, the gauge and the statuses: the joint bundle adjustment's, with 14 parameters per
+ *   camera where it has 7.  Additions:  a trial in which any fx or fy would not be > 0 is REJECTED before it is linearised;  the
+ *   updates are f <- f (1 + delta), every other intrinsic p <- p + delta;  on return K and dist hold the current values of what was an
+ *   unknown, every other entry (k3 always) is not written.  mocap_set_ba_progress is not honoured.
+ *   The gauge multiplies every t and X by |t_1 in| / |t_1 out|: |t_1| comes back as it came to a few ulp (a norm of three rounded
+ *   products), camera 0's pose bit for bit.  With MOCAP_BAL_ST_CAMERA_UNSEEN or MOCAP_BAL_ST_NO_POINTS the call returns 0 with R, t,
+ *   K and dist untouched; X_out IS written: the start (the DLT points of the points that take part, NaN for the others).
+ * Sums.  sum E^T E and sum E^T z through the Gram of mocap_ba_normal_eq as in the joint bundle adjustment (NP up to 224).  A camera's
+ *   block U (upper triangle of 14 x 14) and g_c are 119 sums: the triangle is cut into four ROW BANDS, rows 0-1, 2-4, 5-8 and 9-13 (the
+ *   last also carries the cost and the counters), grid ceil(N / 256) x C x 4, every band recomputing the view; each band goes
+ *   through the project's one tree (one lane per point, lane -> wave by shuffles, wave -> workgroup through LDS in wave order, one
+ *   partial per workgroup, one wave per camera and band folds the slab): the order of every sum is a function of N alone.  No
+ *   floating-point atomics anywhere: two calls on the same input give the same bytes.  All arithmetic is IEEE double, no fused
+ *   operation.  A pass is 6 launches and one host round trip, as in the joint bundle adjustment.
+ *
+ * mocap_ba_lens_normal_eq: ONE linearisation at the given cameras and the given points X [N][3] (NaN rows do not take part), at
+ *   damping `lambda`: S [n_c][n_c], rhs [n_c], *cost (may be NULL), info (may be NULL) as mocap_ba_joint_normal_eq fills them.
+ * mocap_ba_lens_solve: the loop.  X_out [N][3] (may be NULL).  info [MOCAP_BAL_INFO] (may be NULL): the layout of mocap_ba_joint_solve,
+ *   [8] MOCAP_BAL_ST_* (the values of MOCAP_BAJ_ST_*).
+ * MOCAP_E_ARG, every output untouched, for: C or N out of range; a K that is not plain or whose fx, fy are not finite and > 0; a
+ *   cx, cy or distortion coefficient that is not finite; any flag with C = 2; unknown flag bits; huber_px, ftol or lambda negative or
+ *   not finite; max_iter < 1; a null obs, R, t, K, dist, X, S or rhs.
+ *
+ * mocap_undistort_points: raw pixels in [N][C][2] -> ideal pinhole pixels out [N][C][2] under K [C][9], dist [C][5] (checked as
+ *   above; 1 <= C <= MOCAP_BAL_MAX_CAMERAS, 1 <= N <= MOCAP_UNDISTORT_MAX_POINTS), one lane per observation: the same raw capture feeds
+ *   mocap_determine_scale, mocap_acquire_floor, mocap_ba_joint_solve and mocap_resect_camera once the lenses are known.
+ *   x0 = (u - cx) / fx, y0 = (v - cy) / fy;  from (x, y) = (x0, y0), MOCAP_UNDISTORT_NEWTON times:  the lens and its Jacobian at
+ *   (x, y);  ex = xd - x0, ey = yd - y0;  det = Jxx Jyy - Jxy Jxy;  x <- x - (Jyy ex - Jxy ey) / det,  y <- y - (Jxx ey - Jxy ex) / det
+ *   (both from the old x, y).  out = (fx x + cx, fy y + cy).  A NaN in either coordinate gives NaN in both; a camera whose five
+ *   coefficients are all zero has its pixels copied bit for bit.  in and out may be the same buffer.
+ * mocap_undistort_points_dev: the same with in and out as device pointers, on the context's stream; K and dist are host pointers.
+ * Out of scope: k3 and higher-order terms as unknowns, a known-length wand constraint, priors on the intrinsics, skew, more than 16
+ *   cameras, fusing the launches. */
+#define MOCAP_BAL_MAX_CAMERAS 16
+#define MOCAP_BAL_MAX_POINTS 65536
+#define MOCAP_BAL_INFO 12 /* doubles */
+#define MOCAP_UNDISTORT_MAX_POINTS 1048576
+#define MOCAP_UNDISTORT_NEWTON 8
+#define MOCAP_BAL_FOCAL 1u      /* flags: fx, fy of every camera are unknowns */
+#define MOCAP_BAL_CENTRE 2u     /* ... cx, cy */
+#define MOCAP_BAL_RADIAL 4u     /* ... k1, k2 */
+#define MOCAP_BAL_TANGENTIAL 8u /* ... p1, p2 */
+enum {
+  MOCAP_BAL_ST_CAMERA_UNSEEN = 1,   /* a camera has no observation on a participating point: nothing was changed */
+  MOCAP_BAL_ST_NO_POINTS = 2,       /* no point takes part: nothing was changed */
+  MOCAP_BAL_ST_SINGULAR = 4,        /* the reduced system had no Cholesky factor in some pass (that trial was rejected) */
+  MOCAP_BAL_ST_POINT_SINGULAR = 8,  /* some point's V_lambda had no Cholesky factor in some linearisation (the point did not move) */
+  MOCAP_BAL_ST_LAMBDA = 16,         /* stopped because lam > 1e12 */
+  MOCAP_BAL_ST_MAX_ITER = 32,       /* stopped after max_iter passes */
+  MOCAP_BAL_ST_BAD_DEPTH = 64       /* mocap_ba_lens_normal_eq: a view was not used (depth not finite or <= 0) */
+};
+int mocap_ba_lens_normal_eq(mocap_ctx* ctx, int C, int64_t N, const double* obs, const double* R, const double* t, const double* K,
+                            const double* dist, const double* X, uint32_t flags, double huber_px, double lambda, double* S,
+                            double* rhs, double* cost, double* info);
+int mocap_ba_lens_solve(mocap_ctx* ctx, int C, int64_t N, const double* obs, double* R, double* t, double* K, double* dist,
+                        double* X_out, uint32_t flags, double huber_px, double ftol, int max_iter, double* info);
+int mocap_undistort_points(mocap_ctx* ctx, int C, int64_t N, const double* in, const double* K, const double* dist, double* out);
+int mocap_undistort_points_dev(mocap_ctx* ctx, int C, int64_t N, const double* d_in, const double* K, const double* dist,
+                               double* d_out);
 
 #ifdef __cplusplus
 }

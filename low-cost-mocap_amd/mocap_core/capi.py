@@ -73,6 +73,15 @@ BAJ_ST_POINT_SINGULAR = 8 # ... some point's 3 x 3 block had no Cholesky factor 
 BAJ_ST_LAMBDA = 16        # ... stopped because the damping passed 1e12
 BAJ_ST_MAX_ITER = 32      # ... stopped after max_iter passes
 BAJ_ST_BAD_DEPTH = 64     # ... ba_joint_normal_eq: a view was not used (depth not finite or <= 0)
+BAL_MAX_CAMERAS = 16      # mocap_ba_lens_*: cameras at most
+BAL_MAX_POINTS = 65536    # ... points at most
+BAL_INFO = 12             # ... doubles of `info` (the layout of mocap_ba_joint_solve)
+BAL_FOCAL, BAL_CENTRE, BAL_RADIAL, BAL_TANGENTIAL = 1, 2, 4, 8   # ... flags: (fx, fy) / (cx, cy) / (k1, k2) / (p1, p2) of every camera are unknowns
+BAL_REFINE = {"focal": BAL_FOCAL, "centre": BAL_CENTRE, "radial": BAL_RADIAL, "tangential": BAL_TANGENTIAL}
+BAL_ST_CAMERA_UNSEEN, BAL_ST_NO_POINTS, BAL_ST_SINGULAR, BAL_ST_POINT_SINGULAR = 1, 2, 4, 8   # ... status: the values of BAJ_ST_*
+BAL_ST_LAMBDA, BAL_ST_MAX_ITER, BAL_ST_BAD_DEPTH = 16, 32, 64
+UNDISTORT_MAX_POINTS = 1 << 20   # mocap_undistort_points: rows at most
+UNDISTORT_NEWTON = 8      # ... Newton steps per observation
 RESECT_MAX_POINTS = 131072  # mocap_resect_*: rows at most
 RESECT_MAX_HYP = 4096     # ... hypotheses at most
 RESECT_INFO = 12          # ... doubles of `info`
@@ -210,6 +219,10 @@ SIGNATURES = {
     "mocap_resect_camera": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mocap_resect_camera_dev": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mocap_resect_hypotheses": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _u64, _vp, _vp, _vp, _vp]),
+    "mocap_ba_lens_normal_eq": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "mocap_ba_lens_solve": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _i32, _vp]),
+    "mocap_undistort_points": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "mocap_undistort_points_dev": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -1520,6 +1533,114 @@ class MocapCore:
         info = dict(zip(self._BAJ_INFO_KEYS, info.tolist()))
         info["status"] = int(info["status"])
         return R.reshape(-1, 3, 3), t, s, X, info
+
+    # ------------------------------------------------------------------ lens calibration (poses, points and intrinsics together)
+    @staticmethod
+    def _bal_refuse(why):
+        e = MocapError(f"mocap_core error {MOCAP_E_ARG}: lens calibration: {why}")
+        e.code = MOCAP_E_ARG
+        raise e
+
+    @staticmethod
+    def bal_flags(refine):
+        """("focal", "centre", ...) or an integer of BAL_* bits -> the bits."""
+        if isinstance(refine, (int, np.integer)):
+            return int(refine)
+        bits = 0
+        for name in refine:
+            if name not in BAL_REFINE:
+                MocapCore._bal_refuse(f"unknown parameter group {name!r}: {sorted(BAL_REFINE)}")
+            bits |= BAL_REFINE[name]
+        return bits
+
+    def _bal_inputs(self, obs, R, t, K, dist, refine, huber_px):
+        """The checks that need no device, as the library makes them (MOCAP_E_ARG), and the arrays in the C layout."""
+        R = np.array(R, dtype=np.float64, order="C").reshape(-1, 9)
+        C = R.shape[0]
+        t = np.array(t, dtype=np.float64, order="C").reshape(-1, 3)
+        K = np.array(K, dtype=np.float64, order="C").reshape(-1, 9)
+        dist = np.array(dist, dtype=np.float64, order="C").reshape(-1, 5)
+        flags = self.bal_flags(refine)
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if not 2 <= C <= BAL_MAX_CAMERAS:
+            self._bal_refuse(f"{C} cameras, 2 .. {BAL_MAX_CAMERAS} are taken")
+        if not (t.shape[0] == C and K.shape[0] == C and dist.shape[0] == C):
+            self._bal_refuse(f"t, K and dist must hold {C} cameras like R")
+        if obs.size % (2 * C) or not 1 <= obs.size // (2 * C) <= BAL_MAX_POINTS:
+            self._bal_refuse(f"obs must be [N][{C}][2] with 1 <= N <= {BAL_MAX_POINTS}")
+        if flags & ~15:
+            self._bal_refuse(f"unknown flag bits {flags:#x}")
+        if flags and C == 2:
+            self._bal_refuse("intrinsics as unknowns need at least 3 cameras")
+        if not (np.isfinite(huber_px) and huber_px >= 0):
+            self._bal_refuse("huber_px must be finite and >= 0")
+        plain = (K[:, [1, 3, 6, 7]] == 0).all() and (K[:, 8] == 1).all() and np.isfinite(K).all() and (K[:, [0, 4]] > 0).all()
+        if not plain or not np.isfinite(dist).all():
+            self._bal_refuse("every K must be [[fx,0,cx],[0,fy,cy],[0,0,1]] with fx, fy > 0, every coefficient finite")
+        return obs.reshape(-1, C, 2), R, t, K, dist, flags
+
+    def ba_lens_normal_eq(self, obs, R, t, K, dist, X, refine=(), huber_px=0.0, lam=0.0):
+        """mocap_ba_lens_normal_eq: one linearisation of the lens calibration at the cameras (R [C][3][3], t [C][3], K [C][3][3],
+        dist [C][5] = k1 k2 p1 p2 k3) and the points X [N][3] (NaN rows do not take part) -> {"S" [n_c][n_c], "rhs" [n_c], "cost",
+        "info"}: the Schur-reduced camera system at damping `lam`; columns (omega, t) per camera 1 .. C-1, then per camera 0 .. C-1
+        the pairs named in `refine` in the order focal, centre, radial, tangential.  Needs no set_cameras."""
+        obs, R, t, K, dist, flags = self._bal_inputs(obs, R, t, K, dist, refine, huber_px)
+        N, C = obs.shape[:2]
+        if not (np.isfinite(lam) and lam >= 0):
+            self._bal_refuse("lam must be finite and >= 0")
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(N, 3)
+        n_c = 6 * (C - 1) + 2 * bin(flags).count("1") * C
+        S = np.zeros((n_c, n_c))
+        rhs = np.zeros(n_c)
+        cost = ctypes.c_double()
+        info = np.zeros(BAL_INFO)
+        self._check(self.lib.mocap_ba_lens_normal_eq(self._h, C, N, _p(obs), _p(R), _p(t), _p(K), _p(dist), _p(X), flags, float(huber_px),
+                                                     float(lam), _p(S), _p(rhs), ctypes.addressof(cost), _p(info)))
+        return {"S": S, "rhs": rhs, "cost": cost.value, "info": dict(zip(self._BAJ_INFO_KEYS, info.tolist()))}
+
+    def ba_lens_solve(self, obs, R, t, K, dist, refine=("focal", "centre", "radial"), huber_px=0.0, ftol=1e-10, max_iter=100):
+        """mocap_ba_lens_solve: Levenberg-Marquardt over the poses of cameras 1 .. C-1, every point and the intrinsics named in
+        `refine` of every camera -> (R [C][3][3], t [C][3], K [C][3][3], dist [C][5], X [N][3], info).  Camera 0's pose comes back
+        as it went in, |t_1| too (the gauge); rows of X whose point did not take part are NaN.  The capture must be raw (taken with
+        zero distortion coefficients) and must fill the images.  Needs no set_cameras."""
+        obs, R, t, K, dist, flags = self._bal_inputs(obs, R, t, K, dist, refine, huber_px)
+        if not (np.isfinite(ftol) and ftol >= 0) or int(max_iter) < 1:
+            self._bal_refuse("ftol must be finite and >= 0, max_iter >= 1")
+        N, C = obs.shape[:2]
+        X = np.full((N, 3), np.nan)
+        info = np.zeros(BAL_INFO)
+        self._check(self.lib.mocap_ba_lens_solve(self._h, C, N, _p(obs), _p(R), _p(t), _p(K), _p(dist), _p(X), flags, float(huber_px),
+                                                 float(ftol), int(max_iter), _p(info)))
+        info = dict(zip(self._BAJ_INFO_KEYS, info.tolist()))
+        info["status"] = int(info["status"])
+        return R.reshape(-1, 3, 3), t, K.reshape(-1, 3, 3), dist, X, info
+
+    def _undistort_inputs(self, K, dist):
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(-1, 9)
+        dist = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1, 5)
+        if not 1 <= K.shape[0] <= BAL_MAX_CAMERAS or dist.shape[0] != K.shape[0]:
+            self._bal_refuse(f"K [C][3][3] and dist [C][5] with 1 <= C <= {BAL_MAX_CAMERAS}")
+        return K, dist
+
+    def undistort_points(self, points, K, dist):
+        """mocap_undistort_points: raw pixels [N][C][2] (NaN = unseen, passed through) -> the ideal pinhole pixels under K [C][3][3]
+        and dist [C][5], by UNDISTORT_NEWTON Newton steps per observation on the device.  A camera with zero coefficients is
+        copied bit for bit."""
+        K, dist = self._undistort_inputs(K, dist)
+        C = K.shape[0]
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.size % (2 * C) or not 1 <= pts.size // (2 * C) <= UNDISTORT_MAX_POINTS:
+            self._bal_refuse(f"points must be [N][{C}][2] with 1 <= N <= {UNDISTORT_MAX_POINTS}")
+        pts = pts.reshape(-1, C, 2)
+        out = np.empty_like(pts)
+        self._check(self.lib.mocap_undistort_points(self._h, C, pts.shape[0], _p(pts), _p(K), _p(dist), _p(out)))
+        return out
+
+    def undistort_points_dev(self, d_in, d_out, n_points, K, dist):
+        """mocap_undistort_points_dev: the same on device pointers (integers), enqueued on the context's stream."""
+        K, dist = self._undistort_inputs(K, dist)
+        self._check(self.lib.mocap_undistort_points_dev(self._h, K.shape[0], int(n_points), ctypes.c_void_p(int(d_in)), _p(K), _p(dist),
+                                                        ctypes.c_void_p(int(d_out))))
 
     # ------------------------------------------------------------------ camera resection
     RESECT_INFO_KEYS = ("valid", "winner_inliers", "winner_hypothesis", "winner_solution", "no_solution", "inliers", "accepted",

@@ -1565,3 +1565,79 @@ def bundle_adjustment_joint(image_points, camera_poses, socketio=None, refine_fo
         socketio.emit("camera-pose", {"camera_poses": camera_pose_to_serializable(poses)})
     out = (poses,) + ((scales,) if refine_focal else ()) + ((info,) if return_info else ())
     return out[0] if len(out) == 1 else out
+
+
+def _lens_arrays(C):
+    """K [C][3][3] and dist [C][5] of the camera params; a camera without "distortion_coef" has zeros."""
+    K = _intrinsics(C)
+    params = _state["camera_params"]
+    dist = np.zeros((C, 5))
+    for c in range(C):
+        d = np.asarray(params[c].get("distortion_coef", [0.0] * 5), dtype=np.float64).ravel()
+        dist[c, :min(5, d.size)] = d[:5]
+    return K, dist
+
+
+def calibrate_lenses(image_points, camera_poses, refine=("focal", "centre", "radial"), huber_px=0.0, max_iter=100, ftol=1e-10,
+                     return_info=False):
+    """Lens calibration from a wand capture (mocap_ba_lens_solve, include/mocap_core.h "lens calibration"): the poses of cameras
+    1 .. C-1, every 3-D point and, per camera, the intrinsics named in `refine` -- "focal" (fx, fy), "centre" (cx, cy), "radial"
+    (k1, k2), "tangential" (p1, p2), or an integer of capi.BAL_* bits -- as unknowns of one bundle adjustment.  Needs three cameras.  The start is the camera params
+    as set_camera_params has them (nominal values do: the data sheet's focal length, the picture's centre, zero distortion).
+
+    THE CAPTURE: image_points are `capture-points` rows taken RAW, i.e. with distortion_coef = 0 in the camera params while
+    capturing, so that the blob stage does not undistort with a lens nobody knows yet; and the wand must FILL THE IMAGES, out to
+    the corners of every camera's picture.  Points that cover only the middle of the pictures do not determine a lens: the solver
+    still returns, with intrinsics that are worth nothing (DESIGN 3.7r has the figures).
+
+    Returns (camera_poses, camera_params): poses in the reference's dict shape (camera 0 and |t_1| as they came), and a list of
+    {"intrinsic_matrix": 3x3 list, "distortion_coef": [k1, k2, p1, p2, k3]} in camera-params.json's convention, ready for
+    set_camera_params (other keys of the current params, like "rotation", are kept); with return_info the solver's info dict
+    last.  undistort_image_points(image_points, camera_params) then turns the same raw capture into what determine_scale,
+    acquire_floor, bundle_adjustment_joint and reseat_camera take."""
+    C = len(camera_poses)
+    try:
+        flags = capi.MocapCore.bal_flags(refine)
+    except capi.MocapError as e:
+        raise ValueError(str(e))
+    if flags & ~15:
+        raise ValueError(f"unknown bits in refine: {flags:#x}")
+    if flags and C < 3:
+        raise ValueError("lens calibration needs at least 3 cameras: with two, the intrinsics are not observable")
+    if not (np.isfinite(huber_px) and huber_px >= 0 and np.isfinite(ftol) and ftol >= 0 and int(max_iter) >= 1):
+        raise ValueError("huber_px and ftol must be finite and >= 0, max_iter at least 1")
+    obs = _obs_array(image_points, C)
+    R, t = _pose_arrays(camera_poses)
+    K, dist = _lens_arrays(C)
+    with _state["lock"]:
+        core = _ba_core()
+    with _state["ba_lock"]:
+        R1, t1, K1, d1, _, info = core.ba_lens_solve(obs, R, t, K, dist, refine=flags, huber_px=huber_px, ftol=ftol, max_iter=max_iter)
+    poses = [{"R": R1[c].copy(), "t": t1[c].copy()} for c in range(C)]
+    params = []
+    for c in range(C):
+        p = dict(_state["camera_params"][c])
+        p["intrinsic_matrix"] = K1[c].tolist()
+        p["distortion_coef"] = d1[c].tolist()
+        params.append(p)
+    return (poses, params, info) if return_info else (poses, params)
+
+
+def undistort_image_points(image_points, camera_params=None):
+    """Raw capture rows -> the ideal pinhole pixels under each camera's intrinsic_matrix and distortion_coef
+    (mocap_undistort_points): [N][C][2] float64, NaN where a camera did not see the point.  camera_params: the list
+    calibrate_lenses returns; None = the params of set_camera_params."""
+    params = _state["camera_params"] if camera_params is None else camera_params
+    if params is None:
+        raise RuntimeError("set_camera_params() has not been called and no camera_params were given")
+    C = len(params)
+    K = np.array([np.array(p["intrinsic_matrix"], dtype=np.float64) for p in params])
+    dist = np.zeros((C, 5))
+    for c in range(C):
+        d = np.asarray(params[c].get("distortion_coef", [0.0] * 5), dtype=np.float64).ravel()
+        dist[c, :min(5, d.size)] = d[:5]
+    obs = _obs_array(image_points, C)
+    with _state["lock"]:
+        core = _ba_core()
+    with _state["ba_lock"]:
+        return core.undistort_points(obs, K, dist)
