@@ -1,12 +1,13 @@
 // ba_lens.hpp -- lens calibration (include/mocap_core.h, "lens calibration"): the lens model and the per-view arithmetic, written once
 // for the kernels of csrc/ba_lens.hip and for a stand-alone host program (tests/native/bal_view_host.cpp), and what those kernels are
-// launched with (laid out by csrc/ba_lens_capi.hip).  Every expression is written in the order the header pins; the build compiles
-// with -ffp-contract=off.  This file includes nothing of the device: the host program compiles it with a plain C++ compiler.
+// instantiated with (the camera model of csrc/ba_schur.hpp).  Every expression is written in the order the header pins; the build compiles
+// with -ffp-contract=off.  Without a HIP compiler this file includes nothing of the device and ends before the model: the host program
+// compiles it with a plain C++ compiler.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #ifdef __HIPCC__
-#include <hip/hip_runtime.h>
+#include "ba_schur.hpp"
 #endif
 
 #if !defined(__HIPCC__) && !defined(__host__)
@@ -24,15 +25,11 @@ constexpr int kBalMaxPoints = 65536;  // ... MOCAP_BAL_MAX_POINTS
 constexpr int kBalNewton = 8;         // ... MOCAP_UNDISTORT_NEWTON
 constexpr int kBalCam = 24;           // doubles per camera of the table: R [9] row-major, t [3], fx, fy, cx, cy, k1, k2, p1, p2, k3, 3 unused
 constexpr int kBalPar = 14;           // a camera's parameters: omega 3, t 3, fx, fy, cx, cy, k1, k2, p1, p2
-// The camera block U (upper triangle of 14 x 14, row i = U[i][i .. 13] followed by g[i]: 15 - i values) is cut into four ROW BANDS,
-// one per blockIdx.z of the camera kernel:  rows 0-1 (29 values), 2-4 (36), 5-8 (34), 9-13 (20, then the six counters).  One partial
-// per workgroup, camera and band: slab [C][4][calib_partials(N)][kBalSlab], sums [C][4][kBalSlab].
+// The camera block (csrc/ba_schur.hpp: the upper triangle of 14 x 14 row by row, row i = 15 - i values) is cut into four ROW BANDS:
+// rows 0-1 (29 values), 2-4 (36), 5-8 (34), 9-13 (20, then the six counters).
 constexpr int kBalBands = 4;
 constexpr int kBalSlab = 36;
-// band 3, behind its 20 values: [20] sum of the points' rho (camera 0 only)  [21] views used  [22] views down-weighted
-//   [23] views skipped (depth not finite or <= 0)  [24] participating points (camera 0 only)  [25] singular points (camera 0 only)
 constexpr int kBalCount = 20;
-constexpr int kBalPointSingular = 1;  // a point's flag: V_lambda had no Cholesky factor, the point stays where it is this pass
 
 __host__ __device__ constexpr int bal_band_lo(int b) { return b == 0 ? 0 : b == 1 ? 2 : b == 2 ? 5 : 9; }
 __host__ __device__ constexpr int bal_band_hi(int b) { return b == 0 ? 2 : b == 1 ? 5 : b == 2 ? 9 : 14; }
@@ -166,31 +163,21 @@ BAL_INLINE void bal_undistort(TabK K9, TabD k, double u, double v, double& uo, d
 }
 
 #ifdef __HIPCC__
-// what one linearisation reads and writes; every pointer device-accessible (G and sums: pinned host memory)
-struct BalArgs {
-  int C, q, n_c, NP;
-  uint32_t sel;           // MOCAP_BAL_* bits: which pairs of (fx fy | cx cy | k1 k2 | p1 p2) are unknowns, q = 2 x (bits set)
-  int64_t N, m_pad;
-  double huber, lambda;
-  const double* obs;      // [N][C][2], NaN = unseen
-  const double* cams;     // [C][kBalCam] of the point of linearisation
-  const double* X;        // [N][3]
-  const int32_t* part;    // [N] 1 = the point takes part
-  double* Jaug;           // [m_pad][NP]: the point's rows 3 p .. 3 p + 2 of [E | z | 0]
-  double* L;              // [N][6]: l00 l10 l20 l11 l21 l22
-  double* rho;            // [N]
-  int32_t* flags;         // [N] kBalPoint*
-  double* partial;        // launch_ba_gram's K slices
-  int ksplit;
-  double* G;              // [NP][NP] out: Jaug^T Jaug
-  double* slab;           // [C][kBalBands][calib_partials(N)][kBalSlab]
-  double* sums;           // [C][kBalBands][kBalSlab] out
+// The model: 24 doubles per camera, 14 parameters (flag bits: fx fy | cx cy | k1 k2 | p1 p2), four row bands.
+struct BalModel {
+  using View = BalView;
+  static constexpr int kCam = kBalCam, kPar = kBalPar, kBands = kBalBands, kSlab = kBalSlab, kCount = kBalCount;
+  __host__ __device__ static constexpr int band_lo(int b) { return bal_band_lo(b); }
+  __host__ __device__ static constexpr int band_hi(int b) { return bal_band_hi(b); }
+  __host__ __device__ static constexpr int band_of(int i) { return bal_band_of(i); }
+  __host__ __device__ static constexpr int row_off(int i) { return bal_row_off(i); }
+  template <class Tab>
+  __host__ __device__ static __forceinline__ void view(Tab cam, const double (&X)[3], double u, double v, double huber, View& o) {
+    bal_view(cam, X, u, v, huber, o);
+  }
 };
 
-// linearise + Gram + camera blocks + fold: 5 launches
-hipError_t launch_bal_linearise(const BalArgs& a, hipStream_t stream);
-// X_trial = X - L^-T (z + E delta) per point, from the linearisation `a`
-hipError_t launch_bal_backsub(const BalArgs& a, const double* delta, double* X_trial, hipStream_t stream);
+hipError_t launch_bal_linearise(const SchurArgs& a, hipStream_t stream);
 // out [N][C][2] = the ideal pinhole pixels of in [N][C][2] under K [C][9], dist [C][5] (all device pointers)
 hipError_t launch_bal_undistort(int C, int64_t N, const double* in, const double* K, const double* dist, double* out,
                                 hipStream_t stream);

@@ -150,37 +150,6 @@ bool CholSecular::solve(double Delta, double& alpha_io, double* p_live) {
 }
 
 // ------------------------------------------------------------------ joint bundle adjustment
-void baj_assemble(int C, bool focal, int NP, const double* G, const double* sums, double lambda, double* S, double* rhs) {
-  const int n = 6 * (C - 1) + (focal ? C : 0);
-  auto u = [](int i, int j) { return i * 7 - i * (i - 1) / 2 + (j - i); };  // packed upper triangle of the 7 x 7 block
-  for (int i = 0; i < n * n; i++) S[i] = 0.0;
-  for (int i = 0; i < n; i++) rhs[i] = 0.0;
-  for (int c = 0; c < C; c++) {
-    const double* U = sums + 41 * c;
-    int idx[7];  // the block's rows in S; -1 = not an unknown
-    for (int k = 0; k < 6; k++) idx[k] = c ? 6 * (c - 1) + k : -1;
-    idx[6] = focal ? 6 * (C - 1) + c : -1;
-    for (int i = 0; i < 7; i++) {
-      if (idx[i] < 0) continue;
-      for (int j = i; j < 7; j++) {
-        if (idx[j] < 0) continue;
-        const double v = i == j ? U[u(i, i)] + lambda * U[u(i, i)] : U[u(i, j)];
-        S[idx[i] * n + idx[j]] = v;
-        S[idx[j] * n + idx[i]] = v;
-      }
-      rhs[idx[i]] = -U[28 + i];
-    }
-  }
-  for (int i = 0; i < n; i++) {
-    for (int j = i; j < n; j++) {
-      const double v = S[i * n + j] - G[(size_t)i * NP + j];
-      S[i * n + j] = v;
-      S[j * n + i] = v;
-    }
-    rhs[i] = rhs[i] + G[(size_t)i * NP + n];
-  }
-}
-
 bool baj_chol_solve(int n, double* S, const double* rhs, double* delta) {
   // S = L L^T, L in the lower triangle, row by row, every sum left to right
   for (int i = 0; i < n; i++) {

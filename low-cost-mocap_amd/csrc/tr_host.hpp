@@ -27,11 +27,8 @@ class CholSecular {
   double *B_ = nullptr, *L_ = nullptr, *invd_ = nullptr, *g_ = nullptr, *q_ = nullptr, *w_ = nullptr;
 };
 
-// ---- joint bundle adjustment (include/mocap_core.h, "joint bundle adjustment"): the host's share of one iteration, plain double
-// loops in the order the header states.
-// S = U_lambda - sum E^T E, rhs = -g_c + sum E^T z.  G [NP][NP] = [E | z]^T [E | z] (its upper triangle is read), sums [C][41] the
-// camera blocks as csrc/ba_joint.hpp lays them out; n_c = 6 (C - 1) + (focal ? C : 0).  S [n_c][n_c] row-major, rhs [n_c].
-void baj_assemble(int C, bool focal, int NP, const double* G, const double* sums, double lambda, double* S, double* rhs);
+// ---- joint bundle adjustment and lens calibration (include/mocap_core.h; the loop: csrc/ba_schur_host.hpp): the host's share of
+// one iteration, plain double loops in the order the header states.
 // S delta = rhs by a dense Cholesky (S is overwritten by its factor).  false: a pivot is not finite or not > 0.
 bool baj_chol_solve(int n, double* S, const double* rhs, double* delta);
 // R <- exp([w]x) R (Rodrigues), R row-major 3 x 3
