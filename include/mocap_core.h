@@ -1089,6 +1089,118 @@ int mocap_fill_rows_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d
                         const int32_t* rows, const double* markers, const int32_t* d_flag, const double* d_Rm, const double* d_t_pose,
                         const int32_t* d_flag_s, const double* d_quat_s, const double* d_pos_s, double* d_filled, int32_t* d_src);
 
+/* ---------------------------------------------------------------- joints (the core's own contract)
+ * Which bodies of a recorded session are joined, where, and how.  "body trajectories" ends at bodies that know nothing of each other;
+ * this section finds, for every pair of bodies, the point (ball joint) or the line (hinge) the two share throughout the capture,
+ * builds a skeleton from the pairs that have one, and gives a joint's motion per frame.  The fit is the classical linear one:
+ * symmetrical centre of rotation estimation (SCoRE) for the centre, symmetrical axis of rotation analysis (SARA) for the axis.
+ * Offline and opt-in: with nothing called nothing changes.  helpers.session_joints and helpers.session_joint_motion are the glue.
+ *
+ * A. mocap_find_joints[_dev]: n_frames F in 1 .. MOCAP_RG_MAX_FRAMES; B in 2 .. MOCAP_BP_MAX_BODIES; flag [B][F] i32, Rm [B][F][9],
+ *    t_pose [B][F][3] as mocap_pose_rows writes them;
+ *      min_common  >= 6: frames two bodies must share to be judged
+ *      tol_rank    finite, in (0, 1): an eigenvalue at or below it counts as zero
+ *      max_sep     metres, > 0; +inf allowed: the largest rms distance between the two images of a joint's centre
+ *    MOCAP_E_ARG, every output untouched, for a value outside these or a null buffer.
+ *    All arithmetic is IEEE double, no fused operation, in the order written here; / and sqrt are correctly rounded.
+ *    1. Pair sums, per pair a < b, over the frames f at which both flags are MOCAP_BP_POSED and the 24 values Rm_a, t_a, Rm_b, t_b
+ *       are finite (n = their number, exact):
+ *         Rel_ij = (Rm_a[0][i] * Rm_b[0][j] + Rm_a[1][i] * Rm_b[1][j]) + Rm_a[2][i] * Rm_b[2][j]      (Rel = Rm_a^T Rm_b)
+ *         dt = t_b - t_a per component;  d_i = (Rm_a[0][i] * dt_0 + Rm_a[1][i] * dt_1) + Rm_a[2][i] * dt_2   (d = Rm_a^T (t_b - t_a))
+ *         g_j = (Rel_0j * d_0 + Rel_1j * d_1) + Rel_2j * d_2                                      (g = Rel^T d)
+ *         dd = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2
+ *       Sixteen sums: the nine Rel_ij, d (3), g (3) and dd, each by SUM exactly as "rigid groups" item 2 defines it (tiles of 256
+ *       frames, the tree of csrc/tree_fold.hpp, an absent frame carries +0.0).  (No output of this version depends on SUM(dd): it fills the
+ *       sixteenth slot of a pair's fold, and is what a closed-form residual would start from.)  How the device arrives at that association
+ *       order is its own business.
+ *    2. System.  Rbar = SUM(Rel) / n per entry, dbar, gbar likewise;  M = [[I, -Rbar], [-Rbar^T, I]], 6 x 6, I with exact 1 and 0;
+ *       rhs = (dbar_0, dbar_1, dbar_2, -gbar_0, -gbar_1, -gbar_2).  Cyclic Jacobi on M by the very rules "body trajectories" item 1
+ *       spells out for Horn's 4 x 4 matrix -- the sweep's off = the sum of the |A_pq| in pair order and the end at off == 0, the skip
+ *       rule, the g = 100 |A_pq| rule from the fifth sweep on, the rotation formulae, V from the identity -- with the index running
+ *       0 .. 5, k = 0 .. 5, and the 15 pairs in lexicographic order 01, 02, .. 05, 12, .. 45; at most 30 sweeps (every input of the
+ *       tests ends within 9; the limit only bounds a matrix with a NaN in it).  lambda = the diagonal, ordered ascending, the lower
+ *       index first among equals.
+ *    3. Kind, the first rule that applies:
+ *         n < min_common                          MOCAP_JT_UNSEEN    nothing computed, every double NaN
+ *         a lambda or an entry of V not finite    MOCAP_JT_SINGULAR  every double NaN
+ *         two or more lambda <= tol_rank          MOCAP_JT_FIXED     the bodies did not turn against each other: no centre is determined
+ *         exactly one lambda <= tol_rank          MOCAP_JT_HINGE
+ *         none                                    MOCAP_JT_BALL
+ *    4. Solution, the minimum-norm one: x = 0; over the k with lambda_k > tol_rank in the order of item 2:
+ *       h = (the sum from 0 over i = 0 .. 5 of V_ik * rhs_i) / lambda_k, then x_i = x_i + h * V_ik.  c_a = x[0 .. 3) in a's coordinates,
+ *       c_b = x[3 .. 6) in b's.  Under HINGE every point of the axis is a centre; the one found is the point of the axis this
+ *       minimum-norm rule picks (the one nearest the two bodies' origins, taken together), not a point of any anatomical meaning.
+ *       Under FIXED it is whatever the kept directions give.
+ *    5. Axis, under HINGE only (else NaN): with k0 the first of the order, axis_a = (V_0k0, V_1k0, V_2k0) / na,
+ *       na = sqrt((x * x + y * y) + z * z) of those three, axis_b likewise from the rows 3 .. 5 with its own norm nb; both are negated
+ *       iff the first non-zero component of axis_a is negative.  na or nb not > 0: MOCAP_JT_SINGULAR.
+ *    6. Residual, a second pass over the same frames with the rounded centres, under FIXED, HINGE and BALL:
+ *         w_a,i = ((Rm_a[i][0] * c_a0 + Rm_a[i][1] * c_a1) + Rm_a[i][2] * c_a2) + t_a,i;  w_b likewise;  e = w_a - w_b
+ *         sep = sqrt(SUM((e_0 * e_0 + e_1 * e_1) + e_2 * e_2) / n)
+ *       accepted iff the kind is HINGE or BALL and sep <= max_sep (a NaN fails).
+ *    7. Skeleton.  Kruskal over the accepted pairs a < b in ascending order of (the bits of sep as an unsigned integer, a, b): a pair
+ *       whose bodies are not yet connected becomes a tree edge.  In each component the lowest body is the root;
+ *       parent[b] = b's neighbour on the tree path towards its root, -1 for a root and for a body with no accepted pair;
+ *       n_joints = the number of tree edges.
+ *    Outputs, every byte written; each [B][B] table is symmetric save centre and axis:
+ *      cnt [B][B] i32        n; the diagonal follows the same rule (the body's POSED frames with twelve finite values)
+ *      kind [B][B] i32       MOCAP_JT_*; the diagonal is UNSEEN
+ *      accepted [B][B] i32   the diagonal is 0
+ *      lam [B][B][3] f64     the three smallest lambda in order
+ *      sep [B][B] f64
+ *      centre [B][B][3] f64  centre[p][q] is the joint of the pair {p, q} IN p's COORDINATES: c_a at [a][b], c_b at [b][a]
+ *      axis [B][B][3] f64    likewise: axis_a at [a][b], axis_b at [b][a]
+ *      parent [B] i32, n_joints i32 (one value)
+ *    Two calls on the same input give the same bytes, and so do the host form and the "_dev" form (any NaN equal to any NaN).  No
+ *    floating-point atomics.  The "_dev" form enqueues on the context's stream (every pointer device-accessible) and does not wait;
+ *    the host form uploads, runs and downloads.  The workspace of one call stays under 256 MB: the pairs go through it in rounds.
+ *
+ * B. mocap_joint_series[_dev]: a joint's motion per frame.  The joints of a call: J in 1 .. MOCAP_JT_MAX_JOINTS; body_a, body_b [J]
+ *    i32 (in 0 .. B-1, different), kind [J] i32 (a MOCAP_JT_* value), c_a, c_b [J][3] (finite), axis_b [J][3] (read and finite under
+ *    HINGE), q_ref [J][4] (w, x, y, z; finite, |q|^2 within 1e-6 of 1): a reference orientation of b in a, the identity allowed.
+ *    These seven arrays are HOST memory in both forms: the host checks them and hands them to the device inside kernel arguments, as
+ *    "body trajectories" does with its bodies -- a "_dev" call neither waits nor keeps a pointer to them.  flag [B][F] i32,
+ *    quat [B][F][4], Rm [B][F][9], t_pose [B][F][3] are mocap_pose_rows'; n_frames and B as under A.
+ *    MOCAP_E_ARG, every output untouched, for anything else or a null buffer.
+ *    Per (joint j, frame f), all [J][F]:
+ *      present i32      1 iff both flags are MOCAP_BP_POSED; every double below is NaN where it is 0
+ *      centre [3]       w_a, w_b as in A.6 from the given c_a, c_b;  centre_i = (w_a,i + w_b,i) * 0.5
+ *      gap              e = w_a - w_b;  gap = sqrt((e_0 * e_0 + e_1 * e_1) + e_2 * e_2)
+ *      quat_rel [4]     conj(q_ref) (x) (conj(q_a) (x) q_b), conj negating x, y, z, the Hamilton product p (x) q term by term:
+ *                         w = ((p_w * q_w - p_x * q_x) - p_y * q_y) - p_z * q_z      x = ((p_w * q_x + p_x * q_w) + p_y * q_z) - p_z * q_y
+ *                         y = ((p_w * q_y - p_x * q_z) + p_y * q_w) + p_z * q_x      z = ((p_w * q_z + p_x * q_y) - p_y * q_x) + p_z * q_w
+ *                       mocap_pose_rows' sign walk makes q_a and q_b continuous along f, so the product is continuous too.
+ *      twist [2]        under HINGE: s = (x * ax + y * ay) + z * az of quat_rel against axis_b, m = sqrt(w * w + s * s),
+ *                       twist = (w / m, s / m): cosine and sine of HALF the hinge angle against q_ref.  NaN where m is not > 0 and
+ *                       under every other kind.
+ *    There is no atan2 on the device: the angle 2 atan2(twist_1, twist_0) is the helper's step, so every double here is + - * / sqrt.
+ *    quat_rel [J][F][4] is a table mocap_smooth_rotations accepts unchanged (J in the place of B), centre [J][F][3] one
+ *    mocap_smooth_tracks accepts.  One lane per (joint, frame), frames along the lanes.
+ * Out of scope: joints between more than two bodies; universal or sliding joints as kinds of their own; robust fits; weighting by
+ * marker count; a streaming form. */
+#define MOCAP_JT_MAX_JOINTS 64
+enum {
+  MOCAP_JT_UNSEEN = 0,    /* fewer than min_common frames in common: nothing computed */
+  MOCAP_JT_SINGULAR = 1,  /* the eigen-problem gave a value that is not finite */
+  MOCAP_JT_FIXED = 2,     /* two or more eigenvalues at or below tol_rank: the bodies did not turn against each other */
+  MOCAP_JT_HINGE = 3,     /* exactly one: a line is shared */
+  MOCAP_JT_BALL = 4       /* none: a point is shared (if sep says so) */
+};
+int mocap_find_joints(mocap_ctx* ctx, int64_t n_frames, int B, const int32_t* flag, const double* Rm, const double* t_pose,
+                      int min_common, double tol_rank, double max_sep, int32_t* cnt, int32_t* kind, int32_t* accepted, double* lam,
+                      double* sep, double* centre, double* axis, int32_t* parent, int32_t* n_joints);
+int mocap_find_joints_dev(mocap_ctx* ctx, int64_t n_frames, int B, const int32_t* d_flag, const double* d_Rm, const double* d_t_pose,
+                          int min_common, double tol_rank, double max_sep, int32_t* d_cnt, int32_t* d_kind, int32_t* d_accepted,
+                          double* d_lam, double* d_sep, double* d_centre, double* d_axis, int32_t* d_parent, int32_t* d_n_joints);
+int mocap_joint_series(mocap_ctx* ctx, int64_t n_frames, int B, const int32_t* flag, const double* quat, const double* Rm,
+                       const double* t_pose, int J, const int32_t* body_a, const int32_t* body_b, const int32_t* kind, const double* c_a,
+                       const double* c_b, const double* axis_b, const double* q_ref, int32_t* present, double* centre, double* gap,
+                       double* quat_rel, double* twist);
+int mocap_joint_series_dev(mocap_ctx* ctx, int64_t n_frames, int B, const int32_t* d_flag, const double* d_quat, const double* d_Rm,
+                           const double* d_t_pose, int J, const int32_t* body_a, const int32_t* body_b, const int32_t* kind,
+                           const double* c_a, const double* c_b, const double* axis_b, const double* q_ref, int32_t* d_present,
+                           double* d_centre, double* d_gap, double* d_quat_rel, double* d_twist);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

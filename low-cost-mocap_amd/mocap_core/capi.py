@@ -62,6 +62,8 @@ RG_MAX_ROWS, RG_MAX_FRAMES = 256, 1 << 22    # mocap_rigid_groups: rows and fram
 BP_MAX_BODIES = 64        # mocap_pose_rows / mocap_smooth_rotations / mocap_fill_rows: bodies of a call at most
 BP_POSED, BP_FEW, BP_DEGENERATE, BP_RMS = 1, 2, 4, 8   # ... a (body, frame)'s flag (include/mocap_core.h)
 BP_SRC_NONE, BP_SRC_MEASURED, BP_SRC_RIGID, BP_SRC_RIGID_FILLED = 0, 1, 2, 3   # ... where a filled sample comes from
+JT_MAX_JOINTS = 64        # mocap_joint_series: joints of a call at most
+JT_UNSEEN, JT_SINGULAR, JT_FIXED, JT_HINGE, JT_BALL = 0, 1, 2, 3, 4   # mocap_find_joints: a pair's kind (include/mocap_core.h)
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -160,6 +162,10 @@ SIGNATURES = {
     "mocap_pose_rows_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_smooth_rotations": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mocap_smooth_rotations_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_find_joints": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_find_joints_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_joint_series": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_joint_series_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_fill_rows": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_fill_rows_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
@@ -1047,6 +1053,79 @@ class MocapCore:
         self._check(self.lib.mocap_fill_rows_dev(self._h, int(n_frames), int(R), _vp(d_traj), B, _p(n), _p(rows), _p(q), _vp(d_flag),
                                                  _vp(d_Rm), _vp(d_t_pose), _vp(d_flag_s or 0), _vp(d_quat_s or 0), _vp(d_pos_s or 0),
                                                  _vp(d_filled), _vp(d_src)))
+
+    # ------------------------------------------------------------------ joints (which bodies are joined, where and how)
+    JOINTS_OUT = ("cnt", "kind", "accepted", "lam", "sep", "centre", "axis", "parent", "n_joints")
+    SERIES_OUT = ("present", "centre", "gap", "quat_rel", "twist")
+
+    def find_joints(self, flag, R, t_pose, min_common=30, tol_rank=1e-4, max_sep=float("inf")):
+        """mocap_find_joints over host arrays flag [B][F], R [B][F][3][3], t_pose [B][F][3] (pose_rows') -> {"cnt", "kind" (JT_*),
+        "accepted" int32 [B][B], "lam" [B][B][3]: the three smallest eigenvalues of the pair's 6 x 6 system, "sep" [B][B]: the rms
+        distance between the two images of the centre, "centre", "axis" [B][B][3]: centre[p][q] is the joint of the pair {p, q} in
+        p's coordinates (axis: HINGE only), "parent" int32 [B]: the skeleton (-1 = a root or a body of no joint), "n_joints" int}."""
+        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        B, F = flag.shape
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(B, F, 9)
+        t_pose = np.ascontiguousarray(t_pose, dtype=np.float64).reshape(B, F, 3)
+        o = {k: np.zeros((B, B), dtype=np.int32) for k in ("cnt", "kind", "accepted")}
+        o.update({k: np.zeros((B, B, 3)) for k in ("lam", "centre", "axis")})
+        o.update(sep=np.zeros((B, B)), parent=np.zeros(B, dtype=np.int32), n_joints=np.zeros(1, dtype=np.int32))
+        self._check(self.lib.mocap_find_joints(self._h, F, B, _p(flag), _p(R), _p(t_pose), int(min_common), float(tol_rank),
+                                               float(max_sep), *[_p(o[k]) for k in self.JOINTS_OUT]))
+        o["n_joints"] = int(o["n_joints"][0])
+        return o
+
+    def find_joints_dev(self, n_frames, B, d_flag, d_Rm, d_t_pose, min_common, tol_rank, max_sep, d_cnt, d_kind, d_accepted, d_lam,
+                        d_sep, d_centre, d_axis, d_parent, d_n_joints):
+        """Device pointers (ints), shapes as find_joints; d_n_joints: int32[1]."""
+        self._check(self.lib.mocap_find_joints_dev(self._h, int(n_frames), int(B), _vp(d_flag), _vp(d_Rm), _vp(d_t_pose),
+                                                   int(min_common), float(tol_rank), float(max_sep), _vp(d_cnt), _vp(d_kind),
+                                                   _vp(d_accepted), _vp(d_lam), _vp(d_sep), _vp(d_centre), _vp(d_axis),
+                                                   _vp(d_parent), _vp(d_n_joints)))
+
+    @staticmethod
+    def _joint_arrays(joints):
+        """joints = [{"a", "b", "kind", "centre_a" or "c_a", "centre_b" or "c_b", "axis_b", "q_ref"}] (session_joints' list; q_ref
+        defaults to the identity, axis_b to zero) -> (J, body_a, body_b, kind int32 [J], c_a, c_b, axis_b [J][3], q_ref [J][4]): the
+        layout of the C entry point, which does every check."""
+        J = len(joints)
+        Jz = max(J, 1)
+        ia, ib, kind = (np.zeros(Jz, dtype=np.int32) for _ in range(3))
+        c_a, c_b, axis_b, q_ref = np.zeros((Jz, 3)), np.zeros((Jz, 3)), np.zeros((Jz, 3)), np.zeros((Jz, 4))
+        for j, jt in enumerate(joints):
+            ia[j], ib[j], kind[j] = int(jt["a"]), int(jt["b"]), int(jt["kind"])
+            c_a[j] = jt["centre_a"] if "centre_a" in jt else jt["c_a"]
+            c_b[j] = jt["centre_b"] if "centre_b" in jt else jt["c_b"]
+            axis = jt.get("axis_b")
+            axis_b[j] = 0.0 if axis is None or kind[j] != JT_HINGE else axis
+            ref = jt.get("q_ref")
+            q_ref[j] = (1.0, 0.0, 0.0, 0.0) if ref is None else ref
+        return J, ia, ib, kind, c_a, c_b, axis_b, q_ref
+
+    def joint_series(self, flag, quat, R, t_pose, joints):
+        """mocap_joint_series over host arrays flag [B][F], quat [B][F][4], R [B][F][3][3], t_pose [B][F][3] (pose_rows') and joints
+        (see _joint_arrays) -> {"present" int32 [J][F], "centre" [J][F][3]: the joint's place in the world, "gap" [J][F]: the distance
+        between its two images, "quat_rel" [J][F][4]: b's orientation in a against q_ref, "twist" [J][F][2]: cosine and sine of half
+        the hinge angle (HINGE only)}; NaN where a body is not POSED."""
+        flag = np.ascontiguousarray(flag, dtype=np.int32)
+        B, F = flag.shape
+        quat = np.ascontiguousarray(quat, dtype=np.float64).reshape(B, F, 4)
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(B, F, 9)
+        t_pose = np.ascontiguousarray(t_pose, dtype=np.float64).reshape(B, F, 3)
+        J, *arrays = self._joint_arrays(joints)
+        Jz = max(J, 1)
+        o = {"present": np.zeros((Jz, F), dtype=np.int32), "centre": np.zeros((Jz, F, 3)), "gap": np.zeros((Jz, F)),
+             "quat_rel": np.zeros((Jz, F, 4)), "twist": np.zeros((Jz, F, 2))}
+        self._check(self.lib.mocap_joint_series(self._h, F, B, _p(flag), _p(quat), _p(R), _p(t_pose), J, *[_p(a) for a in arrays],
+                                                *[_p(o[k]) for k in self.SERIES_OUT]))
+        return o
+
+    def joint_series_dev(self, n_frames, B, d_flag, d_quat, d_Rm, d_t_pose, joints, d_present, d_centre, d_gap, d_quat_rel, d_twist):
+        """Device pointers (ints), shapes as joint_series; joints: host data, as there."""
+        J, *arrays = self._joint_arrays(joints)
+        self._check(self.lib.mocap_joint_series_dev(self._h, int(n_frames), int(B), _vp(d_flag), _vp(d_quat), _vp(d_Rm), _vp(d_t_pose),
+                                                    J, *[_p(a) for a in arrays], _vp(d_present), _vp(d_centre), _vp(d_gap),
+                                                    _vp(d_quat_rel), _vp(d_twist)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

@@ -867,6 +867,144 @@ def session_body_poses(t, session, bodies, max_rms=float("inf"), degree=2, W=8, 
     return out
 
 
+def session_joints(poses, min_common=30, tol_rank=1e-4, max_sep=float("inf")):
+    """The joints of a session's bodies ("joints", include/mocap_core.h): mocap_find_joints over poses["flag"], poses["R"] and
+    poses["t_pose"].  poses = what session_body_poses returns, NumPy or resident (resident poses are read in place; only the [B][B]
+    and [B] outputs come to the host).  Two bodies are joined when they share min_common frames, their relative rotation spans
+    more than one axis (BALL) or exactly one (HINGE) by tol_rank, and the two images of the joint's centre stay within max_sep (rms,
+    metres); the skeleton is the minimum spanning forest over those pairs by that distance.  Returns {"joints": a list of {"a", "b",
+    "kind" (capi.JT_HINGE or capi.JT_BALL), "centre_a", "centre_b" [3]: the joint in a's and in b's coordinates, "axis_a", "axis_b"
+    [3] (HINGE; else NaN), "sep", "frames"} for the tree edges, a < b, ordered by (a, b); "parent" int32 [B]: each body's neighbour
+    towards the root of its tree (-1 = a root or a body of no joint); "pairs": mocap_find_joints' tables}."""
+    flag = poses["flag"]
+    resident = getattr(flag, "is_cuda", False)
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            res = core.find_joints(flag, poses["R"], poses["t_pose"], min_common=min_common, tol_rank=tol_rank, max_sep=max_sep)
+        else:
+            import torch
+            B, F = flag.shape
+            Rm, t_pose = poses["R"], poses["t_pose"]
+            assert flag.dtype == torch.int32 and flag.is_contiguous()
+            for a, n in ((Rm, 9), (t_pose, 3)):
+                assert a.dtype == torch.float64 and a.is_contiguous() and a.is_cuda and a.numel() == B * F * n
+            if flag.device.index != core.device_id:
+                raise ValueError(f"the session lives on {flag.device}, the core on GPU {core.device_id}: a resident session is read in place")
+            dev = flag.device
+            d = {k: torch.empty((B, B), dtype=torch.int32, device=dev) for k in ("cnt", "kind", "accepted")}
+            d.update({k: torch.empty((B, B, 3), dtype=torch.float64, device=dev) for k in ("lam", "centre", "axis")})
+            d.update(sep=torch.empty((B, B), dtype=torch.float64, device=dev), parent=torch.empty(B, dtype=torch.int32, device=dev),
+                     n_joints=torch.empty(1, dtype=torch.int32, device=dev))
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.find_joints_dev(F, B, flag.data_ptr(), Rm.data_ptr(), t_pose.data_ptr(), min_common, tol_rank, max_sep,
+                                 *[d[k].data_ptr() for k in core.JOINTS_OUT])
+            core.synchronize()
+            res = {k: v.cpu().numpy() for k, v in d.items()}
+            res["n_joints"] = int(res["n_joints"][0])
+    parent = res["parent"]
+    joints = []
+    for child in range(parent.size):
+        if parent[child] >= 0:
+            a, b = sorted((int(child), int(parent[child])))
+            joints.append({"a": a, "b": b, "kind": int(res["kind"][a, b]), "centre_a": res["centre"][a, b].copy(),
+                           "centre_b": res["centre"][b, a].copy(), "axis_a": res["axis"][a, b].copy(), "axis_b": res["axis"][b, a].copy(),
+                           "sep": float(res["sep"][a, b]), "frames": int(res["cnt"][a, b])})
+    joints.sort(key=lambda j: (j["a"], j["b"]))
+    return {"joints": joints, "parent": parent, "pairs": res}
+
+
+def _unwrapped_angle(twist, present, xp):
+    """2 atan2(twist_s, twist_c) along the last axis of twist [J][F][2], unwrapped over the present frames of each joint (a jump of
+    more than pi between consecutive present frames is a turn of 2 pi the other way); NaN elsewhere.  xp = numpy or torch."""
+    raw = 2.0 * xp.arctan2(twist[..., 1], twist[..., 0])
+    out = xp.full_like(raw, float("nan"))
+    for j in range(raw.shape[0]):
+        at = xp.nonzero((present[j] != 0) & ~xp.isnan(raw[j]))
+        at = at[0] if isinstance(at, tuple) else at[:, 0]
+        if at.shape[0] == 0:
+            continue
+        v = raw[j][at]
+        step = v[1:] - v[:-1]
+        turns = xp.cumsum(xp.round(step / (2.0 * np.pi)), 0)
+        out[j][at[1:]] = v[1:] - 2.0 * np.pi * turns
+        out[j][at[:1]] = v[:1]
+    return out
+
+
+def session_joint_motion(t, poses, joints, degree=2, W=8, span=float("inf"), n_min=None, max_gap=0):
+    """The motion of a session's joints ("joints", include/mocap_core.h): mocap_joint_series, then mocap_smooth_tracks over the
+    joints' centres and mocap_smooth_rotations over the relative quaternions.  t [F], poses = session_body_poses' dict, joints =
+    session_joints' list (or its dict), NumPy or resident (then every result stays a torch tensor on that GPU).  A joint without
+    "q_ref" gets b's orientation in a at the joint's first present frame, so its angles start at zero.  Returns {"present" [J][F],
+    "centre" [J][F][3], "gap" [J][F], "quat_rel" [J][F][4], "twist" [J][F][2]: the series; "pos", "vel", "acc" [J][F][3]: the centre
+    smoothed; "quat_s" [J][F][4], "omega" [J][F][3], "flag_s" [J][F]: the relative orientation smoothed; "angle" [J][F]: the hinge
+    angle against q_ref in radians, unwrapped along the present frames (NaN for other kinds); "q_ref" [J][4]}."""
+    joints = joints["joints"] if isinstance(joints, dict) else list(joints)
+    if not joints:
+        raise ValueError("session_joint_motion: no joints")
+    flag = poses["flag"]
+    resident = getattr(flag, "is_cuda", False)
+    n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+    par = (int(degree), int(W), float(span), n_min, int(max_gap))
+    J = len(joints)
+    B, F = flag.shape
+    # the reference orientations: conj(q_a) (x) q_b at each joint's first frame with both bodies POSED (two quaternions per joint)
+    joints = [dict(j) for j in joints]
+    for j in joints:
+        if j.get("q_ref") is None:
+            both = (flag[j["a"]] == capi.BP_POSED) & (flag[j["b"]] == capi.BP_POSED)
+            at = both.nonzero()
+            at = at[0] if isinstance(at, tuple) else at[:, 0]
+            j["q_ref"] = (1.0, 0.0, 0.0, 0.0)
+            if at.shape[0]:
+                f0 = int(at[0])
+                qa, qb = (np.asarray(poses["quat"][k][f0].cpu() if resident else poses["quat"][k][f0], dtype=np.float64) for k in (j["a"], j["b"]))
+                p = (qa[0], -qa[1], -qa[2], -qa[3])
+                ref = np.array([((p[0] * qb[0] - p[1] * qb[1]) - p[2] * qb[2]) - p[3] * qb[3],
+                                ((p[0] * qb[1] + p[1] * qb[0]) + p[2] * qb[3]) - p[3] * qb[2],
+                                ((p[0] * qb[2] - p[1] * qb[3]) + p[2] * qb[0]) + p[3] * qb[1],
+                                ((p[0] * qb[3] + p[1] * qb[2]) - p[2] * qb[1]) + p[3] * qb[0]])
+                j["q_ref"] = ref / np.sqrt(ref @ ref)
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            out = core.joint_series(flag, poses["quat"], poses["R"], poses["t_pose"], joints)
+            tr = core.smooth_tracks(t, out["centre"], *par)
+            rot = core.smooth_rotations(t, out["quat_rel"], *par)
+            out.update(pos=tr["pos"], vel=tr["vel"], acc=tr["acc"], quat_s=rot["quat_s"], omega=rot["omega"], flag_s=rot["flag"])
+            out["angle"] = _unwrapped_angle(out["twist"], out["present"], np)
+        else:
+            import torch
+            dev = flag.device
+            if dev.index != core.device_id:
+                raise ValueError(f"the session lives on {dev}, the core on GPU {core.device_id}: a resident session is read in place")
+            t = t if getattr(t, "is_cuda", False) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(dev)
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == F
+
+            def f64(*shape):
+                return torch.empty(shape, dtype=torch.float64, device=dev)
+
+            def i32(*shape):
+                return torch.empty(shape, dtype=torch.int32, device=dev)
+
+            out = {"present": i32(J, F), "centre": f64(J, F, 3), "gap": f64(J, F), "quat_rel": f64(J, F, 4), "twist": f64(J, F, 2),
+                   "pos": f64(J, F, 3), "vel": f64(J, F, 3), "acc": f64(J, F, 3), "quat_s": f64(J, F, 4), "omega": f64(J, F, 3),
+                   "flag_s": i32(J, F)}
+            ws = {"res": f64(J, F), "n_tr": i32(J, F), "flag_tr": i32(J, F), "res_rot": f64(J, F), "n_rot": i32(J, F)}
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.joint_series_dev(F, B, flag.data_ptr(), poses["quat"].data_ptr(), poses["R"].data_ptr(), poses["t_pose"].data_ptr(), joints,
+                                  *[out[k].data_ptr() for k in core.SERIES_OUT])
+            core.smooth_tracks_dev(F, J, t.data_ptr(), out["centre"].data_ptr(), *par, out["pos"].data_ptr(), out["vel"].data_ptr(),
+                                   out["acc"].data_ptr(), ws["res"].data_ptr(), ws["n_tr"].data_ptr(), ws["flag_tr"].data_ptr())
+            core.smooth_rotations_dev(F, J, t.data_ptr(), out["quat_rel"].data_ptr(), *par, out["quat_s"].data_ptr(),
+                                      out["omega"].data_ptr(), ws["res_rot"].data_ptr(), ws["n_rot"].data_ptr(), out["flag_s"].data_ptr())
+            core.synchronize()
+            out["angle"] = _unwrapped_angle(out["twist"], out["present"], torch)
+    out["q_ref"] = np.array([j["q_ref"] for j in joints], dtype=np.float64)
+    return out
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
