@@ -1201,6 +1201,78 @@ int mocap_joint_series_dev(mocap_ctx* ctx, int64_t n_frames, int B, const int32_
                            const double* c_a, const double* c_b, const double* axis_b, const double* q_ref, int32_t* d_present,
                            double* d_centre, double* d_gap, double* d_quat_rel, double* d_twist);
 
+/* ---------------------------------------------------------------- joint poses (the core's own contract)
+ * Bodies with hidden markers posed through their joints.  mocap_pose_rows poses every body alone: with fewer than three markers
+ * seen, or a collinear set, the frame is MOCAP_BP_FEW or MOCAP_BP_DEGENERATE and its pose NaN.  With the skeleton of "joints" known
+ * such a frame is determined by a neighbour's pose: a ball joint gives the hidden body one point, a hinge a line, and the fit is
+ * stage 1's own with one or two more correspondences.  The fit propagates along the skeleton from every posed body.  Offline and
+ * opt-in: with nothing called nothing changes.  helpers.session_joint_poses is the glue.
+ *
+ * mocap_pose_joints[_dev]:
+ *   traj [R][F][3], R, n_frames F, and the bodies (B, n_markers, rows, markers; HOST memory) with the ranges and refusals of "body
+ *     trajectories"; B in 2 .. MOCAP_BP_MAX_BODIES.
+ *   flag [B][F] i32, quat [B][F][4], Rm [B][F][9], t_pose [B][F][3]: mocap_pose_rows' outputs over the same traj and bodies.
+ *   The joints, HOST memory in both forms as "joints" B takes them (checked on the host, handed to the device inside kernel
+ *     arguments; a "_dev" call neither waits nor keeps a pointer to them): J in 1 .. B-1; body_a, body_b [J] i32 in 0 .. B-1 and
+ *     different; kind [J] i32, MOCAP_JT_HINGE or MOCAP_JT_BALL only; c_a, c_b [J][3] finite: the joint's centre in a's and in b's
+ *     coordinates; axis_a, axis_b [J][3]: the hinge's axis in a's and in b's coordinates as mocap_find_joints signs them (both map to
+ *     ONE world direction), read under HINGE alone and then finite with (x x + y y) + z z within 1e-6 of 1.  The joints form a
+ *     forest: no pair of bodies appears twice and there is no cycle (a union-find over the bodies in joint order).
+ *   axis_len   metres, finite, > 0: how far along the axis a hinge's second virtual point lies
+ *   max_rms    metres, > 0, +inf allowed: the largest rms of a fit through a joint
+ *   max_rounds 1 .. MOCAP_JP_MAX_ROUNDS: how many joints away from a POSED body a pose may travel
+ *   MOCAP_E_ARG, every output untouched, for anything else or a null buffer.
+ *   -> all [B][F]: flag_j, hops, via i32; quat_j [4], Rm_j [9], t_j [3], rms_j f64.
+ * All arithmetic is IEEE double, no fused operation, in the order written here; / and sqrt are correctly rounded.  Every byte of
+ * every output is written.  Two calls on the same input give the same bytes, and so do the host form and the "_dev" form (any NaN
+ * equal to any NaN).  No floating-point atomics (one 32-bit integer maximum in LDS, exact in any order).
+ * Per frame f:
+ *   Round 0.  A body whose flag is MOCAP_BP_POSED: hops = 0, via = -1, flag_j = POSED, quat_j, Rm_j, t_j = its quat, Rm, t_pose
+ *     (copied), rms_j = NaN.  Every other body starts with hops = -1.
+ *   Round r = 1 .. max_rounds.  A body y with hops = -1 whose input flag is FEW or DEGENERATE is a candidate (an RMS frame never
+ *     is).  Its joints are tried in ascending joint index; a joint is tried only if its other body x has hops = r - 1 exactly (so
+ *     every directed joint is tried at most once per frame, and a body is posed from the nearest posed body of its tree).  The first
+ *     try that succeeds sets flag_j = MOCAP_BP_JOINTED, hops = r, via = the joint's index and the four doubles' tables; a failed
+ *     try leaves y a candidate for its later joints and for later rounds.
+ *   A try of y through a joint with x.  Presence is stage 1's (traj[rows[y][m]][f] is three finite values), k = the number present.
+ *     The point list: the present markers of y in ascending m (model markers[y][m], world the sample), then the joint's virtual
+ *     points, with c_y, axis_y the joint's centre and axis in y's coordinates, c_x, axis_x in x's, and Rx, tx = Rm_j, t_j of x:
+ *       first    model v0 = c_y;  world w0_i = ((Rx_i0 * c_x0 + Rx_i1 * c_x1) + Rx_i2 * c_x2) + tx_i
+ *       second, under HINGE only    model v1_i = c_y,i + axis_len * axis_y,i;  world w1_i = w0_i + axis_len * u_i,
+ *                u_i = (Rx_i0 * axis_x0 + Rx_i1 * axis_x1) + Rx_i2 * axis_x2
+ *     The try is POSSIBLE iff the model points of the list hold three that span a plane by the rigid-body section's rule,
+ *     |u x v| >= 0.1 |u| |v| (the host tabulates this as a 256-bit mask per directed joint, indexed by the present subset, as it
+ *     does per body for stage 1).  The fit is stage 1's, operation for operation, over the list in its order, c = k + 1 or k + 2:
+ *     the centroids, S, Horn's matrix, the Jacobi sweep, the top eigenvector, R, t, and rms over all c points.
+ *     The try SUCCEEDS iff it is possible, w, x, y, z are finite and rms <= max_rms (a NaN fails).  Then quat_j = (w, x, y, z) as
+ *     computed, Rm_j = R, t_j = t, rms_j = rms.
+ *   After the last round a body still at hops = -1 keeps its input flag in flag_j, via = -1, and NaN in quat_j, Rm_j, t_j, rms_j.
+ *   Sign continuity.  quat_j goes through stage 1's walk over the frames whose flag_j is POSED or JOINTED, in ascending f; the
+ *     "computed" quaternion of a POSED frame is the input's.  (A POSED frame's quat_j may so be the negative of its quat.)
+ * flag_j with JOINTED read as POSED, Rm_j and t_j are tables mocap_fill_rows, mocap_find_joints and mocap_joint_series accept
+ * unchanged; quat_j and t_j are tables mocap_smooth_rotations and mocap_smooth_tracks accept.
+ * One launch per round, one lane per (body, frame), frames along the lanes; the sign walk is stage 1's kernels.  The "_dev" form
+ * enqueues on the context's stream (every pointer but the bodies and the joints device-accessible; no output may overlap an
+ * input) and does not wait; the host form uploads, runs and downloads.
+ * Out of scope: a global least-squares fit of the whole skeleton (all joints closed at once); joint limits; a pose from a BALL
+ * joint and one marker; two anchors in one fit; weights for the virtual points; the live loop; any change to mocap_fill_rows or
+ * mocap_joint_series. */
+#define MOCAP_JP_MAX_ROUNDS 16
+enum {
+  MOCAP_BP_JOINTED = 16  /* mocap_pose_joints' flag_j: no pose from the body's own markers, one through a joint */
+};
+int mocap_pose_joints(mocap_ctx* ctx, int64_t n_frames, int R, const double* traj, int B, const int32_t* n_markers, const int32_t* rows,
+                      const double* markers, const int32_t* flag, const double* quat, const double* Rm, const double* t_pose, int J,
+                      const int32_t* body_a, const int32_t* body_b, const int32_t* kind, const double* c_a, const double* c_b,
+                      const double* axis_a, const double* axis_b, double axis_len, double max_rms, int max_rounds, int32_t* flag_j,
+                      int32_t* hops, int32_t* via, double* quat_j, double* Rm_j, double* t_j, double* rms_j);
+int mocap_pose_joints_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_traj, int B, const int32_t* n_markers,
+                          const int32_t* rows, const double* markers, const int32_t* d_flag, const double* d_quat, const double* d_Rm,
+                          const double* d_t_pose, int J, const int32_t* body_a, const int32_t* body_b, const int32_t* kind,
+                          const double* c_a, const double* c_b, const double* axis_a, const double* axis_b, double axis_len,
+                          double max_rms, int max_rounds, int32_t* d_flag_j, int32_t* d_hops, int32_t* d_via, double* d_quat_j,
+                          double* d_Rm_j, double* d_t_j, double* d_rms_j);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

@@ -9,8 +9,8 @@
 //            the top eigenvector and quaternion -> R are rb_pose.hpp's own functions.
 //   sign     the previous POSED frame of every frame as a prefix maximum (the tile's last POSED frame from the pose kernel, one
 //            workgroup per body over the tiles, then within the tile), the flip against it, and the flips' prefix parity the same
-//            way: four small launches behind the pose kernel, no walk over frames (block_scan.hpp's prefix and tile scan, the
-//            good-time launches' own).  Maximum and XOR are exact in any order.
+//            way: four small launches behind the pose kernel, no walk over frames (sign_walk.hpp, shared with "joint poses", over
+//            block_scan.hpp's prefix and tile scan, the good-time launches' own).  Maximum and XOR are exact in any order.
 //   smooth   track_smooth.hip's layout with four doubles per sample: 256 frames and a halo of W on either side in LDS (t, four
 //            planes, one byte of bits: 13.1 KB), each lane walks its window three times.  Staging, fit and residual walk are
 //            window_fit.hpp's with four channels, the marker smoother's own; this kernel keeps the n2 test between the solve and
@@ -21,6 +21,7 @@
 #include "block_scan.hpp"
 #include "mocap_device.hpp"
 #include "rb_pose.hpp"
+#include "sign_walk.hpp"
 #include "window_fit.hpp"
 
 namespace mocap {
@@ -158,47 +159,9 @@ __global__ __launch_bounds__(kT) void bp_pose_kernel(PoseRowsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ sign continuity
-// the flip of every POSED frame against the POSED frame before it, and the flips' parity within the tile
-__global__ __launch_bounds__(kT) void bp_flip_kernel(PoseRowsArgs a) {
-  __shared__ int32_t s[kT];
-  const int b = blockIdx.y, lane = threadIdx.x;
-  const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + lane;
-  const size_t o = (size_t)b * F + (f < F ? f : 0), tp = (size_t)b * gridDim.x + blockIdx.x;
-  const bool posed = f < F && a.flag[o] == kBpPosed;
-  block_prefix<OpMaxI32>(posed ? (int32_t)f : -1, s);
-  const int32_t in_tile = lane > 0 ? s[lane - 1] : -1, before_tile = a.tile_i32[tp];
-  const int32_t prev = in_tile > before_tile ? in_tile : before_tile;
-  int32_t flip = 0;
-  if (posed) {
-    const double* q = a.quat + 4 * o;
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    if (prev < 0) {
-      const double lead = w != 0.0 ? w : x != 0.0 ? x : y != 0.0 ? y : z;
-      flip = lead < 0.0;
-    } else {
-      const double* u = a.quat + 4 * ((size_t)b * F + prev);
-      const double d = ((u[0] * w + u[1] * x) + u[2] * y) + u[3] * z;
-      flip = d < 0.0;
-    }
-  }
-  __syncthreads();  // (s is read above and rewritten below)
-  const int32_t par = block_prefix<OpXor>(flip, s);
-  if (f < F) a.parity[o] = (uint8_t)par;
-  __syncthreads();  // every lane has read tile_i32[tp]
-  if (lane == kT - 1) a.tile_i32[tp] = par;
-}
-
-__global__ __launch_bounds__(kT) void bp_sign_kernel(PoseRowsArgs a) {
-  const int b = blockIdx.y;
-  const int64_t F = a.n_frames, f = (int64_t)blockIdx.x * kT + threadIdx.x;
-  if (f >= F) return;
-  const size_t o = (size_t)b * F + f;
-  if (a.flag[o] != kBpPosed) return;
-  if (!((a.parity[o] ^ a.tile_i32[(size_t)b * gridDim.x + blockIdx.x]) & 1)) return;
-  double* q = a.quat + 4 * o;
-#pragma unroll
-  for (int i = 0; i < 4; i++) q[i] = -q[i];
-}
+struct BpOnPosed {  // the frames that carry a quaternion (sign_walk.hpp)
+  __device__ static bool on(int32_t flag) { return flag == kBpPosed; }
+};
 
 // ------------------------------------------------------------------------------------------------------------------ rotations
 template <int D>
@@ -309,19 +272,10 @@ hipError_t launch_put_bodies(const BpBody* host, int B, BpBody* dev, hipStream_t
 }
 
 hipError_t launch_pose_rows(const PoseRowsArgs& a, hipStream_t stream) {
-  const int64_t P = ts_tiles(a.n_frames);
-  const dim3 block(kT), grid((unsigned)P, (unsigned)a.B), per_body((unsigned)a.B);
-  hipError_t e;
+  const dim3 block(kT), grid((unsigned)ts_tiles(a.n_frames), (unsigned)a.B);
   hipLaunchKernelGGL(bp_pose_kernel, grid, block, 0, stream, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(tile_scan_kernel<OpMaxI32>, per_body, block, 0, stream, a.tile_i32, P);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bp_flip_kernel, grid, block, 0, stream, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(tile_scan_kernel<OpXor>, per_body, block, 0, stream, a.tile_i32, P);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(bp_sign_kernel, grid, block, 0, stream, a);
-  return hipGetLastError();
+  if (hipError_t e = hipGetLastError()) return e;
+  return launch_sign_walk<BpOnPosed>(SignWalkArgs{a.n_frames, a.flag, a.quat, a.tile_i32, a.parity}, a.B, false, stream);
 }
 
 hipError_t launch_smooth_rotations(const SmoothRotationsArgs& a, hipStream_t stream) {

@@ -1,6 +1,8 @@
 // body_session.hpp -- body trajectories (include/mocap_core.h, "body trajectories"): what body_session.hip launches and
 // body_session_capi.hip lays out.  A header of its own: no existing translation unit includes it.
 #pragma once
+#include <vector>
+
 #include "track_smooth.hpp"
 
 namespace mocap {
@@ -66,5 +68,10 @@ hipError_t launch_pose_rows(const PoseRowsArgs& a, hipStream_t stream);
 hipError_t launch_smooth_rotations(const SmoothRotationsArgs& a, hipStream_t stream);
 // two launches: the row table, the fill
 hipError_t launch_fill_rows(const FillRowsArgs& a, hipStream_t stream);
+
+// Host side (body_session_capi.hip), shared with "joint poses": the bodies of a call checked by the section's rules and tabulated
+// with their posable masks.  `who` is the public call's name in the error text; the context's lock is the caller's.
+int bodies_table(mocap_ctx* ctx, const char* who, int R, int B, const int32_t* n_markers, const int32_t* rows, const double* markers,
+                 std::vector<BpBody>& table);
 
 }  // namespace mocap

@@ -12,6 +12,7 @@
 #include "../../include/mocap_core.h"
 #include "body_session.hpp"
 #include "ctx.hpp"
+#include "span_rule.hpp"
 
 using namespace mocap;
 
@@ -22,15 +23,6 @@ static_assert(kBpSrcNone == MOCAP_BP_SRC_NONE && kBpSrcMeasured == MOCAP_BP_SRC_
               "sources");
 
 namespace {
-
-// |(q_j - q_i) x (q_k - q_i)| >= 0.1 |q_j - q_i| |q_k - q_i|, the rigid-body section's rule in its order
-bool triple_spans(const double* qi, const double* qj, const double* qk) {
-  const double u[3] = {qj[0] - qi[0], qj[1] - qi[1], qj[2] - qi[2]}, v[3] = {qk[0] - qi[0], qk[1] - qi[1], qk[2] - qi[2]};
-  const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-  const double nc = std::sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
-  const double nu = std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]), nv = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-  return nc >= (0.1 * nu) * nv;
-}
 
 // bit s of the mask: the marker subset s holds a spanning triple (so it has >= 3 markers)
 void posable_mask(int n, const double (*q)[3], unsigned long long mask[4]) {
@@ -48,9 +40,11 @@ void posable_mask(int n, const double (*q)[3], unsigned long long mask[4]) {
   }
 }
 
-// the common body description, checked and tabulated
-int bodies_table(mocap_ctx* ctx, const char* who, int R, int B, const int32_t* n_markers, const int32_t* rows, const double* markers,
-                 std::vector<BpBody>& table) {
+}  // namespace
+
+// the common body description, checked and tabulated ("joint poses" takes its bodies through it too: body_session.hpp)
+int mocap::bodies_table(mocap_ctx* ctx, const char* who, int R, int B, const int32_t* n_markers, const int32_t* rows,
+                        const double* markers, std::vector<BpBody>& table) {
   if (B < 1 || B > kBpMaxBodies) return ctx->fail(MOCAP_E_ARG, "%s: B=%d outside 1 .. %d", who, B, kBpMaxBodies);
   if (!n_markers || !rows || !markers) return ctx->fail(MOCAP_E_ARG, "%s: null buffer", who);
   table.assign((size_t)B, BpBody{});
@@ -80,6 +74,8 @@ int bodies_table(mocap_ctx* ctx, const char* who, int R, int B, const int32_t* n
   }
   return MOCAP_OK;
 }
+
+namespace {
 
 int pose_check(mocap_ctx* ctx, int64_t n_frames, int R, const double* traj, double max_rms, const int32_t* n_used,
                const int32_t* present, const double* quat, const double* Rm, const double* t_pose, const double* rms,

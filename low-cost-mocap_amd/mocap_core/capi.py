@@ -64,6 +64,8 @@ BP_POSED, BP_FEW, BP_DEGENERATE, BP_RMS = 1, 2, 4, 8   # ... a (body, frame)'s f
 BP_SRC_NONE, BP_SRC_MEASURED, BP_SRC_RIGID, BP_SRC_RIGID_FILLED = 0, 1, 2, 3   # ... where a filled sample comes from
 JT_MAX_JOINTS = 64        # mocap_joint_series: joints of a call at most
 JT_UNSEEN, JT_SINGULAR, JT_FIXED, JT_HINGE, JT_BALL = 0, 1, 2, 3, 4   # mocap_find_joints: a pair's kind (include/mocap_core.h)
+BP_JOINTED = 16           # mocap_pose_joints: a (body, frame) posed through a joint, beside the BP_* flags above
+JP_MAX_ROUNDS = 16        # ... rounds (joints away from a POSED body) at most
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -166,6 +168,10 @@ SIGNATURES = {
     "mocap_find_joints_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_joint_series": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_joint_series_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_pose_joints": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl,
+                                 _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_pose_joints_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_fill_rows": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_fill_rows_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
@@ -1126,6 +1132,58 @@ class MocapCore:
         self._check(self.lib.mocap_joint_series_dev(self._h, int(n_frames), int(B), _vp(d_flag), _vp(d_quat), _vp(d_Rm), _vp(d_t_pose),
                                                     J, *[_p(a) for a in arrays], _vp(d_present), _vp(d_centre), _vp(d_gap),
                                                     _vp(d_quat_rel), _vp(d_twist)))
+
+    # ------------------------------------------------------------------ joint poses (hidden bodies posed through their joints)
+    JOINT_POSE_OUT = ("flag", "hops", "via", "quat", "R", "t_pose", "rms_j")
+
+    @staticmethod
+    def _joint_pose_arrays(joints):
+        """joints = [{"a", "b", "kind", "centre_a" or "c_a", "centre_b" or "c_b", "axis_a", "axis_b"}] (session_joints' list; the axes
+        are read under JT_HINGE alone) -> (J, body_a, body_b, kind int32 [J], c_a, c_b, axis_a, axis_b [J][3]): the layout of the C
+        entry point, which does every check."""
+        J = len(joints)
+        Jz = max(J, 1)
+        ia, ib, kind = (np.zeros(Jz, dtype=np.int32) for _ in range(3))
+        c_a, c_b, axis_a, axis_b = (np.zeros((Jz, 3)) for _ in range(4))
+        for j, jt in enumerate(joints):
+            ia[j], ib[j], kind[j] = int(jt["a"]), int(jt["b"]), int(jt["kind"])
+            c_a[j] = jt["centre_a"] if "centre_a" in jt else jt["c_a"]
+            c_b[j] = jt["centre_b"] if "centre_b" in jt else jt["c_b"]
+            if kind[j] == JT_HINGE:
+                axis_a[j], axis_b[j] = jt["axis_a"], jt["axis_b"]
+        return J, ia, ib, kind, c_a, c_b, axis_a, axis_b
+
+    def pose_joints(self, traj, bodies, flag, quat, R, t_pose, joints, axis_len=0.1, max_rms=float("inf"), max_rounds=4):
+        """mocap_pose_joints over host arrays: traj [R][F][3] and bodies as pose_rows takes them, pose_rows' flag [B][F], quat
+        [B][F][4], R [B][F][3][3] and t_pose [B][F][3], and joints (see _joint_pose_arrays) -> {"flag" int32 [B][F]: the input's with
+        BP_JOINTED where a FEW or DEGENERATE frame got a pose through a joint, "hops" [B][F]: joints between the body and the POSED
+        body the pose came from (0 = POSED itself, -1 = no pose), "via" [B][F]: the joint it came through (-1 = none), "quat",
+        "R", "t_pose": the poses (quat sign-continuous over the POSED and JOINTED frames), "rms_j" [B][F]: a jointed fit's rms}."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        Rr, F, _ = traj.shape
+        B, n, rows, q = self._session_bodies(bodies)
+        Bz = max(B, 1)
+        flag = np.ascontiguousarray(flag, dtype=np.int32).reshape(Bz, F)
+        quat = np.ascontiguousarray(quat, dtype=np.float64).reshape(Bz, F, 4)
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(Bz, F, 9)
+        t_pose = np.ascontiguousarray(t_pose, dtype=np.float64).reshape(Bz, F, 3)
+        J, *arrays = self._joint_pose_arrays(joints)
+        o = {k: np.zeros((Bz, F), dtype=np.int32) for k in ("flag", "hops", "via")}
+        o.update(quat=np.zeros((Bz, F, 4)), R=np.zeros((Bz, F, 3, 3)), t_pose=np.zeros((Bz, F, 3)), rms_j=np.zeros((Bz, F)))
+        self._check(self.lib.mocap_pose_joints(self._h, F, Rr, _p(traj), B, _p(n), _p(rows), _p(q), _p(flag), _p(quat), _p(R), _p(t_pose),
+                                               J, *[_p(a) for a in arrays], float(axis_len), float(max_rms), int(max_rounds),
+                                               *[_p(o[k]) for k in self.JOINT_POSE_OUT]))
+        return o
+
+    def pose_joints_dev(self, n_frames, R, d_traj, bodies, d_flag, d_quat, d_Rm, d_t_pose, joints, axis_len, max_rms, max_rounds,
+                        d_flag_j, d_hops, d_via, d_quat_j, d_Rm_j, d_t_j, d_rms_j):
+        """Device pointers (ints), shapes as pose_joints; bodies and joints: host data, as there."""
+        B, n, rows, q = self._session_bodies(bodies)
+        J, *arrays = self._joint_pose_arrays(joints)
+        self._check(self.lib.mocap_pose_joints_dev(self._h, int(n_frames), int(R), _vp(d_traj), B, _p(n), _p(rows), _p(q), _vp(d_flag),
+                                                   _vp(d_quat), _vp(d_Rm), _vp(d_t_pose), J, *[_p(a) for a in arrays], float(axis_len),
+                                                   float(max_rms), int(max_rounds), _vp(d_flag_j), _vp(d_hops), _vp(d_via),
+                                                   _vp(d_quat_j), _vp(d_Rm_j), _vp(d_t_j), _vp(d_rms_j)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

@@ -1005,6 +1005,99 @@ def session_joint_motion(t, poses, joints, degree=2, W=8, span=float("inf"), n_m
     return out
 
 
+def session_joint_poses(t, session, bodies, poses, joints, axis_len=0.1, max_rms=float("inf"), max_rounds=4, degree=2, W=8,
+                        span=float("inf"), n_min=None, max_gap=0, fill=True):
+    """The bodies session_body_poses could not pose, posed through the skeleton ("joint poses", include/mocap_core.h):
+    mocap_pose_joints over session["traj"], the bodies, poses (session_body_poses' dict) and joints (session_joints' dict or its
+    list), then the two smoothers over the new tables and, with fill, mocap_fill_rows.  NumPy or resident: resident arrays are read
+    in place and every result stays a torch tensor on that GPU.  A frame whose flag is BP_FEW or BP_DEGENERATE gets a pose from a
+    neighbour at most max_rounds joints away from a POSED body: two markers and a ball joint's centre, or one marker off a hinge's
+    axis (axis_len metres along it lies the hinge's second point), fitted like any other pose and kept when its rms is within
+    max_rms.  Returns a dict shaped like poses: {"flag" [B][F] (capi.BP_*, BP_JOINTED among them), "quat", "R", "t_pose": the poses;
+    "hops" [B][F]: joints between the body and the POSED body its pose came from (0 = POSED, -1 = none), "via" [B][F]: the joint,
+    "rms_j" [B][F]; "rms", "n_used", "present": poses' own; "flag_posed" [B][F]: flag with JOINTED read as POSED -- what
+    mocap_fill_rows is given here, and with it in the place of "flag" session_joint_motion sees a joint in those frames too;
+    "pos", "vel", "acc", "quat_s", "omega", "res_rot", "flag_s": the smoothers' results as session_body_poses names them; with fill
+    "filled" [R][F][3], "src" [R][F] and "from_joint" [R][F] bool: the rows filled from a JOINTED pose}."""
+    joints = joints["joints"] if isinstance(joints, dict) else list(joints)
+    if not joints:
+        raise ValueError("session_joint_poses: no joints")
+    for b, body in enumerate(bodies):
+        if not isinstance(body, dict) or "rows" not in body or "markers" not in body:
+            raise ValueError(f"session_joint_poses: body {b} has no 'rows': pass learn_session_bodies' list")
+    traj = session["traj"]
+    resident = getattr(traj, "is_cuda", False)
+    n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+    par = (int(degree), int(W), float(span), n_min, int(max_gap))
+    B = len(bodies)
+    row_body = np.full(traj.shape[0], -1, dtype=np.int64)
+    for b, body in enumerate(bodies):
+        row_body[np.asarray(body["rows"], dtype=np.int64)] = b
+    owned = np.flatnonzero(row_body >= 0)
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            o = core.pose_joints(traj, bodies, poses["flag"], poses["quat"], poses["R"], poses["t_pose"], joints, axis_len=axis_len,
+                                 max_rms=max_rms, max_rounds=max_rounds)
+            posed = np.where(o["flag"] == capi.BP_JOINTED, capi.BP_POSED, o["flag"]).astype(np.int32)
+            tr = core.smooth_tracks(t, o["t_pose"], *par)
+            rot = core.smooth_rotations(t, o["quat"], *par)
+            out = {**o, "rms": poses["rms"], "n_used": poses["n_used"], "present": poses["present"], "flag_posed": posed, "pos": tr["pos"],
+                   "vel": tr["vel"], "acc": tr["acc"], "quat_s": rot["quat_s"], "omega": rot["omega"], "res_rot": rot["res"],
+                   "flag_s": rot["flag"]}
+            if fill:
+                out.update(core.fill_rows(traj, bodies, posed, o["R"], o["t_pose"], rot["flag"], rot["quat_s"], tr["pos"]))
+                out["from_joint"] = np.zeros(out["src"].shape, dtype=bool)
+                out["from_joint"][owned] = (out["src"][owned] == capi.BP_SRC_RIGID) & (o["flag"][row_body[owned]] == capi.BP_JOINTED)
+        else:
+            import torch
+            R, F = traj.shape[0], traj.shape[1]
+            assert traj.dtype == torch.float64 and traj.is_contiguous() and traj.dim() == 3 and traj.shape[2] == 3
+            if traj.device.index != core.device_id:
+                raise ValueError(f"the session lives on {traj.device}, the core on GPU {core.device_id}: a resident session is read in place")
+            dev = traj.device
+            t = t if getattr(t, "is_cuda", False) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(dev)
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == F
+            for k, n, dt in (("flag", 1, torch.int32), ("quat", 4, torch.float64), ("R", 9, torch.float64), ("t_pose", 3, torch.float64)):
+                a = poses[k]
+                assert a.is_cuda and a.device == dev and a.dtype == dt and a.is_contiguous() and a.numel() == B * F * n, k
+
+            def f64(*shape):
+                return torch.empty(shape, dtype=torch.float64, device=dev)
+
+            def i32(*shape):
+                return torch.empty(shape, dtype=torch.int32, device=dev)
+
+            out = {"flag": i32(B, F), "hops": i32(B, F), "via": i32(B, F), "quat": f64(B, F, 4), "R": f64(B, F, 3, 3), "t_pose": f64(B, F, 3),
+                   "rms_j": f64(B, F), "rms": poses["rms"], "n_used": poses["n_used"], "present": poses["present"], "pos": f64(B, F, 3),
+                   "vel": f64(B, F, 3), "acc": f64(B, F, 3), "quat_s": f64(B, F, 4), "omega": f64(B, F, 3), "res_rot": f64(B, F),
+                   "flag_s": i32(B, F)}
+            ws = {"res": f64(B, F), "n_tr": i32(B, F), "flag_tr": i32(B, F), "n_rot": i32(B, F)}
+            if fill:
+                out.update(filled=f64(R, F, 3), src=i32(R, F))
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.pose_joints_dev(F, R, traj.data_ptr(), bodies, poses["flag"].data_ptr(), poses["quat"].data_ptr(), poses["R"].data_ptr(),
+                                 poses["t_pose"].data_ptr(), joints, axis_len, max_rms, max_rounds,
+                                 *[out[k].data_ptr() for k in core.JOINT_POSE_OUT])
+            core.smooth_tracks_dev(F, B, t.data_ptr(), out["t_pose"].data_ptr(), *par, out["pos"].data_ptr(), out["vel"].data_ptr(),
+                                   out["acc"].data_ptr(), ws["res"].data_ptr(), ws["n_tr"].data_ptr(), ws["flag_tr"].data_ptr())
+            core.smooth_rotations_dev(F, B, t.data_ptr(), out["quat"].data_ptr(), *par, out["quat_s"].data_ptr(),
+                                      out["omega"].data_ptr(), out["res_rot"].data_ptr(), ws["n_rot"].data_ptr(), out["flag_s"].data_ptr())
+            core.synchronize()                                # the mapped flag is torch's own arithmetic, on torch's stream
+            jointed = out["flag"] == capi.BP_JOINTED
+            out["flag_posed"] = torch.where(jointed, torch.full_like(out["flag"], capi.BP_POSED), out["flag"]).contiguous()
+            if fill:
+                torch.cuda.current_stream(dev).synchronize()
+                core.fill_rows_dev(F, R, traj.data_ptr(), bodies, out["flag_posed"].data_ptr(), out["R"].data_ptr(), out["t_pose"].data_ptr(),
+                                   out["flag_s"].data_ptr(), out["quat_s"].data_ptr(), out["pos"].data_ptr(), out["filled"].data_ptr(),
+                                   out["src"].data_ptr())
+                core.synchronize()
+                at, of = torch.from_numpy(owned).to(dev), torch.from_numpy(row_body[owned]).to(dev)
+                out["from_joint"] = torch.zeros((R, F), dtype=torch.bool, device=dev)
+                out["from_joint"][at] = (out["src"][at] == capi.BP_SRC_RIGID) & jointed[of]
+    return out
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
