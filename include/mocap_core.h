@@ -1273,6 +1273,94 @@ int mocap_pose_joints_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double*
                           double max_rms, int max_rounds, int32_t* d_flag_j, int32_t* d_hops, int32_t* d_via, double* d_quat_j,
                           double* d_Rm_j, double* d_t_j, double* d_rms_j);
 
+/* ---------------------------------------------------------------- skeleton fit (the core's own contract)
+ * All joints of a frame closed at once.  After mocap_pose_joints a POSED body ignores its joints and a JOINTED body sees one
+ * neighbour.  This stage fits every posed body of a frame together: the markers' residuals and, per joint, the weighted distance
+ * between the joint's two images, by a fixed number of Levenberg-Marquardt steps per frame.  Offline and opt-in: with nothing
+ * called nothing changes.  helpers.session_skeleton_fit is the glue.
+ *
+ * mocap_fit_skeleton[_dev]:
+ *   traj [R][F][3], R, n_frames F, and the bodies (B, n_markers, rows, markers; HOST memory) exactly as mocap_pose_joints takes
+ *     them; B in 2 .. MOCAP_BP_MAX_BODIES.
+ *   flag [B][F] i32, quat [B][F][4], t_pose [B][F][3]: mocap_pose_joints' flag_j, quat_j, t_j, or mocap_pose_rows' tables.  A
+ *     (body, frame) is ACTIVE iff its flag is MOCAP_BP_POSED or MOCAP_BP_JOINTED and its seven doubles are finite.
+ *   The joints, HOST memory in both forms, with mocap_pose_joints' rules and refusals (one check function serves both calls).
+ *   axis_len   metres, finite, > 0: how far along the axis a hinge's second virtual point lies
+ *   w_joint    finite, > 0: the weight of a virtual point's squared residual against a marker's
+ *   iters      1 .. MOCAP_SK_MAX_ITERS: the passes of the loop, all of them run
+ *   MOCAP_E_ARG, every output untouched, for anything else or a null buffer.
+ *   -> [B][F]: quat_s [4], Rm_s [9], t_s [3], rms_s;  [F]: cost0, cost f64, steps, n_act i32.
+ * All arithmetic is IEEE double, no fused operation, in the order written here; / and sqrt are correctly rounded; no
+ * trigonometric function.  Every byte of every output is written.  Two calls on the same input give the same bytes, and so do
+ * the host form and the "_dev" form (any NaN equal to any NaN).  No floating-point atomics (the sign walk's one 32-bit integer
+ * maximum in LDS, exact in any order).  Sums written "a + b + c" run left to right.
+ * Tables (host).  The root of a component of the forest is its lowest body; every other body has a parent, a depth (joints to
+ *   the root) and the joint to its parent.  The ELIMINATION ORDER is by (depth descending, body ascending).
+ * Per frame f, with q_b, t_b the current pose of body b (at the start quat and t_pose as given, not normalised):
+ *   R_b = the rigid-body section's quaternion -> R formula on q_b.  rot(R, p)_i = (R_i0 p_0 + R_i1 p_1) + R_i2 p_2.
+ *   Presence is stage 1's (traj[rows[b][m]][f] is three finite values).  A joint is ACTIVE iff both its bodies are.
+ *   A point of a body is (y, r, w): y its place relative to t_b in world axes, r its residual, w its weight.  In this order:
+ *     the present markers in ascending m: y = rot(R_b, markers[b][m]), r_i = (y_i + t_b,i) - x_i, w = 1;
+ *     then the body's active joints in ascending joint index, c, axis the joint's centre and axis in b's coordinates, and the
+ *     same with ' for the body on the other side: y0 = rot(R_b, c), W0_i = y0_i + t_b,i, u = rot(R_b, axis),
+ *     y1_i = y0_i + axis_len * u_i, W1_i = W0_i + axis_len * u_i; the first point is (y0, W0 - W0', w_joint), the second, under
+ *     HINGE only, (y1, W1 - W1', w_joint).
+ *   The body's terms, all starting at 0, per point:  S00 += w * (y1 y1 + y2 y2); S01 -= w * (y0 y1); S02 -= w * (y0 y2);
+ *     S11 += w * (y0 y0 + y2 y2); S12 -= w * (y1 y2); S22 += w * (y0 y0 + y1 y1); m_i += w * y_i; s += w;
+ *     g0 += w * (y1 r2 - y2 r1); g1 += w * (y2 r0 - y0 r2); g2 += w * (y0 r1 - y1 r0); g_3+i += w * r_i.
+ *   The body's own block H (6 x 6 symmetric; step = (omega, tau), a point moves by omega x y + tau, J = [-[y]x, I]), its diagonal
+ *     damped: H_kk = d + lam * d for d = S00, S11, S22, s, s, s; H10 = S01, H20 = S02, H21 = S12; H31 = m2, H32 = -m1, H40 = -m2,
+ *     H42 = m0, H50 = m1, H51 = -m0; every other entry 0.
+ *   The coupling C [child's rows][parent's columns] of an active joint between a body c and its parent p, over the joint's one or
+ *     two points k with yc_k, yp_k the y above on either side: E_k,ij = [i = j] ((yc0 yp0 + yc1 yp1) + yc2 yp2) - yp_i * yc_j
+ *     (off the diagonal -(yp_i * yc_j)); C_ij = -(w_joint * (E_0,ij [+ E_1,ij])) for i, j < 3; u = w_joint * (yc_0 [+ yc_1]),
+ *     v = w_joint * (yp_0 [+ yp_1]); C04 = u2, C05 = -u1, C13 = -u2, C15 = u0, C23 = u1, C24 = -u0; C31 = -v2, C32 = v1, C40 = v2,
+ *     C42 = -v0, C50 = -v1, C51 = v0; C33 = C44 = C55 = -(w_joint * n), n = 1 or 2; every other entry 0.
+ *   Cost shares: a body's = the sum over its present markers, ascending m, of (r0 r0 + r1 r1) + r2 r2; a joint's =
+ *     w_joint * e0 [+ w_joint * e1] with e_k the same expression of the joint's residuals taken from its child's side.  The
+ *     frame's cost = the active bodies' shares in ascending b, then the active joints' in ascending joint index, added to 0.
+ *   Solve.  Walk the elimination order; for an active body i: M = its own block, from which the complements of its active
+ *     children have been subtracted in elimination order; M = L D L^T without pivoting, "point refinement"'s rule at 6 x 6:
+ *     t_ik = a_ik - sum_{m<k} l_im t_km, l_ik = t_ik / d_k, d_i = a_ii - sum_{k<i} l_ik t_ik, each sum subtracted term by term in
+ *     ascending index.  x = M^-1 b: u_i = b_i - sum_{k<i} l_ik u_k; x_i = u_i / d_i - sum_{k>i} l_ki x_k, ascending k, i from 5
+ *     down.  z = M^-1 g.  If its parent p is active: W = M^-1 C column by column, and for the parent
+ *     H_rc -= ((C_0r W_0c + C_1r W_1c) + ... + C_5r W_5c) for r >= c, g_r -= ((C_0r z_0 + C_1r z_1) + ... + C_5r z_5).
+ *     Then in reverse order: delta_i = -(z_i + ((W_i0 delta_p,0 + W_i1 delta_p,1) + ...)) with an active parent, else -z_i.
+ *     An inactive body contributes nothing and cuts the tree: the subtrees on either side are solved as they stand.
+ *   Update (trial pose).  h = omega * 0.5; nd = sqrt(((1 + hx hx) + hy hy) + hz hz); d = (1 / nd, hx / nd, hy / nd, hz / nd);
+ *     q' = d (x) q (Hamilton's product, each component summed left to right in the order d_w, d_x, d_y, d_z), divided by
+ *     sqrt(((w w + x x) + y y) + z z); t' = t + tau.
+ *   Levenberg-Marquardt, "point refinement"'s rule at the scale of a frame: lam = 1e-3; exactly `iters` passes: the terms and the
+ *     cost at the current poses, the solve, the trial poses, the trial cost.  ACCEPT iff every pivot of every active body is
+ *     finite and > 0, cost0 is finite, and the trial cost is finite and < the current cost.  On accept the trial poses become
+ *     current, lam = lam / 10 and steps += 1; otherwise lam = lam * 10.  Accept and reject are selects.  A frame whose start cost
+ *     is not finite, or which has no active body, is so left as it came with steps = 0.
+ *   -> quat_s, t_s = the current pose; Rm_s = R of quat_s; rms_s = sqrt(share / k) over the body's k present markers at that
+ *     pose, NaN with k = 0; an inactive (body, frame) gets NaN in every double.  cost0 = the cost at the start, cost = at the
+ *     returned poses, steps = the accepted passes, n_act = the active joints.
+ *   Sign continuity.  quat_s then goes through stage 1's walk over the frames whose input flag is POSED or JOINTED.
+ * The caller keeps using its flag: with JOINTED read as POSED, Rm_s and t_s are tables mocap_fill_rows, mocap_find_joints and
+ * mocap_joint_series accept unchanged; quat_s and t_s are tables mocap_smooth_rotations and mocap_smooth_tracks accept.
+ * Four launches per pass (terms: one lane per (body, frame); solve: one lane per frame; trial cost; accept), the frames taken in
+ * rounds of whole tiles under a fixed workspace cap -- no result depends on where a round ends.  The "_dev" form enqueues on the
+ * context's stream (every pointer but the bodies and the joints device-accessible; no output may overlap an input) and does not
+ * wait; the host form uploads, runs and downloads.
+ * Out of scope: joint limits; a robust (Huber) cost; acceptance per component instead of per frame; a pose for a body that is
+ * not active at the start (a BALL joint and one marker); body geometry or joint centres as unknowns; the live loop; any change
+ * to an existing stage. */
+#define MOCAP_SK_MAX_ITERS 16
+int mocap_fit_skeleton(mocap_ctx* ctx, int64_t n_frames, int R, const double* traj, int B, const int32_t* n_markers, const int32_t* rows,
+                       const double* markers, const int32_t* flag, const double* quat, const double* t_pose, int J,
+                       const int32_t* body_a, const int32_t* body_b, const int32_t* kind, const double* c_a, const double* c_b,
+                       const double* axis_a, const double* axis_b, double axis_len, double w_joint, int iters, double* quat_s,
+                       double* Rm_s, double* t_s, double* rms_s, double* cost0, double* cost, int32_t* steps, int32_t* n_act);
+int mocap_fit_skeleton_dev(mocap_ctx* ctx, int64_t n_frames, int R, const double* d_traj, int B, const int32_t* n_markers,
+                           const int32_t* rows, const double* markers, const int32_t* d_flag, const double* d_quat,
+                           const double* d_t_pose, int J, const int32_t* body_a, const int32_t* body_b, const int32_t* kind,
+                           const double* c_a, const double* c_b, const double* axis_a, const double* axis_b, double axis_len,
+                           double w_joint, int iters, double* d_quat_s, double* d_Rm_s, double* d_t_s, double* d_rms_s,
+                           double* d_cost0, double* d_cost, int32_t* d_steps, int32_t* d_n_act);
+
 /* ---------------------------------------------------------------- point consolidation (the core's own contract)
  * Each blob supports at most one point.  The frame path reproduces the reference's find_point_correspondance_and_object_points,
  * in which a blob that is not the closest match of any root becomes a root of its own: one marker often comes back as two or three

@@ -66,6 +66,7 @@ JT_MAX_JOINTS = 64        # mocap_joint_series: joints of a call at most
 JT_UNSEEN, JT_SINGULAR, JT_FIXED, JT_HINGE, JT_BALL = 0, 1, 2, 3, 4   # mocap_find_joints: a pair's kind (include/mocap_core.h)
 BP_JOINTED = 16           # mocap_pose_joints: a (body, frame) posed through a joint, beside the BP_* flags above
 JP_MAX_ROUNDS = 16        # ... rounds (joints away from a POSED body) at most
+SK_MAX_ITERS = 16         # mocap_fit_skeleton: passes of the loop at most
 BAJ_MAX_CAMERAS = 16      # mocap_ba_joint_*: cameras at most
 BAJ_MAX_POINTS = 131072   # ... points at most
 BAJ_INFO = 12             # ... doubles of `info`
@@ -172,6 +173,10 @@ SIGNATURES = {
                                  _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_pose_joints_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_fit_skeleton": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl,
+                                  _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_fit_skeleton_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_fill_rows": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_fill_rows_dev": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocap_set_point_consolidation": (_i32, [_vp, _i32]),
@@ -1184,6 +1189,40 @@ class MocapCore:
                                                    _vp(d_quat), _vp(d_Rm), _vp(d_t_pose), J, *[_p(a) for a in arrays], float(axis_len),
                                                    float(max_rms), int(max_rounds), _vp(d_flag_j), _vp(d_hops), _vp(d_via),
                                                    _vp(d_quat_j), _vp(d_Rm_j), _vp(d_t_j), _vp(d_rms_j)))
+
+    # ------------------------------------------------------------------ skeleton fit (all joints of a frame closed at once)
+    SKELETON_FIT_OUT = ("quat", "R", "t_pose", "rms_s", "cost0", "cost", "steps", "n_act")
+
+    def fit_skeleton(self, traj, bodies, flag, quat, t_pose, joints, axis_len=0.1, w_joint=1.0, iters=8):
+        """mocap_fit_skeleton over host arrays: traj [R][F][3] and bodies as pose_rows takes them, flag [B][F], quat [B][F][4] and
+        t_pose [B][F][3] (pose_joints' or pose_rows' tables) and joints (see _joint_pose_arrays) -> {"quat" [B][F][4] (sign-continuous
+        over the POSED and JOINTED frames), "R" [B][F][3][3], "t_pose" [B][F][3], "rms_s" [B][F]: the fitted poses and each body's
+        marker rms under them (NaN for a body that was not posed at the start); "cost0", "cost" [F]: the frame's cost before and
+        after, "steps" [F]: accepted passes, "n_act" [F]: joints with both bodies posed}."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        Rr, F, _ = traj.shape
+        B, n, rows, q = self._session_bodies(bodies)
+        Bz = max(B, 1)
+        flag = np.ascontiguousarray(flag, dtype=np.int32).reshape(Bz, F)
+        quat = np.ascontiguousarray(quat, dtype=np.float64).reshape(Bz, F, 4)
+        t_pose = np.ascontiguousarray(t_pose, dtype=np.float64).reshape(Bz, F, 3)
+        J, *arrays = self._joint_pose_arrays(joints)
+        o = {"quat": np.zeros((Bz, F, 4)), "R": np.zeros((Bz, F, 3, 3)), "t_pose": np.zeros((Bz, F, 3)), "rms_s": np.zeros((Bz, F)),
+             "cost0": np.zeros(F), "cost": np.zeros(F), "steps": np.zeros(F, dtype=np.int32), "n_act": np.zeros(F, dtype=np.int32)}
+        self._check(self.lib.mocap_fit_skeleton(self._h, F, Rr, _p(traj), B, _p(n), _p(rows), _p(q), _p(flag), _p(quat), _p(t_pose), J,
+                                                *[_p(a) for a in arrays], float(axis_len), float(w_joint), int(iters),
+                                                *[_p(o[k]) for k in self.SKELETON_FIT_OUT]))
+        return o
+
+    def fit_skeleton_dev(self, n_frames, R, d_traj, bodies, d_flag, d_quat, d_t_pose, joints, axis_len, w_joint, iters, d_quat_s, d_Rm_s,
+                         d_t_s, d_rms_s, d_cost0, d_cost, d_steps, d_n_act):
+        """Device pointers (ints), shapes as fit_skeleton; bodies and joints: host data, as there."""
+        B, n, rows, q = self._session_bodies(bodies)
+        J, *arrays = self._joint_pose_arrays(joints)
+        self._check(self.lib.mocap_fit_skeleton_dev(self._h, int(n_frames), int(R), _vp(d_traj), B, _p(n), _p(rows), _p(q), _vp(d_flag),
+                                                    _vp(d_quat), _vp(d_t_pose), J, *[_p(a) for a in arrays], float(axis_len),
+                                                    float(w_joint), int(iters), _vp(d_quat_s), _vp(d_Rm_s), _vp(d_t_s), _vp(d_rms_s),
+                                                    _vp(d_cost0), _vp(d_cost), _vp(d_steps), _vp(d_n_act)))
 
     # ------------------------------------------------------------------ marker tracker (identities over time)
     def set_marker_tracker(self, gate=0.05, max_missed=5, vel_alpha=0.5, T_max=64):

@@ -1098,6 +1098,87 @@ def session_joint_poses(t, session, bodies, poses, joints, axis_len=0.1, max_rms
     return out
 
 
+def session_skeleton_fit(t, session, bodies, poses_j, joints, axis_len=0.1, w_joint=1.0, iters=8, degree=2, W=8, span=float("inf"),
+                         n_min=None, max_gap=0, fill=True):
+    """All joints of a frame closed at once ("skeleton fit", include/mocap_core.h): mocap_fit_skeleton over session["traj"], the
+    bodies, poses_j (session_joint_poses' dict, or session_body_poses') and joints (session_joints' dict or its list), then the
+    two smoothers over the fitted tables and, with fill, mocap_fill_rows.  NumPy or resident: resident arrays are read in place and
+    every result stays a torch tensor on that GPU.  Every body of a frame whose flag is BP_POSED or BP_JOINTED is fitted together
+    with the others: the markers' residuals and, per joint between two such bodies, w_joint times the squared distance between the
+    joint's two images (a hinge has a second point axis_len metres along its axis), by `iters` Levenberg-Marquardt passes.
+    Returns a dict shaped like session_joint_poses': {"flag": poses_j's own; "quat", "R", "t_pose": the fitted poses (NaN where the
+    body had none); "rms_s" [B][F]: each body's marker rms under them; "cost0", "cost" [F]: the frame's cost before and after;
+    "steps" [F]: accepted passes; "n_act" [F]: joints with both bodies posed; "hops", "via", "rms_j", "rms", "n_used", "present":
+    poses_j's own where it has them; "flag_posed" [B][F]: flag with JOINTED read as POSED; "pos", "vel", "acc", "quat_s", "omega",
+    "res_rot", "flag_s": the smoothers' results; with fill "filled" [R][F][3] and "src" [R][F]}.  session_joint_motion reads the
+    result directly."""
+    joints = joints["joints"] if isinstance(joints, dict) else list(joints)
+    if not joints:
+        raise ValueError("session_skeleton_fit: no joints")
+    for b, body in enumerate(bodies):
+        if not isinstance(body, dict) or "rows" not in body or "markers" not in body:
+            raise ValueError(f"session_skeleton_fit: body {b} has no 'rows': pass learn_session_bodies' list")
+    traj = session["traj"]
+    resident = getattr(traj, "is_cuda", False)
+    n_min = min(int(degree) + 2, 2 * int(W) + 1) if n_min is None else int(n_min)
+    par = (int(degree), int(W), float(span), n_min, int(max_gap))
+    B = len(bodies)
+    carried = {k: poses_j[k] for k in ("hops", "via", "rms_j", "rms", "n_used", "present") if k in poses_j}
+    with _state["lock"]:
+        core = get_core()
+        if not resident:
+            o = core.fit_skeleton(traj, bodies, poses_j["flag"], poses_j["quat"], poses_j["t_pose"], joints, axis_len=axis_len,
+                                  w_joint=w_joint, iters=iters)
+            flag = np.ascontiguousarray(poses_j["flag"], dtype=np.int32)
+            posed = np.where(flag == capi.BP_JOINTED, capi.BP_POSED, flag).astype(np.int32)
+            tr = core.smooth_tracks(t, o["t_pose"], *par)
+            rot = core.smooth_rotations(t, o["quat"], *par)
+            out = {**carried, **o, "flag": flag, "flag_posed": posed, "pos": tr["pos"], "vel": tr["vel"], "acc": tr["acc"],
+                   "quat_s": rot["quat_s"], "omega": rot["omega"], "res_rot": rot["res"], "flag_s": rot["flag"]}
+            if fill:
+                out.update(core.fill_rows(traj, bodies, posed, o["R"], o["t_pose"], rot["flag"], rot["quat_s"], tr["pos"]))
+        else:
+            import torch
+            R, F = traj.shape[0], traj.shape[1]
+            assert traj.dtype == torch.float64 and traj.is_contiguous() and traj.dim() == 3 and traj.shape[2] == 3
+            if traj.device.index != core.device_id:
+                raise ValueError(f"the session lives on {traj.device}, the core on GPU {core.device_id}: a resident session is read in place")
+            dev = traj.device
+            t = t if getattr(t, "is_cuda", False) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(dev)
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == F
+            for k, n, dt in (("flag", 1, torch.int32), ("quat", 4, torch.float64), ("t_pose", 3, torch.float64)):
+                a = poses_j[k]
+                assert a.is_cuda and a.device == dev and a.dtype == dt and a.is_contiguous() and a.numel() == B * F * n, k
+
+            def f64(*shape):
+                return torch.empty(shape, dtype=torch.float64, device=dev)
+
+            def i32(*shape):
+                return torch.empty(shape, dtype=torch.int32, device=dev)
+
+            flag = poses_j["flag"]
+            out = {**carried, "flag": flag, "quat": f64(B, F, 4), "R": f64(B, F, 3, 3), "t_pose": f64(B, F, 3), "rms_s": f64(B, F),
+                   "cost0": f64(F), "cost": f64(F), "steps": i32(F), "n_act": i32(F), "pos": f64(B, F, 3), "vel": f64(B, F, 3),
+                   "acc": f64(B, F, 3), "quat_s": f64(B, F, 4), "omega": f64(B, F, 3), "res_rot": f64(B, F), "flag_s": i32(B, F)}
+            ws = {"res": f64(B, F), "n_tr": i32(B, F), "flag_tr": i32(B, F), "n_rot": i32(B, F)}
+            if fill:
+                out.update(filled=f64(R, F, 3), src=i32(R, F))
+            out["flag_posed"] = torch.where(flag == capi.BP_JOINTED, torch.full_like(flag, capi.BP_POSED), flag).contiguous()
+            torch.cuda.current_stream(dev).synchronize()      # whatever torch itself still has queued on these buffers
+            core.fit_skeleton_dev(F, R, traj.data_ptr(), bodies, flag.data_ptr(), poses_j["quat"].data_ptr(), poses_j["t_pose"].data_ptr(),
+                                  joints, axis_len, w_joint, iters, *[out[k].data_ptr() for k in core.SKELETON_FIT_OUT])
+            core.smooth_tracks_dev(F, B, t.data_ptr(), out["t_pose"].data_ptr(), *par, out["pos"].data_ptr(), out["vel"].data_ptr(),
+                                   out["acc"].data_ptr(), ws["res"].data_ptr(), ws["n_tr"].data_ptr(), ws["flag_tr"].data_ptr())
+            core.smooth_rotations_dev(F, B, t.data_ptr(), out["quat"].data_ptr(), *par, out["quat_s"].data_ptr(),
+                                      out["omega"].data_ptr(), out["res_rot"].data_ptr(), ws["n_rot"].data_ptr(), out["flag_s"].data_ptr())
+            if fill:
+                core.fill_rows_dev(F, R, traj.data_ptr(), bodies, out["flag_posed"].data_ptr(), out["R"].data_ptr(), out["t_pose"].data_ptr(),
+                                   out["flag_s"].data_ptr(), out["quat_s"].data_ptr(), out["pos"].data_ptr(), out["filled"].data_ptr(),
+                                   out["src"].data_ptr())
+            core.synchronize()
+    return out
+
+
 def _bodies_core():
     """The registration lives in the context: a core handed over by set_core gets it on first use (callers hold the lock)."""
     core = get_core()
