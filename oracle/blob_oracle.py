@@ -68,13 +68,21 @@ def binary_mask(frame_bgr):
 
 def centroids_from_mask(mask):
     """helpers.py:147-156: one [x, y] per contour with non-zero area, in findContours' order."""
+    return contours_from_mask(mask)[1]
+
+
+def contours_from_mask(mask):
+    """The same, with what the mask-level tests compare besides: (number of contours found, the [x, y] list, per listed
+    contour the bounding box [x0, y0, x1, y1] (inclusive) of its vertex list)."""
     contours, _ = ci.find_contours(mask, ci.RETR_TREE, ci.CHAIN_APPROX_SIMPLE)
-    pts = []
+    pts, boxes = [], []
     for c in contours:
         m = ci.moments(c)
         if m["m00"] != 0:
             pts.append([int(m["m10"] / m["m00"]), int(m["m01"] / m["m00"])])
-    return pts
+            v = c.reshape(-1, 2)
+            boxes.append([int(v[:, 0].min()), int(v[:, 1].min()), int(v[:, 0].max()), int(v[:, 1].max())])
+    return len(contours), pts, boxes
 
 
 def find_dots(raw_frames, Ks, dists, rotations=None):

@@ -102,6 +102,7 @@ typedef struct {
   int parent, is_hole;
   long long a00, a10, a01;
   int first_child, next_sibling;
+  int bx0, by0, bx1, by1; /* bounding box of the border's pixels, original pixel coordinates */
 } contour_t;
 
 static const int DY8[8] = {0, -1, -1, -1, 0, 1, 1, 1};
@@ -115,6 +116,8 @@ static void fetch_contour(int32_t* img, int W, int y0, int x0, int nbd, int is_h
     x1 = x0 + DX8[s];
   } while (img[y1 * W + x1] == 0 && s != s_end);
   c->a00 = c->a10 = c->a01 = 0;
+  c->bx0 = c->bx1 = x0 - 1;
+  c->by0 = c->by1 = y0 - 1;
   if (s == s_end) {
     img[y0 * W + x0] = -nbd;
     return; /* single pixel: a one-vertex polygon, all sums 0 */
@@ -142,6 +145,10 @@ static void fetch_contour(int32_t* img, int W, int y0, int x0, int nbd, int is_h
       c->a00 += dxy;
       c->a10 += dxy * (px + qx);
       c->a01 += dxy * (py + qy);
+      if (qx < c->bx0) c->bx0 = (int)qx;
+      if (qx > c->bx1) c->bx1 = (int)qx;
+      if (qy < c->by0) c->by0 = (int)qy;
+      if (qy > c->by1) c->by1 = (int)qy;
     }
     if (y4 == y0 && x4 == x0 && y3 == y1 && x3 == x1) break;
     y3 = y4;
@@ -151,8 +158,10 @@ static void fetch_contour(int32_t* img, int W, int y0, int x0, int nbd, int is_h
 }
 
 /* mask [S][S] (0 / non-zero) -> centroids in cv.findContours(RETR_TREE) order, skipping m00 == 0.
-   Returns the number of centroids (all of them, even beyond cap); *n_contours = contours found. */
-static int centroids_from_mask(const uint8_t* mask, int S, int cap, float* out, int* n_contours) {
+   Returns the number of centroids (all of them, even beyond cap); *n_contours = contours found.
+   bbox (may be NULL): int16 [cap][4] = x0, y0, x1, y1 (inclusive, original pixel coordinates) over every border
+   pixel of the contour behind each kept centroid. */
+int bo_centroids_from_mask(const uint8_t* mask, int S, int cap, float* out, int* n_contours, int16_t* bbox) {
   const int W = S + 2;
   int32_t* img = (int32_t*)calloc((size_t)W * W, sizeof(int32_t));
   for (int y = 0; y < S; y++)
@@ -205,6 +214,12 @@ static int centroids_from_mask(const uint8_t* mask, int S, int cap, float* out, 
       if (count < cap) {
         out[2 * count] = (float)(int)(m10 / m00);
         out[2 * count + 1] = (float)(int)(m01 / m00);
+        if (bbox) {
+          bbox[4 * count] = (int16_t)c->bx0;
+          bbox[4 * count + 1] = (int16_t)c->by0;
+          bbox[4 * count + 2] = (int16_t)c->bx1;
+          bbox[4 * count + 3] = (int16_t)c->by1;
+        }
       }
       count++;
     }
@@ -218,6 +233,18 @@ static int centroids_from_mask(const uint8_t* mask, int S, int cap, float* out, 
   free(cs);
   free(img);
   return count;
+}
+
+/* The same over n masks [n][S][S]: counts_total[n] (not clipped), n_contours[n], out [n][cap][2], bbox [n][cap][4] or
+   NULL.  Slots at and beyond a mask's count are left as the caller filled them. */
+void bo_centroids_from_masks(const uint8_t* masks, int64_t n, int S, int cap, int32_t* counts_total, int32_t* n_contours,
+                             float* out, int16_t* bbox) {
+  for (int64_t i = 0; i < n; i++) {
+    int nc = 0;
+    counts_total[i] = bo_centroids_from_mask(masks + (size_t)i * S * S, S, cap, out + (size_t)i * cap * 2, &nc,
+                                             bbox ? bbox + (size_t)i * cap * 4 : NULL);
+    n_contours[i] = nc;
+  }
 }
 
 /* One raw frame [rows][cols][3] RGB -> processed BGR frame [S][S][3] (may be NULL), centroids. */
@@ -296,7 +323,7 @@ int bo_find_dots(const blob_cam* c, const uint8_t* raw, int M_max, float* blobs,
     mask[o] = grey > 51 ? 255 : 0;
   }
   int nc = 0;
-  const int n = centroids_from_mask(mask, S, M_max, blobs, &nc);
+  const int n = bo_centroids_from_mask(mask, S, M_max, blobs, &nc, NULL);
   if (n_contours) *n_contours = nc;
   free(sq);
   free(und);

@@ -48,6 +48,10 @@ def _load():
         L.bo_cam_destroy.argtypes = [vp]
         L.bo_find_dots.restype = i32
         L.bo_find_dots.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.bo_centroids_from_mask.restype = i32
+        L.bo_centroids_from_mask.argtypes = [vp, i32, i32, vp, vp, vp]
+        L.bo_centroids_from_masks.restype = None
+        L.bo_centroids_from_masks.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -107,6 +111,21 @@ class COracle:
         r = np.empty((P, N))
         _load().mo_ba_residuals(self._h, P, _p(params), N, _p(obs), _p(r))
         return r
+
+
+def contours_from_masks(masks, M_max, fill=0):
+    """masks [n][S][S] (0 / non-zero) -> counts_total i32 [n] (NOT clipped to M_max), n_contours i32 [n], blobs f32
+    [n][M_max][2], bbox i16 [n][M_max][4] (x0, y0, x1, y1 inclusive of the contour behind each kept centroid): the
+    sequential Suzuki-Abe scan of oracle/c/blob_oracle.c on bare masks.  Slots at and beyond a count hold `fill`."""
+    masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    n, S, S2 = masks.shape
+    assert S == S2 and M_max >= 1
+    counts = np.zeros(n, dtype=np.int32)
+    ncont = np.zeros(n, dtype=np.int32)
+    blobs = np.full((n, M_max, 2), fill, dtype=np.float32)
+    bbox = np.full((n, M_max, 4), fill, dtype=np.int16)
+    _load().bo_centroids_from_masks(_p(masks), n, S, int(M_max), _p(counts), _p(ncont), _p(blobs), _p(bbox))
+    return counts, ncont, blobs, bbox
 
 
 class BlobOracle:
