@@ -1984,6 +1984,112 @@ int mocap_undistort_points(mocap_ctx* ctx, int C, int64_t N, const double* in, c
 int mocap_undistort_points_dev(mocap_ctx* ctx, int C, int64_t N, const double* d_in, const double* K, const double* dist,
                                double* d_out);
 
+/* ---------------------------------------------------------------- predicted precision (the core's own contract)
+ * How well, in the caller's length unit, the rig CAN know a point.  Every quality number above is a reprojection error in px^2; this
+ * stage answers in metres: with independent pixel noise of standard deviation sigma_px in every view, the triangulated point's
+ * first-order covariance is sigma_px^2 H^-1, H = sum over the views of J^T J -- the normal matrix "point refinement" forms, evaluated
+ * at a given point with no observation and no iteration.  Opt-in and stateless: nothing is stored in the context, no other entry
+ * point changes a byte.  Three forms: named points, the points of a frame batch, and a voxel grid (the capture-volume map).
+ *
+ * Camera table.  P_c = K_c [R_c | t_c] of "point refinement", each camera with its own K, as built at mocap_set_cameras (MOCAP_E_NOCAMS
+ *   without).
+ * Caller's coordinates.  `frame`: 12 doubles, the row-major 3 x 4 matrix [A | a], or NULL for the identity: camera-0 coordinates are
+ *   X = A x + a for the caller's x.  The host folds it into a per-call table  P'_c = P_c [[A, a], [0, 1]]:
+ *     P'[r][j] = (P[r][0] A[0][j] + P[r][1] A[1][j]) + P[r][2] A[2][j]  (j < 3),
+ *     P'[r][3] = ((P[r][0] a[0] + P[r][1] a[1]) + P[r][2] a[2]) + P[r][3];      frame == NULL: P' = P byte for byte.
+ *   The kernels see P' and x alone: every result is in the caller's coordinates and no inverse of A is taken anywhere.  Every entry
+ *   of frame must be finite.
+ * One view at x = (X, Y, Z), camera table row P = P'_c (the expressions of "point refinement"):
+ *     a = P00 X + P01 Y + P02 Z + P03, b and w likewise from rows 1 and 2, each summed left to right;  pu = a / w, pv = b / w;
+ *     Ju[k] = (P0k - pu P2k) / w,  Jv[k] = (P1k - pv P2k) / w,  k < 3   (eight divisions per view).
+ *   The six entries of H (00 01 02 11 12 22) start at 0 and take, per view in ascending camera order,  H_ij = H_ij + Ju[i] Ju[j],  then
+ *   H_ij = H_ij + Jv[i] Jv[j].  There is no observation: no residual, no g, no cost.
+ * Which cameras are views.
+ *     named        bit c of seen[i] (uint64), c < C; higher bits are ignored.
+ *     frame path   corr[f][k][c] >= 0; the index itself is not read.
+ *     visibility   (seen == NULL, and always in the map)  camera c is a view iff  w is finite and w > 0,  w >= near and w <= far,
+ *                  0 <= pu and pu < width,  0 <= pv and pv < height -- comparisons of doubles (width, height converted), a NaN fails.
+ *                  near >= 0 and finite, far > near (far may be +inf), width, height >= 1;  read only in this form.
+ *   n_views = the number of views;  a named or frame-path view whose w is not finite or <= 0 still counts and sets MOCAP_PM_BAD_VIEW.
+ * Decomposition.  A = H as a full symmetric 3 x 3, V = identity; cyclic Jacobi by the rule "body trajectories" item 1 spells out
+ *   for Horn's matrix, with the index running 0 .. 2: at most MOCAP_PM_SWEEPS sweeps; a sweep begins with
+ *   off = (|A01| + |A02|) + |A12| and ends the iteration when off == 0; the pairs in the order 01, 02, 12; the skip rule, the g rule
+ *   from the fifth sweep, theta, t, cs, sn and the updates of A and V word for word.  lam = (A00, A11, A22) is then sorted ascending by
+ *   the network  (0,1) (1,2) (0,1):  a step (i, j) swaps lam_i, lam_j and columns i, j of V iff lam_i > lam_j.
+ * Outputs, per point / slot / voxel:
+ *     info      MOCAP_PM_OK, or the reasons below (0 only for a slot that holds no point)
+ *     n_views
+ *     sig[3]    ascending: sigma_px / sqrt(lam_2), sigma_px / sqrt(lam_1), sigma_px / sqrt(lam_0): the principal standard deviations
+ *     axis[3]   column 0 of V (the direction of sig[2]) as the iteration left it, not renormalised; negated when its component of
+ *               largest magnitude (the first among equals) is negative
+ *     cov[6]    packed like H:  s2 = sigma_px sigma_px, d_k = s2 / lam_k,
+ *               cov_ij = ((V_i0 V_j0) d_0 + (V_i1 V_j1) d_1) + (V_i2 V_j2) d_2
+ *   When info is not MOCAP_PM_OK every double is a quiet NaN.  Reasons (the first three are found in the one pass over the cameras and
+ *   may come together; DEGENERATE comes alone, the decomposition is made only without them):
+ *     MOCAP_PM_BAD_POINT    a coordinate of x is not finite
+ *     MOCAP_PM_BAD_VIEW     a named or frame-path view whose w is not finite or <= 0
+ *     MOCAP_PM_FEW_VIEWS    fewer than 2 views
+ *     MOCAP_PM_DEGENERATE   an eigenvalue that is not finite, or lam_0 <= lam_2 * 2^-40 (a point on the baseline of its only two
+ *                           cameras; a point at 1e200)
+ * All arithmetic is IEEE double, nothing fused, `/` and sqrt IEEE, in the order written.  Every output byte is written; the host form,
+ * the _dev form, a second call and a second stream give the same bits; no floating-point atomics.  The _dev forms enqueue on the
+ * context's stream and do not wait (frame, origin and e0 .. e2 are HOST pointers in both forms, read before the call returns).
+ *
+ * mocap_point_precision / _dev: N points xyz [N][3] (1 <= N <= MOCAP_PM_MAX_POINTS), seen [N] uint64 or NULL (by visibility; width,
+ *   height, near, far are read only then) -> cov [N][6] (may be NULL), sig [N][3], axis [N][3] (may be NULL), n_views [N] i32,
+ *   info [N] i32.
+ * mocap_frame_precision / _dev: xyz [F][K_max][3], corr [F][K_max][C], n_pts [F], status [F] (may be NULL) exactly as the frame path
+ *   wrote them (with a world transform set, pass its inverse as `frame`) -> the same outputs per slot [F][K_max].  The refinement's
+ *   skip rule: a frame with status & (MOCAP_ST_ROOT_OVERFLOW | MOCAP_ST_CAND_OVERFLOW | MOCAP_ST_HIT_OVERFLOW) or n_pts outside
+ *   0 .. K_max, and every slot >= n_pts[f], gets info = 0, n_views = 0 and NaN.  n_frames >= 0, K_max >= 1,
+ *   n_frames K_max <= MOCAP_PM_MAX_POINTS; n_frames == 0 returns 0 and touches nothing.
+ * mocap_coverage_map / _dev: voxel (i, j, k), i < nx fastest, sits at  x_d = ((origin_d + i e0_d) + j e1_d) + k e2_d  per component
+ *   (i, j, k converted to double); 1 <= nx, ny, nz <= MOCAP_PM_MAX_DIM, nx ny nz <= MOCAP_PM_MAX_VOXELS; views by visibility.
+ *     n_views [nz][ny][nx] u8    the visibility count, whatever the info
+ *     sig_max [nz][ny][nx] f32   sig[2] rounded to the nearest float32; NaN unless info is OK
+ *     seen    [nz][ny][nx] u64   the views' bits; may be NULL
+ *     summary [MOCAP_PM_SUMMARY] i64:  [0 .. 64] the number of voxels seen by exactly v cameras;  [65] the number of GOOD voxels -- OK,
+ *       n_views >= min_views and the double sig[2] <= max_sigma (min_views >= 0; max_sigma may be +inf, not NaN);  [66 .. 71] imin, imax,
+ *       jmin, jmax, kmin, kmax over the GOOD voxels, with none: every min the dimension, every max -1.  Integers only (per-workgroup
+ *       reduction, then integer atomics): independent of any order.
+ * mocap_precision_limits: MOCAP_PM_MAX_POINTS, MOCAP_PM_MAX_VOXELS, MOCAP_PM_SUMMARY (any pointer may be NULL).
+ * MOCAP_E_ARG, every output untouched, for: sigma_px not finite or <= 0; a frame entry that is not finite; N, n_frames, K_max, nx, ny,
+ *   nz or their product out of range; width, height, near, far against the rule above where they are read; min_views < 0; max_sigma
+ *   NaN; a null required buffer.
+ * Out of scope: lens distortion in the visibility test or the Jacobian, occlusion, per-blob pixel noise, the covariance of the
+ *   calibration itself, using the covariances as weights in the later stages. */
+#define MOCAP_PM_MAX_POINTS 16777216
+#define MOCAP_PM_MAX_VOXELS 134217728
+#define MOCAP_PM_MAX_DIM 1024
+#define MOCAP_PM_SUMMARY 72 /* int64 */
+#define MOCAP_PM_SWEEPS 16
+enum {
+  MOCAP_PM_OK = 1,          /* sig, axis and cov are the stage's */
+  MOCAP_PM_BAD_POINT = 2,   /* NaN: a coordinate that is not finite */
+  MOCAP_PM_BAD_VIEW = 4,    /* NaN: a named or frame-path view with a depth that is not finite or <= 0 */
+  MOCAP_PM_FEW_VIEWS = 8,   /* NaN: fewer than 2 views */
+  MOCAP_PM_DEGENERATE = 16  /* NaN: H has no usable inverse */
+};
+void mocap_precision_limits(int* max_points, int64_t* max_voxels, int* summary_len);
+int mocap_point_precision(mocap_ctx* ctx, int64_t N, const double* xyz, const uint64_t* seen, int width, int height, double near,
+                          double far, double sigma_px, const double* frame, double* cov, double* sig, double* axis, int32_t* n_views,
+                          int32_t* info);
+int mocap_point_precision_dev(mocap_ctx* ctx, int64_t N, const double* d_xyz, const uint64_t* d_seen, int width, int height, double near,
+                              double far, double sigma_px, const double* frame, double* d_cov, double* d_sig, double* d_axis,
+                              int32_t* d_n_views, int32_t* d_info);
+int mocap_frame_precision(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* xyz, const int16_t* corr, const int32_t* n_pts,
+                          const int32_t* status, double sigma_px, const double* frame, double* cov, double* sig, double* axis,
+                          int32_t* n_views, int32_t* info);
+int mocap_frame_precision_dev(mocap_ctx* ctx, int64_t n_frames, int K_max, const double* d_xyz, const int16_t* d_corr,
+                              const int32_t* d_n_pts, const int32_t* d_status, double sigma_px, const double* frame, double* d_cov,
+                              double* d_sig, double* d_axis, int32_t* d_n_views, int32_t* d_info);
+int mocap_coverage_map(mocap_ctx* ctx, int nx, int ny, int nz, const double* origin, const double* e0, const double* e1,
+                       const double* e2, int width, int height, double near, double far, double sigma_px, const double* frame,
+                       int min_views, double max_sigma, uint8_t* n_views, float* sig_max, uint64_t* seen, int64_t* summary);
+int mocap_coverage_map_dev(mocap_ctx* ctx, int nx, int ny, int nz, const double* origin, const double* e0, const double* e1,
+                           const double* e2, int width, int height, double near, double far, double sigma_px, const double* frame,
+                           int min_views, double max_sigma, uint8_t* d_n_views, float* d_sig_max, uint64_t* d_seen, int64_t* d_summary);
+
 #ifdef __cplusplus
 }
 #endif

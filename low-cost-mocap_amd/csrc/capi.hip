@@ -312,6 +312,7 @@ extern "C" int mocap_set_cameras(mocap_ctx* ctx, int C, const double* K, const d
   memcpy(K9, K, sizeof(double) * 9 * C);
   memcpy(K9 + nK9, Ptrue.data(), sizeof(double) * 12 * C);  // each camera's own K: the table of the point refinement
   ctx->hF.assign(F, F + nF);
+  ctx->hPown = Ptrue;
 
   // a frame call may be in flight on another stream of the same context: the mutex serialises
   // host calls; wait for queued device work before replacing the tables it reads.

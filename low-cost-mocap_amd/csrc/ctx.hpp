@@ -157,6 +157,9 @@ struct mocap_ctx {
   // camera resection (csrc/resect_capi.hip): rows, candidate table, mask and slab; pinned: the record of a linearisation, poses up
   DevBuf rs_ws;
   PinBuf rs_pin;
+  // predicted precision (csrc/precision_capi.hip): the host copy of the table behind d_Pown, and the per-call table P' on the device
+  std::vector<double> hPown;
+  DevBuf pm_tab;
 
   int fail(int code, const char* fmt, ...);
   int hip_fail(hipError_t e, const char* what);

@@ -91,6 +91,10 @@ RESECT_MAX_POINTS = 131072  # mocap_resect_*: rows at most
 RESECT_MAX_HYP = 4096     # ... hypotheses at most
 RESECT_INFO = 12          # ... doubles of `info`
 RESECT_OK, RESECT_TOO_FEW, RESECT_NO_MODEL = 0, 1, 2   # ... status: fewer than 4 valid rows / no candidate reaches min_inliers
+PM_MAX_POINTS, PM_MAX_VOXELS, PM_MAX_DIM = 1 << 24, 1 << 27, 1024   # mocap_point_precision / mocap_coverage_map: points, voxels, nx ny nz at most
+PM_SUMMARY = 72           # ... int64 entries of the map's summary: histogram [0..64], GOOD [65], imin imax jmin jmax kmin kmax [66..71]
+PM_SWEEPS = 16            # ... Jacobi sweeps at most
+PM_OK, PM_BAD_POINT, PM_BAD_VIEW, PM_FEW_VIEWS, PM_DEGENERATE = 1, 2, 4, 8, 16   # ... a point's info word (include/mocap_core.h)
 OPT_EXHAUSTIVE_WALK = 2
 OPT_BOUNDED_RESUBMIT = 4
 
@@ -240,6 +244,15 @@ SIGNATURES = {
     "mocap_ba_lens_solve": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _i32, _vp]),
     "mocap_undistort_points": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "mocap_undistort_points_dev": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "mocap_precision_limits": (None, [ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
+    "mocap_point_precision": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_point_precision_dev": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_frame_precision": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_frame_precision_dev": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocap_coverage_map": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _vp, _i32, _dbl, _vp, _vp, _vp,
+                                  _vp]),
+    "mocap_coverage_map_dev": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _dbl, _dbl, _dbl, _vp, _i32, _dbl, _vp, _vp,
+                                      _vp, _vp]),
 }
 
 _lib = None
@@ -1444,6 +1457,95 @@ class MocapCore:
     def triangulate_refined_dev(self, N, d_obs, iters, d_xyz, d_err=0, d_info=0):
         self._check(self.lib.mocap_triangulate_refined_dev(self._h, int(N), _vp(d_obs), int(iters), _vp(d_xyz), _vp(d_err or 0),
                                                            _vp(d_info or 0)))
+
+    # ------------------------------------------------------------------ predicted precision (point covariances, the capture-volume map)
+    @staticmethod
+    def _pm_frame(frame):
+        return None if frame is None else np.ascontiguousarray(frame, dtype=np.float64).reshape(12)
+
+    @staticmethod
+    def _pm_image(image_size):
+        return (0, 0) if image_size is None else (int(image_size[0]), int(image_size[1]))
+
+    def point_precision(self, xyz, seen=None, sigma_px=1.0, image_size=None, near=0.0, far=float("inf"), frame=None):
+        """mocap_point_precision: xyz [N][3] in the caller's coordinates (frame [3][4] = [A | a] takes them to camera 0's, None = they
+        are camera 0's); seen [N] uint64 view masks, or None = the cameras that see the point inside image_size = (width, height) and
+        near .. far -> {"cov" [N][6], "sig" [N][3] ascending, "axis" [N][3], "n_views" [N], "info" [N] (PM_*)}: sigma_px^2 H^-1."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        N = xyz.shape[0]
+        seen = None if seen is None else np.ascontiguousarray(seen, dtype=np.uint64).reshape(N)
+        frame = self._pm_frame(frame)
+        w, h = self._pm_image(image_size)
+        out = {"cov": np.empty((N, 6)), "sig": np.empty((N, 3)), "axis": np.empty((N, 3)), "n_views": np.empty(N, dtype=np.int32),
+               "info": np.empty(N, dtype=np.int32)}
+        self._check(self.lib.mocap_point_precision(self._h, N, _p(xyz), _p(seen), w, h, float(near), float(far), float(sigma_px), _p(frame),
+                                                   *[_p(out[k]) for k in self.PRECISION_OUT]))
+        return out
+
+    PRECISION_OUT = ("cov", "sig", "axis", "n_views", "info")
+
+    def point_precision_dev(self, N, d_xyz, d_seen, image_size, near, far, sigma_px, frame, d_cov, d_sig, d_axis, d_n_views, d_info):
+        """mocap_point_precision_dev: the arrays are device pointers (d_seen, d_cov, d_axis may be 0), frame a host array or None;
+        enqueued on the context's stream."""
+        frame = self._pm_frame(frame)
+        w, h = self._pm_image(image_size)
+        self._check(self.lib.mocap_point_precision_dev(self._h, int(N), _vp(d_xyz), _vp(d_seen or 0), w, h, float(near), float(far),
+                                                       float(sigma_px), _p(frame), _vp(d_cov or 0), _vp(d_sig), _vp(d_axis or 0),
+                                                       _vp(d_n_views), _vp(d_info)))
+
+    def frame_precision(self, xyz, corr, n_pts, status=None, sigma_px=1.0, frame=None):
+        """mocap_frame_precision over host arrays as the frame path wrote them (xyz [F][K_max][3], corr [F][K_max][C], n_pts [F],
+        status [F] or None) -> the outputs of point_precision per slot [F][K_max]; slots without a point: info 0, n_views 0, NaN."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        F, K_max = xyz.shape[:2]
+        corr = np.ascontiguousarray(corr, dtype=np.int16)
+        assert xyz.shape == (F, K_max, 3) and corr.shape == (F, K_max, self.C)
+        n_pts = np.ascontiguousarray(n_pts, dtype=np.int32).reshape(F)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(F)
+        frame = self._pm_frame(frame)
+        out = {"cov": np.empty((F, K_max, 6)), "sig": np.empty((F, K_max, 3)), "axis": np.empty((F, K_max, 3)),
+               "n_views": np.empty((F, K_max), dtype=np.int32), "info": np.empty((F, K_max), dtype=np.int32)}
+        self._check(self.lib.mocap_frame_precision(self._h, F, K_max, _p(xyz), _p(corr), _p(n_pts), _p(status), float(sigma_px), _p(frame),
+                                                   *[_p(out[k]) for k in self.PRECISION_OUT]))
+        return out
+
+    def frame_precision_dev(self, n_frames, K_max, d_xyz, d_corr, d_n_pts, d_status, sigma_px, frame, d_cov, d_sig, d_axis, d_n_views,
+                            d_info):
+        frame = self._pm_frame(frame)
+        self._check(self.lib.mocap_frame_precision_dev(self._h, int(n_frames), int(K_max), _vp(d_xyz), _vp(d_corr), _vp(d_n_pts),
+                                                       _vp(d_status or 0), float(sigma_px), _p(frame), _vp(d_cov or 0), _vp(d_sig),
+                                                       _vp(d_axis or 0), _vp(d_n_views), _vp(d_info)))
+
+    @staticmethod
+    def _pm_grid(origin, e0, e1, e2):
+        return [np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e0, e1, e2)]
+
+    def coverage_map(self, shape, origin, e0, e1, e2, image_size, near=0.0, far=float("inf"), sigma_px=1.0, frame=None, min_views=2,
+                     max_sigma=float("inf"), want_seen=False):
+        """mocap_coverage_map: shape = (nx, ny, nz); voxel (i, j, k) at origin + i e0 + j e1 + k e2 in the caller's coordinates ->
+        {"n_views" [nz][ny][nx] u8, "sig_max" [nz][ny][nx] f32, "seen" u64 (want_seen), "summary" [PM_SUMMARY] i64}."""
+        nx, ny, nz = (int(v) for v in shape)
+        g = self._pm_grid(origin, e0, e1, e2)
+        frame = self._pm_frame(frame)
+        w, h = self._pm_image(image_size)
+        n = (max(nz, 0), max(ny, 0), max(nx, 0))
+        out = {"n_views": np.empty(n, dtype=np.uint8), "sig_max": np.empty(n, dtype=np.float32),
+               "seen": np.empty(n, dtype=np.uint64) if want_seen else None, "summary": np.empty(PM_SUMMARY, dtype=np.int64)}
+        self._check(self.lib.mocap_coverage_map(self._h, nx, ny, nz, *[_p(v) for v in g], w, h, float(near), float(far), float(sigma_px),
+                                                _p(frame), int(min_views), float(max_sigma), _p(out["n_views"]), _p(out["sig_max"]),
+                                                _p(out["seen"]), _p(out["summary"])))
+        return out
+
+    def coverage_map_dev(self, shape, origin, e0, e1, e2, image_size, near, far, sigma_px, frame, min_views, max_sigma, d_n_views,
+                         d_sig_max, d_seen, d_summary):
+        """mocap_coverage_map_dev: the four outputs are device pointers (d_seen may be 0); the grid and frame are host arrays."""
+        nx, ny, nz = (int(v) for v in shape)
+        g = self._pm_grid(origin, e0, e1, e2)
+        frame = self._pm_frame(frame)
+        w, h = self._pm_image(image_size)
+        self._check(self.lib.mocap_coverage_map_dev(self._h, nx, ny, nz, *[_p(v) for v in g], w, h, float(near), float(far),
+                                                    float(sigma_px), _p(frame), int(min_views), float(max_sigma), _vp(d_n_views),
+                                                    _vp(d_sig_max), _vp(d_seen or 0), _vp(d_summary)))
 
     # ------------------------------------------------------------------ object filter (`filtered_objects`)
     def set_object_filter(self, num_objects, b=None, a=None, buffer_size=300, process_noise=1e-2, measurement_noise=1.0):

@@ -1953,3 +1953,137 @@ def undistort_image_points(image_points, camera_params=None):
         core = _ba_core()
     with _state["ba_lock"]:
         return core.undistort_points(obs, K, dist)
+
+
+# ----------------------------------------------------------------------------- predicted precision
+def precision_frame(to_world=None):
+    """The `frame` of "predicted precision" (include/mocap_core.h) for coordinates as the frame path returns them: None without a
+    world transform; with one -- x_w = swap_yz(dehom(T [diag(-1, -1, 1) X; 1])) -- the 3 x 4 matrix [A | a] with X = A x_w + a.  The
+    inverse is taken here, once per call, never in the core.  ValueError for a T whose last row is not (0, 0, 0, k), k != 0, or whose
+    linear part is singular."""
+    T = _state["to_world"] if to_world is None else to_world
+    if T is None:
+        return None
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    if not np.all(np.isfinite(T)) or T[3, 0] != 0.0 or T[3, 1] != 0.0 or T[3, 2] != 0.0 or T[3, 3] == 0.0:
+        raise ValueError("predicted precision needs an affine to-world matrix: last row (0, 0, 0, k) with k != 0")
+    swap = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, 1.0, 0.0]])
+    M = swap @ (T[:3, :3] / T[3, 3]) @ np.diag([-1.0, -1.0, 1.0])
+    m = swap @ (T[:3, 3] / T[3, 3])
+    if not np.linalg.matrix_rank(M) == 3:
+        raise ValueError("the to-world matrix's linear part is singular")
+    A = np.linalg.inv(M)
+    return np.concatenate([A, (-A @ m)[:, None]], axis=1)
+
+
+def _precision_out(core, like, shape):
+    """The five outputs of a precision call as tensors beside `like`."""
+    import torch
+    f64 = dict(dtype=torch.float64, device=like.device)
+    i32 = dict(dtype=torch.int32, device=like.device)
+    return {"cov": torch.empty(shape + (6,), **f64), "sig": torch.empty(shape + (3,), **f64), "axis": torch.empty(shape + (3,), **f64),
+            "n_views": torch.empty(shape, **i32), "info": torch.empty(shape, **i32)}
+
+
+def _resident_check(core, *tensors):
+    for a in tensors:
+        if a is not None and (not a.is_cuda or not a.is_contiguous() or a.device.index != core.device_id):
+            raise ValueError(f"a resident array must be contiguous and live on GPU {core.device_id}: it is read in place")
+
+
+def point_precision(object_points, seen=None, sigma_px=1.0, image_size=None, near=0.0, far=float("inf")):
+    """How well the rig can know each of object_points [N][3] (world coordinates when a world transform is set, camera 0's otherwise):
+    {"cov" [N][6] packed 00 01 02 11 12 22, "sig" [N][3] principal standard deviations ascending, "axis" [N][3] the worst direction,
+    "n_views", "info" (capi.PM_*)} for pixel noise sigma_px, in the points' own length unit.  seen: per point the bit mask of the
+    cameras that see it, or None = every camera that has it inside image_size = (width, height) between near and far.  NumPy in,
+    NumPy out; torch tensors on the core's GPU are read in place and answered with tensors."""
+    core = get_core()
+    frame = precision_frame()
+    if seen is None and image_size is None:
+        raise ValueError("point_precision needs seen or image_size")
+    if not getattr(object_points, "is_cuda", False):
+        with _state["lock"]:
+            return core.point_precision(object_points, seen, sigma_px, image_size, near, far, frame)
+    import torch
+    xyz = object_points
+    assert xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3
+    if seen is not None and not getattr(seen, "is_cuda", False):
+        seen = torch.from_numpy(np.ascontiguousarray(seen, dtype=np.uint64).view(np.int64)).to(xyz.device)
+    _resident_check(core, xyz, seen)
+    torch.cuda.current_stream(xyz.device).synchronize()      # whatever torch itself still has queued on these buffers
+    N = xyz.shape[0]
+    out = _precision_out(core, xyz, (N,))
+    with _state["lock"]:
+        core.point_precision_dev(N, xyz.data_ptr(), 0 if seen is None else seen.data_ptr(), image_size, near, far, sigma_px, frame,
+                                 *[out[k].data_ptr() for k in core.PRECISION_OUT])
+        core.synchronize()
+    return out
+
+
+def frame_precision(result, sigma_px=1.0):
+    """Predicted precision of every point of a frame batch: `result` is the dict the batch frame call returns ({"xyz" [F][K_max][3],
+    "corr" [F][K_max][C], "n_out" | "n_pts" [F], "status" [F] optional}), NumPy arrays or torch tensors on the core's GPU (read in
+    place) -> the outputs of point_precision per slot [F][K_max]; a slot without a point has info 0, n_views 0 and NaN."""
+    core = get_core()
+    frame = precision_frame()
+    xyz, corr = result["xyz"], result["corr"]
+    n_pts = result["n_pts"] if "n_pts" in result else result["n_out"]
+    status = result.get("status")
+    if not getattr(xyz, "is_cuda", False):
+        with _state["lock"]:
+            return core.frame_precision(np.asarray(xyz), np.asarray(corr), np.asarray(n_pts), None if status is None else np.asarray(status),
+                                        sigma_px, frame)
+    import torch
+    assert xyz.dtype == torch.float64 and xyz.dim() == 3 and xyz.shape[2] == 3
+    F, K_max = xyz.shape[:2]
+    assert corr.dtype == torch.int16 and tuple(corr.shape) == (F, K_max, core.C)
+    assert n_pts.dtype == torch.int32 and n_pts.numel() == F and (status is None or (status.dtype == torch.int32 and status.numel() == F))
+    _resident_check(core, xyz, corr, n_pts, status)
+    torch.cuda.current_stream(xyz.device).synchronize()
+    out = _precision_out(core, xyz, (F, K_max))
+    with _state["lock"]:
+        core.frame_precision_dev(F, K_max, xyz.data_ptr(), corr.data_ptr(), n_pts.data_ptr(), 0 if status is None else status.data_ptr(),
+                                 sigma_px, frame, *[out[k].data_ptr() for k in core.PRECISION_OUT])
+        core.synchronize()
+    return out
+
+
+def capture_volume(lo, hi, step, image_size, sigma_px=1.0, near=0.0, far=float("inf"), min_views=2, max_sigma=float("inf"),
+                   resident=False, want_seen=False):
+    """Where in the room the rig can track, and how precisely: the box lo .. hi (world coordinates when a world transform is set,
+    camera 0's otherwise) sampled every `step` (a number, or one per axis), n = floor((hi - lo) / step) + 1 voxels per axis from lo.
+    Returns {"n_views" [nz][ny][nx] u8, "sig_max" [nz][ny][nx] f32 (the worst principal standard deviation, NaN where the point has
+    none), "seen" (want_seen), "summary" [capi.PM_SUMMARY], "shape" (nx, ny, nz), "origin", "step",
+    "good_voxels", "good_volume" (good voxels x the voxel's volume, in the caller's cubic unit), "histogram" [65] (voxels seen by
+    exactly v cameras), "bbox" ((lo, hi) of the good voxels in coordinates, or None)}.  A voxel is GOOD when it has a covariance,
+    at least min_views views and sig_max <= max_sigma.  resident=True leaves the arrays on the GPU as torch tensors."""
+    core = get_core()
+    frame = precision_frame()
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    step = np.broadcast_to(np.asarray(step, dtype=np.float64), (3,)).copy()
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(np.isfinite(step)) and np.all(step > 0) and np.all(hi >= lo)):
+        raise ValueError("capture_volume needs finite lo <= hi and step > 0")
+    shape = tuple(int(v) for v in np.floor((hi - lo) / step + 1e-9) + 1)
+    e = np.diag(step)
+    if not resident:
+        with _state["lock"]:
+            out = core.coverage_map(shape, lo, e[0], e[1], e[2], image_size, near, far, sigma_px, frame, min_views, max_sigma, want_seen)
+        summary = out["summary"]
+    else:
+        import torch
+        dev = torch.device("cuda", core.device_id)
+        n = shape[::-1]
+        out = {"n_views": torch.empty(n, dtype=torch.uint8, device=dev), "sig_max": torch.empty(n, dtype=torch.float32, device=dev),
+               "seen": torch.empty(n, dtype=torch.int64, device=dev) if want_seen else None,
+               "summary": torch.empty(capi.PM_SUMMARY, dtype=torch.int64, device=dev)}
+        with _state["lock"]:
+            core.coverage_map_dev(shape, lo, e[0], e[1], e[2], image_size, near, far, sigma_px, frame, min_views, max_sigma,
+                                  out["n_views"].data_ptr(), out["sig_max"].data_ptr(), out["seen"].data_ptr() if want_seen else 0,
+                                  out["summary"].data_ptr())
+            core.synchronize()
+        summary = out["summary"].cpu().numpy()
+    good = int(summary[65])
+    box = summary[66:72].reshape(3, 2)
+    out.update(shape=shape, origin=lo, step=step, good_voxels=good, good_volume=good * float(np.prod(step)),
+               histogram=np.array(summary[:65]), bbox=None if not good else (lo + box[:, 0] * step, lo + box[:, 1] * step))
+    return out
